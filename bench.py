@@ -14,6 +14,7 @@ the CPU baseline (the oracle on all host cores, all 1024 queries, three repeats)
 --no-recall switch the extras off for experiments.
 
   python bench.py --gpus 1 --steps 10 --warmup 3
+  python bench.py --gpus 1 --steps 10 --warmup 3 --dump-outputs DIR     # + the last timed step's D / I as DIR/*.npy
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
          bench.py --gpus N --steps K --warmup W
 
@@ -40,6 +41,7 @@ SEED_C, SEED_X, SEED_Q = 1234, 10000, 999
 SIGMA, SIGMA_Q = 0.5, 0.1
 NCENTRES = 4096
 HBM_PEAK_GBS = 8000.0  # /opt/skills/guides/MI355X_MICROARCH.md: HBM3E 8 TB/s spec
+DUMP_BYTES = 64 << 20  # --dump-outputs: at most this much array data
 
 
 def log(*a):
@@ -78,7 +80,13 @@ def main():
                          "1/2/4/8 GPUs); weak = --n vectors PER GPU (N x --n in all; SURVEY 8(d) C5 asks for both curves)")
     ap.add_argument("--share-gpu", action="store_true",
                     help="dry run: rank r uses device r %% (visible GPUs) instead of requiring one GPU per rank (tests/test_gpu_bench_ranks.py)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one returned (rank 0: the merged result) to DIR: scores.npy "
+                         "(float32 [nq, k]), ids.npy (float64, exact below 2**53) and rows.npy (the query rows kept: all of them "
+                         "unless the arrays pass 64 MB, then a fixed, seeded sample)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(self_launch(args.gpus))
@@ -294,6 +302,8 @@ def main():
         scan_ms = index.get_timing("scan")
         scan_launches = index.get_timing("scan_launches")
         stages_in_timed_region = True
+    # what the last timed step returned, to the host now: the passes below search the same batches again
+    last_out = (out[0].cpu().numpy(), out[1].cpu().numpy()) if args.dump_outputs and rank == 0 else None
     fallbacks_timed = index.get_timing("fallback_queries") / max(1.0, index.get_timing("fast_queries"))
     if not stages_in_timed_region:
         index.set_param("profile", 1)
@@ -650,9 +660,26 @@ def main():
             "faiss_baseline": faiss_res,
         }
         print(json.dumps(res), flush=True)
+        if last_out is not None:
+            dump_outputs(args.dump_outputs, *last_out)
     if world > 1:
         dist.barrier()
         dist.destroy_process_group()
+
+
+def dump_outputs(path, D, I, seed=0):
+    """One search step's result as path/scores.npy (float32), path/ids.npy (float64) and path/rows.npy (float64: the query rows
+    kept).  Results larger than DUMP_BYTES keep a fixed, seeded sample of rows, so that two builds dump the same rows."""
+    os.makedirs(path, exist_ok=True)
+    nq, k = D.shape
+    rows = np.arange(nq)
+    keep = (DUMP_BYTES - 3 * 4096) // (k * (4 + 8) + 8)           # 4096: room for the three .npy headers
+    if nq > keep:
+        rows = np.sort(np.random.default_rng(seed).choice(nq, keep, replace=False))
+    np.save(os.path.join(path, "scores.npy"), np.ascontiguousarray(D[rows], dtype=np.float32))
+    np.save(os.path.join(path, "ids.npy"), np.ascontiguousarray(I[rows], dtype=np.float64))
+    np.save(os.path.join(path, "rows.npy"), rows.astype(np.float64))
+    log(f"dump-outputs: {len(rows)} of {nq} query rows x k = {k} of the last timed step -> {path}")
 
 
 def self_launch(n):

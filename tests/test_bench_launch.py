@@ -24,14 +24,17 @@ def test_bench_self_launches_its_ranks():
 def test_committed_bench_line_keeps_the_contract():
     """The newest full bench line under profiles/ (the driver's `python bench.py` on a GPU box, copied there by the evidence pass)
     carries every key of the bench contract, a roofline whose fraction is achieved / peak, and a CPU baseline that says what it
-    is.  bench.py cannot run without a GPU: this guards the line's SHAPE between GPU sessions."""
-    import glob
+    is.  bench.py cannot run without a GPU: this guards the line's SHAPE between GPU sessions.  "Newest" is the first bench line
+    profiles/INDEX.md lists (newest round first): file times say nothing in a fresh checkout."""
     import json
     import os
+    import re
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    files = sorted(glob.glob(os.path.join(root, "profiles", "r*_bench_ivfpq100M.json")), key=os.path.getmtime)
-    assert files, "no committed bench line under profiles/"
-    lines = [l for l in open(files[-1]) if l.startswith("{")]
+    names = re.findall(r"`(r\w+_bench_ivfpq100M\.json)`", open(os.path.join(root, "profiles", "INDEX.md")).read())
+    assert names, "profiles/INDEX.md lists no bench line"
+    newest = os.path.join(root, "profiles", names[0])
+    assert os.path.exists(newest), f"profiles/INDEX.md lists {names[0]}, which is not committed"
+    lines = [l for l in open(newest) if l.startswith("{")]
     assert len(lines) == 1, "the bench prints ONE JSON line"
     j = json.loads(lines[0])
     for key in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline", "dtype",
@@ -58,3 +61,33 @@ def test_committed_bench_line_keeps_the_contract():
         assert leg["exact_fallback_queries_per_step"] == 0 and leg["oracle_parity_ids_and_scores"] is True, name
         assert leg["ms_per_step"] < 2 * j["ms_per_step"], (name, leg["ms_per_step"])       # no distribution slower than 2x the headline
     assert od["informative"]["recall_by_nprobe"]["nprobe32"]["recall_at_10"] > od["informative"]["recall_by_nprobe"]["nprobe1"]["recall_at_10"]
+
+
+def test_bench_refuses_zero_timed_steps():
+    """--steps is the number of timed steps: zero of them has no time and no last step to report."""
+    r = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--steps", "0"], capture_output=True, text=True, timeout=120)
+    assert r.returncode == 2 and "--steps must be >= 1" in r.stderr, r.stderr
+
+
+def test_dump_outputs_writes_the_step_result(tmp_path, monkeypatch):
+    """bench.py --dump-outputs: scores as float32, ids as float64, every query row of a small result; a result over the byte
+    cap keeps the same seeded sample of rows every time, under the cap."""
+    import numpy as np
+    import bench
+    rng = np.random.default_rng(3)
+    D = rng.standard_normal((1024, 10)).astype(np.float32)
+    I = rng.integers(-1, 10 ** 11, size=(1024, 10), dtype=np.int64)
+    bench.dump_outputs(str(tmp_path / "all"), D, I)
+    s, i, rows = (np.load(tmp_path / "all" / f) for f in ("scores.npy", "ids.npy", "rows.npy"))
+    assert s.dtype == np.float32 and i.dtype == np.float64 and rows.dtype == np.float64
+    assert np.array_equal(s, D) and np.array_equal(i.astype(np.int64), I) and np.array_equal(rows, np.arange(1024))
+    monkeypatch.setattr(bench, "DUMP_BYTES", 64 << 10)
+    for name in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / name), D, I)
+    ra = np.load(tmp_path / "a" / "rows.npy").astype(np.int64)
+    assert 0 < len(ra) < 1024 and np.array_equal(ra, np.unique(ra))
+    assert sum(os.path.getsize(tmp_path / "a" / f) for f in ("scores.npy", "ids.npy", "rows.npy")) <= 64 << 10
+    for f in ("scores.npy", "ids.npy", "rows.npy"):
+        assert np.array_equal(np.load(tmp_path / "a" / f), np.load(tmp_path / "b" / f)), f
+    assert np.array_equal(np.load(tmp_path / "a" / "scores.npy"), D[ra])
+    assert np.array_equal(np.load(tmp_path / "a" / "ids.npy").astype(np.int64), I[ra])

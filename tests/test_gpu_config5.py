@@ -4,9 +4,10 @@ Same index parameters and batch as the headline (M = 96, nbits 8, nlist 4096, np
 shards of 200k vectors each (1.6M vectors instead of 1B), through both multi-GPU forms:
 
   * `rsx_sharded_create` with 8 shards (one process; on a 1-GPU box the shards share cuda:0, on a node one per device),
-  * `sharded.ShardedSearcher` with 8 real ranks (one process per shard; RCCL refuses several ranks per device, so on this
-    box the ranks share cuda:0 and the ONE all_gather_into_tensor runs over gloo — the collective call and the merge are
-    the ones `bench.py --gpus 8` issues over RCCL).
+  * `sharded.ShardedSearcher` with 4 real ranks holding two of the shards each in a two-shard handle (at most six processes
+    may hold the GPU at once, the test process among them, so one process per shard is not possible on one box; RCCL refuses
+    several ranks per device, so the ranks share cuda:0 and the ONE all_gather_into_tensor runs over gloo — the collective
+    call and the merge are the ones `bench.py --gpus N` issues over RCCL).
 
 Bar: ids AND fp32 scores of all 1024 queries equal to the single index holding everything (a sharded index is a partition
 of the same logical index) and to the CPU oracle run on the lists exported from the single index.
@@ -23,6 +24,7 @@ pytestmark = pytest.mark.gpu
 
 D, NLIST, M, NPROBE, NQ, K = 768, 4096, 96, 32, 1024, 10
 NSHARDS, PER_SHARD = 8, 200_000
+NRANKS = 4                  # processes of the ShardedSearcher form, NSHARDS // NRANKS shards each
 N = NSHARDS * PER_SHARD
 NCENT, SEED_C, SEED_X, SEED_Q = 4096, 1234, 10000, 999
 N_TRAIN = 262_144           # 64 points per centroid: a test-sized training set (the bench uses 256 per centroid)
@@ -124,11 +126,13 @@ def _rank(rank, world, port, params_path, ret):
     dev = torch.device("cuda", rank % ndev)
     torch.cuda.set_device(dev)
     p = np.load(params_path)
-    local = rsx.IndexIVFPQ(None, D, NLIST, M, 8, rsx.METRIC_INNER_PRODUCT, device=rank % ndev)
+    per_rank = NSHARDS // world
+    local = rsx.IndexIVFPQ(None, D, NLIST, M, 8, rsx.METRIC_INNER_PRODUCT, devices=[rank % ndev] * per_rank)
+    assert local.nshards == per_rank
     local.set_centroids(p["cen"]); local.set_codebooks(p["cb"])
     local.nprobe = NPROBE
     lo, hi = shard_range(N, rank, world)
-    assert hi - lo == PER_SHARD
+    assert hi - lo == per_rank * PER_SHARD          # the handle cuts the add into per_rank of the eight id-range shards
     x = torch.empty((hi - lo, D), dtype=torch.float16, device=dev)
     rsx.synth_vectors(D, NCENT, SEED_C, SEED_X, 0.5, lo, hi - lo, out=x, device=rank % ndev)
     local.add(x)
@@ -140,7 +144,7 @@ def _rank(rank, world, port, params_path, ret):
     dist.destroy_process_group()
 
 
-def test_config5_eight_ranks_sharded_searcher(gpu, tmp_path):
+def test_config5_eight_shards_on_four_ranks(gpu, tmp_path):
     import torch
     import torch.multiprocessing as mp
     dev = torch.device("cuda", 0)
@@ -156,11 +160,11 @@ def test_config5_eight_ranks_sharded_searcher(gpu, tmp_path):
     np.savez(params, cen=cen, cb=cb)
     with mp.Manager() as m:
         ret = m.dict()
-        mp.spawn(_rank, args=(NSHARDS, _free_port(), params, ret), nprocs=NSHARDS, join=True)
+        mp.spawn(_rank, args=(NRANKS, _free_port(), params, ret), nprocs=NRANKS, join=True)
         got = dict(ret)
-    assert set(got) == set(range(NSHARDS))
-    for r in range(NSHARDS):                      # every rank holds the merged result, and it is the single index's
-        assert_same_results(got[r][0], got[r][1], Ds, Is, f"config 5: rank {r} of 8, merged result vs single index")
+    assert set(got) == set(range(NRANKS))
+    for r in range(NRANKS):                       # every rank holds the merged result, and it is the single index's
+        assert_same_results(got[r][0], got[r][1], Ds, Is, f"config 5: rank {r} of {NRANKS}, merged result vs single index")
 
 
 def test_headline_size_100M_parity_and_invariants(gpu, orc):

@@ -154,19 +154,22 @@ def test_indexer_facade_spans_devices(gpu, orc, tmp_path, index_type):
 
 
 def test_two_real_gpus(gpu):
-    """One shard per visible device, device-resident queries on the last device (peer copies of queries and results)."""
-    if gpu.get_num_gpus() < 2:
-        pytest.skip("needs >= 2 visible GPUs (the 1-GPU box covers the same code with shards sharing device 0)")
+    """One shard per visible device, device-resident vectors and queries on the last device (peer copies of rows, queries and
+    results).  Every box runs it: with one visible GPU the handle keeps two shards, both on device 0, so the fan-out, the
+    fan-in and the merge still run and only the copies stay on the device."""
     import torch
     ng = gpu.get_num_gpus()
+    devices = [r % ng for r in range(max(2, ng))]
+    last = devices[-1]
     d, n, nq, k = 128, 40000, 64, 10
     x, q = _data(gpu, d, n, nq)
     single = gpu.IndexIVFPQ(None, d, 16, 32, 8, 0, device=0)
-    sh = gpu.IndexIVFPQ(None, d, 16, 32, 8, 0, devices=list(range(ng)))
+    sh = gpu.IndexIVFPQ(None, d, 16, 32, 8, 0, devices=devices)
+    assert sh.nshards == len(devices)
     single.train(x[:8000]); sh.set_centroids(single.get_centroids()); sh.set_codebooks(single.get_codebooks())
-    single.add(x); sh.add(torch.from_numpy(x).to(f"cuda:{ng - 1}"))
+    single.add(x); sh.add(torch.from_numpy(x).to(f"cuda:{last}"))
     single.nprobe = sh.nprobe = 4
     Ds, Is = single.search(q, k)
-    Dm, Im = sh.search(torch.from_numpy(q).to(f"cuda:{ng - 1}"), k)
-    assert Dm.device.index == ng - 1
-    assert_same_results(Dm.cpu().numpy(), Im.cpu().numpy(), Ds, Is, f"{ng} real GPUs")
+    Dm, Im = sh.search(torch.from_numpy(q).to(f"cuda:{last}"), k)
+    assert Dm.device.index == last
+    assert_same_results(Dm.cpu().numpy(), Im.cpu().numpy(), Ds, Is, f"{len(devices)} shards on devices {devices}")
