@@ -223,6 +223,39 @@ int rsx_set_param(rsx_index_t* h, const char* key, double value);
  * "scanned_vectors".  Used by bench.py for the roofline object. */
 int rsx_get_timing(rsx_index_t* h, const char* key, double* ms);
 
+/* ---- filtered search (FAISS SearchParameters with an IDSelector) ------------------- */
+
+/* faiss.IDSelector* (FAISS 1.8.0 impl/IDSelector.h): the ids a search may return.  Pure host object: needs no GPU.
+ *   RSX_SEL_RANGE  faiss.IDSelectorRange(lo, hi)      ids in [lo, hi)                              (data, n ignored)
+ *   RSX_SEL_BATCH  faiss.IDSelectorBatch(n, data)     the n int64 ids at data; duplicates allowed   (lo, hi ignored)
+ *   RSX_SEL_BITMAP faiss.IDSelectorBitmap(n, data)    n bytes at data: id i is selected when 0 <= i < 8 n and
+ *                                                     bit (i & 7), least significant first, of byte i >> 3 is set
+ *   invert != 0    faiss.IDSelectorNot(sel)           the complement of the above
+ * data is a HOST or DEVICE pointer; it is copied, nothing is retained.  The reference has no filtered search: its
+ * datastore subsampling (src/search.py:493-500) and decontamination (src/search.py:519-523) drop documents after it. */
+enum rsx_selector_kind { RSX_SEL_RANGE = 0, RSX_SEL_BATCH = 1, RSX_SEL_BITMAP = 2 };
+typedef struct rsx_selector rsx_selector_t;
+int rsx_selector_create(int kind, const void* data, int64_t n, int64_t lo, int64_t hi, int invert, rsx_selector_t** out);
+int rsx_selector_destroy(rsx_selector_t* sel);
+/* sel.is_member(id) for n ids (host pointers): out[i] = 0 / 1.  Host code, no GPU. */
+int rsx_selector_is_member(const rsx_selector_t* sel, int64_t n, const int64_t* ids, uint8_t* out);
+
+/* index.search(x, k, params=faiss.SearchParameters(sel=sel))           (Flat)
+ * index.search(x, k, params=faiss.SearchParametersIVF(sel=sel, nprobe=p)) (IVF-Flat / IVF-PQ)
+ * Returns exactly what rsx_search returns on an index holding only the selected vectors (same trained parameters, ids
+ * and insertion order); slots that cannot be filled get I = -1 and D = -inf (IP) / +inf (L2).  sel may be NULL (no
+ * selection).  nprobe_override > 0 replaces the handle's nprobe for this call only (IVF; ignored by Flat); 0 keeps it.
+ * A filtered search takes the routes whose scans write complete score rows, the unselected rows masked out of them (DESIGN.md
+ * section 7b); the slot mask of a selector is built once per (selector, index state) and cached on the handle: rsx_get_timing
+ * "sel_mask_builds", "sel_mask_ms", "filtered_queries".
+ * Sharded handles apply the selector, over the logical index's ids, to every shard. */
+int rsx_search_sel(rsx_index_t* h, int64_t nq, const void* q, int dtype, int k, const rsx_selector_t* sel,
+                   int nprobe_override, float* D, int64_t* I);
+/* rsx_search_prepass with a selector and an nprobe override (rsx_search_scan finishes it).  The filtered search has no
+ * threshold pre-pass: *tau_dev = NULL, *ntau = 0 whenever sel is not NULL. */
+int rsx_search_prepass_sel(rsx_index_t* h, int64_t nq, const void* q, int dtype, int k, const rsx_selector_t* sel,
+                           int nprobe_override, float* D, int64_t* I, uint64_t** tau_dev, int64_t* ntau);
+
 /* ---- persistence ------------------------------------------------------------------- */
 
 /* faiss.write_index(index, path) / faiss.read_index(path)

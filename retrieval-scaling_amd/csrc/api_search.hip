@@ -1,5 +1,6 @@
 // api_search.hip — the search drivers: search_batch (one internal batch: coarse quantiser, probe selection, table build, threshold
 // pre-pass, scan, selection, exact re-rank, certificate fallbacks) and search_impl (one rsx_search call).  Shared declarations: rsx_host.h.
+#include <chrono>
 #include <cstring>
 #include "rsx_host.h"
 
@@ -49,6 +50,14 @@ static void kp_for(const rsx_index* h, int k, bool fast, int& KP, int& BUF) {
     else want = k + std::max(8, k / 16);
     KP = std::max(16, pow2ceil(want));
     BUF = std::max(2 * KP, (h->kind == KIND_IVFPQ && fast) ? 512 : 256);
+}
+
+// filtered search (h->sel): -inf over the unselected columns of Flat score rows [nq, tstride] whose column c is slot slot0 + c
+static void sel_apply_flat(rsx_index* h, float* temp, int64_t tstride, int64_t nq, int64_t n, int64_t slot0) {
+    if (!h->sel) return;
+    SelApplyArgs sa{};
+    sa.temp = temp; sa.tstride = tstride; sa.nq = nq; sa.mask = h->sel_mask.as<uint32_t>(); sa.flat_n = n; sa.slot0 = slot0;
+    launch_sel_apply(sa, h->st);
 }
 
 // top-k of `nrows` rows of fp32 scores (row r valid length: row_n or n_uniform) into state [nrows, KP]
@@ -358,6 +367,7 @@ static void search_batch(rsx_index* h, int64_t nq, const void* dq, int dtype, in
             ea.X = h->data.p; ea.x_f16 = h->storage_f16; ea.ld = ld; ea.flat_n = N;
             ea.temp = h->w_temp.as<float>(); ea.tstride = tstride;
             launch_exact_scores(ea, h->st);
+            sel_apply_flat(h, h->w_temp.as<float>(), tstride, nq, N, 0);      // filtered search: the unselected rows leave the score rows
             tm.mark("scan");
             select_rows(h, h->w_temp.as<float>(), tstride, nullptr, 0, N, 0, nq, KP, BUF, KP, state, false);
             tm.mark("select");
@@ -377,6 +387,7 @@ static void search_batch(rsx_index* h, int64_t nq, const void* dq, int dtype, in
             a.max_chunks = (int)((round_up(N, 16) + a.chunk_rows - 1) / a.chunk_rows);
             if (a.max_chunks > 65535) { a.chunk_rows = (int)round_up((round_up(N, 16) + 65534) / 65535, 64); a.max_chunks = (int)((round_up(N, 16) + a.chunk_rows - 1) / a.chunk_rows); }
             launch_list_scan(a, h->st);
+            sel_apply_flat(h, h->w_temp.as<float>(), tstride, nq, N, 0);
             tm.mark("scan");
             // threshold = the KP-th approximate key (not the k-th): the exact re-rank needs the true top-KP
             select_rows(h, h->w_temp.as<float>(), tstride, nullptr, 0, N, 0, nq, KP, BUF, KP, state, false);
@@ -391,6 +402,7 @@ static void search_batch(rsx_index* h, int64_t nq, const void* dq, int dtype, in
                 int64_t nv = std::min<int64_t>(CH, vend - v0);
                 launch_flat_gemm(h->w_q16.as<__half>(), (int)nq_pad, h->data.p, h->storage_f16, v0, nv, ld, bias,
                                  h->w_temp.as<float>(), CH, h->st);
+                sel_apply_flat(h, h->w_temp.as<float>(), CH, nq, nv, v0);
                 select_rows(h, h->w_temp.as<float>(), CH, nullptr, 0, nv, (uint32_t)v0, nq, KP, BUF, KP, state, true);
             };
             // Threshold phase: the K'-th key of the first rows is a threshold for everything behind them, so a filtered pass over
@@ -1005,6 +1017,17 @@ static void search_batch(rsx_index* h, int64_t nq, const void* dq, int dtype, in
             tm.mark("scan");
         }
     }
+    if (h->sel) {
+        // filtered search (search_impl turned the in-scan candidate filters off): the scans above wrote complete score rows —
+        // approximate (certified fast scans) or exact — and the unselected rows leave them before the selection
+        if (filtered) RSX_THROW(RSX_ERR_INVALID, "filtered search reached a scan without score rows");
+        SelApplyArgs sa{};
+        sa.temp = h->w_temp.as<float>(); sa.tstride = tmax; sa.nq = nq; sa.mask = h->sel_mask.as<uint32_t>(); sa.flat_n = -1;
+        sa.probe_list = h->w_probelist.as<int32_t>(); sa.seg_start = h->w_segstart.as<int64_t>(); sa.nprobe = nprobe;
+        sa.list_base = h->d_base.as<int64_t>(); sa.list_len = h->d_len.as<int64_t>();
+        launch_sel_apply(sa, h->st);
+        tm.mark("sel_apply");
+    }
     // IVF-PQ, rotated layout, threshold by construction: finalize straight from the complete candidate row (k_pq_final_tab) when K'
     // is large or a table entry is a long chain (M = 16: dsub 48) — the K' cut, its certificate and the second chance disappear
     const int tabP = (fast && filtered && fused_pre_used && rot && h->pq_final_tab != 0) ? pq_final_tab_capacity(h->M, h->CB, k) : 0;
@@ -1129,6 +1152,33 @@ __global__ void k_bias_from_norms(const float* norms, float* bias, int64_t n) {
     if (i < n) bias[i] = -0.5f * norms[i];
 }
 
+// The slot mask of h->sel over the handle's storage (k_sel_mask), rebuilt only when the selector or the index state changed: every
+// add / add_list / reset / re-layout bumps dir_gen (upload_dir), and a re-layout also moves the storage.
+static void ensure_sel_mask(rsx_index* h) {
+    const rsx_selector* s = h->sel;
+    if (h->sel_mask.p && h->sel_mask_serial == s->serial && h->sel_mask_gen == h->dir_gen && h->sel_mask_of == h->data.p) return;
+    const int64_t nslots = std::max<int64_t>(h->total_cap, h->ntotal);
+    h->sel_mask.ensure((size_t)std::max<int64_t>(1, sel_mask_words(nslots)) * 4);
+    const auto t0 = std::chrono::steady_clock::now();
+    SelDevArgs a{};
+    a.kind = s->kind; a.invert = s->invert; a.lo = s->lo; a.hi = s->hi;
+    const size_t bytes = s->kind == RSX_SEL_BITMAP ? s->bitmap.size() : s->kind == RSX_SEL_BATCH ? s->ids.size() * 8 : 0;
+    if (bytes) {
+        const void* src = s->kind == RSX_SEL_BITMAP ? (const void*)s->bitmap.data() : (const void*)s->ids.data();
+        h->sel_dev.ensure(bytes);
+        HIPCHECK(hipMemcpyAsync(h->sel_dev.p, src, bytes, hipMemcpyHostToDevice, h->st));
+    }
+    a.bitmap = s->kind == RSX_SEL_BITMAP ? h->sel_dev.as<uint8_t>() : nullptr; a.nbytes = (int64_t)s->bitmap.size();
+    a.ids = s->kind == RSX_SEL_BATCH ? h->sel_dev.as<int64_t>() : nullptr; a.nids = (int64_t)s->ids.size();
+    const int64_t* slot_ids = (h->kind == KIND_FLAT && !h->custom_ids) ? nullptr : h->ids.as<int64_t>();     // (as k_finalize reads them)
+    launch_sel_mask(a, slot_ids, nslots, h->sel_mask.as<uint32_t>(), h->st);
+    HIPCHECK(hipStreamSynchronize(h->st));      // (the selector's host arrays may go away after the call)
+    HIPCHECK(hipGetLastError());
+    h->sel_mask_serial = s->serial; h->sel_mask_gen = h->dir_gen; h->sel_mask_of = h->data.p;
+    h->timing["sel_mask_builds"] += 1;
+    h->timing["sel_mask_ms"] += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+}
+
 void search_impl(rsx_index* h, int64_t nq, const void* q, int dtype, int k, float* D, int64_t* I) {
     if (nq < 0 || k <= 0) RSX_THROW(RSX_ERR_INVALID, "search: nq=%lld k=%d", (long long)nq, k);
     if (k > 4096) RSX_THROW(RSX_ERR_UNSUPPORTED, "search: k = %d exceeds this build's maximum of 4096 (the reference backends' default k)", k);
@@ -1152,6 +1202,16 @@ void search_impl(rsx_index* h, int64_t nq, const void* q, int dtype, int k, floa
         hipLaunchKernelGGL(k_bias_from_norms, dim3((unsigned)((rows + 255) / 256)), dim3(256), 0, h->st, h->norms.as<float>(),
                            h->w_misc.as<float>(), rows);
     }
+    // A filtered search takes the routes whose scans write complete score rows: the in-scan candidate filters (Flat staged
+    // GEMM, IVF-Flat filtered list scan, IVF-PQ threshold pre-pass + filtered scans) are off for the call, restored on any exit
+    struct RouteOverride {
+        rsx_index* h; int ff, iff, pf;
+        explicit RouteOverride(rsx_index* hh) : h(hh), ff(hh->flat_filter), iff(hh->ivf_filter), pf(hh->pq_filter) {
+            if (h->sel) { h->flat_filter = 0; h->ivf_filter = 0; h->pq_filter = 0; }
+        }
+        ~RouteOverride() { h->flat_filter = ff; h->ivf_filter = iff; h->pq_filter = pf; }
+    } route_override(h);
+    if (h->sel) ensure_sel_mask(h);
     // batch size: bounded by the knob and by the score-buffer budget
     int64_t qb = std::max(1, h->query_batch);
     if (h->kind != KIND_FLAT) {
@@ -1159,7 +1219,7 @@ void search_impl(rsx_index* h, int64_t nq, const void* q, int dtype, int k, floa
         const int pad_to = (h->kind == KIND_IVFPQ) ? 64 : 16;
         int64_t tmax = top_probe_sum(h, nprobe, pad_to, pad_to).first;
         tmax = std::max<int64_t>(round_up(tmax, 256), 256);
-        if (pq_search_needs_score_rows(h, nprobe, k)) qb = std::max<int64_t>(1, std::min<int64_t>(qb, h->temp_budget / (tmax * 4)));
+        if (h->sel || pq_search_needs_score_rows(h, nprobe, k)) qb = std::max<int64_t>(1, std::min<int64_t>(qb, h->temp_budget / (tmax * 4)));
         else qb = std::max<int64_t>(1, std::min<int64_t>(qb, h->temp_budget / (pq_cand_cap(k, h->M) * 16)));      // candidate row + tie scratch
     } else if (nq <= 32) {
         qb = 32;
@@ -1183,6 +1243,7 @@ void search_impl(rsx_index* h, int64_t nq, const void* q, int dtype, int k, floa
             h->w_D.ensure((size_t)nb * k * 4); h->w_I.ensure((size_t)nb * k * 8);
             dD = h->w_D.as<float>(); dI = h->w_I.as<int64_t>();
         }
+        if (h->sel) h->timing["filtered_queries"] += (double)nb;
         search_batch(h, nb, dq, dtype, k, dD, dI);
         const size_t dbytes = (size_t)nb * k * 4, ibytes = (size_t)nb * k * 8;
         const bool pin_out = !o_dev && small && h->pin_out.ensure(round_up(dbytes, 16) + ibytes);

@@ -2312,9 +2312,10 @@ void launch_finalize(const FinalizeArgs& a0, hipStream_t st) {
     else if (a.kind != KIND_IVFPQ && a.nq <= 64) waves = std::min(16, std::max(waves, a.KP / 4));   // one wave per candidate re-score
     else if (a.KP >= 1024) waves = 16;     // the reference's n_docs = 1000: 2048 candidates per query to re-score and sort (4 waves: 3.2 ms per 1024 queries)
     a.probe_lds_off = 0;
-    if (a.kind != KIND_FLAT && a.nprobe <= 1024) {      // the probe table behind everything else (20 bytes per probe)
-        a.probe_lds_off = (int)((shm + 15) / 16 * 16);
-        shm = (size_t)a.probe_lds_off + (size_t)(a.nprobe + 1) * 8 + (size_t)a.nprobe * 12 + 16;
+    const size_t probe_end = (shm + 15) / 16 * 16 + (size_t)(a.nprobe + 1) * 8 + (size_t)a.nprobe * 12 + 16;
+    if (a.kind != KIND_FLAT && a.nprobe <= 1024 && probe_end <= 160 * 1024) {      // the probe table behind everything else (20 bytes per probe)
+        a.probe_lds_off = (int)((shm + 15) / 16 * 16);       // (not at K' = 8192, k > 3855 exact: the entries alone fill the 160 KiB)
+        shm = probe_end;
     }
     static DevSize big;
     if (shm > 48 * 1024) big.grow(shm, [&] { hipFuncSetAttribute((const void*)k_finalize, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm); });

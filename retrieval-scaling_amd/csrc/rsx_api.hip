@@ -1,8 +1,58 @@
 // rsx_api.hip — the C ABI of include/rsx.h: argument checks, error codes (rsx_last_error), dispatch to the host functions of
-// api_build.hip / api_search.hip / api_sharded.hip (rsx_host.h).  Every entry point needs a GPU: there is no CPU search path.
+// api_build.hip / api_search.hip / api_sharded.hip (rsx_host.h).  Every entry point but the selector objects' needs a GPU: there is no
+// CPU search path.
+#include <atomic>
 #include "rsx_host.h"
 
 thread_local std::string g_err;
+
+// The selector and the nprobe override of one filtered search (rsx_search_sel / rsx_search_prepass_sel) on the handle and its shards,
+// restored when the call ends, whether it succeeds or throws (FAISS: SearchParametersIVF.nprobe does not change index.nprobe).
+struct SelScope {
+    rsx_index* h; int nprobe0; bool np_set;
+    SelScope(rsx_index* hh, const rsx_selector* sel, int nprobe_override) : h(hh), nprobe0(hh->nprobe), np_set(nprobe_override > 0) {
+        h->sel = sel;
+        for (auto* c : h->shards) c->sel = sel;
+        if (nprobe_override > 0) { h->nprobe = nprobe_override; for (auto* c : h->shards) c->nprobe = nprobe_override; }
+    }
+    ~SelScope() {
+        h->sel = nullptr;
+        for (auto* c : h->shards) c->sel = nullptr;
+        if (np_set) { h->nprobe = nprobe0; for (auto* c : h->shards) c->nprobe = nprobe0; }
+    }
+};
+
+extern "C" {
+static int search_prepass_common(rsx_index_t* h, int64_t nq, const void* q, int dtype, int k, const rsx_selector* sel, int nprobe_override,
+                                 float* D, int64_t* I, uint64_t** tau_dev, int64_t* ntau) {
+    return guarded([&] {
+        if (!h || !tau_dev || !ntau) RSX_THROW(RSX_ERR_INVALID, "null pointer");
+        if (dtype != RSX_F32 && dtype != RSX_F16) RSX_THROW(RSX_ERR_INVALID, "bad dtype %d", dtype);
+        if (nprobe_override < 0) RSX_THROW(RSX_ERR_INVALID, "nprobe override must be positive or 0 (got %d)", nprobe_override);
+        if (is_sharded(h)) RSX_THROW(RSX_ERR_UNSUPPORTED, "search_prepass: not available on a sharded handle (its shards share one process)");
+        if (nq > h->query_batch) RSX_THROW(RSX_ERR_UNSUPPORTED, "search_prepass: nq = %lld exceeds query_batch = %d (one internal batch per two-call search)", (long long)nq, h->query_batch);
+        if (!h->tc) h->tc.reset(new rsx_index::TwoCall());
+        rsx_index::TwoCall& t = *h->tc;
+        if (t.active) RSX_THROW(RSX_ERR_INVALID, "search_prepass: the previous two-call search has not been finished with rsx_search_scan");
+        t.active = true; t.parked = false; t.go = false; t.done = false; t.status = 0; t.err.clear(); t.tau = nullptr; t.ntau = 0;
+        t.th = std::thread([h, nq, q, dtype, k, sel, nprobe_override, D, I] {
+            rsx_index::TwoCall& tt = *h->tc;
+            { std::lock_guard<std::mutex> lk(tt.mu); tt.worker = std::this_thread::get_id(); }
+            int st_ = RSX_OK; std::string msg;
+            try { HIPCHECK(hipSetDevice(h->device)); SelScope sc(h, sel, nprobe_override); search_impl(h, nq, q, dtype, k, D, I); }
+            catch (const RsxError& e) { st_ = e.code; msg = e.what(); }
+            catch (const std::exception& e) { st_ = RSX_ERR_INVALID; msg = e.what(); }
+            std::lock_guard<std::mutex> lk(tt.mu);
+            tt.status = st_; tt.err = msg; tt.done = true;
+            tt.cv.notify_all();
+        });
+        std::unique_lock<std::mutex> lk(t.mu);
+        t.cv.wait(lk, [&] { return t.parked || t.done; });
+        *tau_dev = t.parked ? t.tau : nullptr;       // null: this search has no threshold pre-pass (Flat, exact paths, one probe, ...)
+        *ntau = t.parked ? t.ntau : 0;
+    });
+}
+}
 
 // ---------------------------------------------------------------------------------------
 // C ABI
@@ -10,7 +60,7 @@ thread_local std::string g_err;
 extern "C" {
 
 const char* rsx_last_error(void) { return g_err.c_str(); }
-int rsx_version(void) { return 1000; }
+int rsx_version(void) { return 1001; }     // 1001: filtered search (rsx_selector_*, rsx_search_sel, rsx_search_prepass_sel)
 
 int rsx_device_count(int* n) {
     return guarded([&] {
@@ -257,34 +307,69 @@ int rsx_search(rsx_index_t* h, int64_t nq, const void* q, int dtype, int k, floa
         search_impl(h, nq, q, dtype, k, D, I);
     });
 }
+int rsx_search_sel(rsx_index_t* h, int64_t nq, const void* q, int dtype, int k, const rsx_selector_t* sel, int nprobe_override,
+                   float* D, int64_t* I) {
+    return guarded([&] {
+        if (!h) RSX_THROW(RSX_ERR_INVALID, "null pointer");
+        refuse_while_two_call(h, "search");
+        if (dtype != RSX_F32 && dtype != RSX_F16) RSX_THROW(RSX_ERR_INVALID, "bad dtype %d", dtype);
+        if (nprobe_override < 0) RSX_THROW(RSX_ERR_INVALID, "nprobe override must be positive or 0 (got %d)", nprobe_override);
+        SelScope sc(h, sel, nprobe_override);
+        if (is_sharded(h)) {
+            if (!h->trained) RSX_THROW(RSX_ERR_NOT_TRAINED, "search before train");
+            sharded_search(h, nq, q, dtype, k, D, I);
+            return;
+        }
+        use_device(h);
+        search_impl(h, nq, q, dtype, k, D, I);
+    });
+}
+
+static std::atomic<uint64_t> g_sel_serial{0};
+int rsx_selector_create(int kind, const void* data, int64_t n, int64_t lo, int64_t hi, int invert, rsx_selector_t** out) {
+    return guarded([&] {
+        if (!out) RSX_THROW(RSX_ERR_INVALID, "null out");
+        if (kind != RSX_SEL_RANGE && kind != RSX_SEL_BATCH && kind != RSX_SEL_BITMAP) RSX_THROW(RSX_ERR_INVALID, "unknown selector kind %d", kind);
+        if (n < 0 || (kind != RSX_SEL_RANGE && n > 0 && !data)) RSX_THROW(RSX_ERR_INVALID, "selector: n = %lld with data %p", (long long)n, data);
+        std::unique_ptr<rsx_selector> s(new rsx_selector());
+        s->kind = kind; s->invert = invert != 0;
+        if (kind == RSX_SEL_RANGE) { s->lo = lo; s->hi = hi; }
+        else {
+            const size_t bytes = (size_t)n * (kind == RSX_SEL_BATCH ? 8 : 1);
+            std::vector<uint8_t> raw(bytes);
+            if (bytes) {
+                if (is_device_ptr(data)) HIPCHECK(hipMemcpy(raw.data(), data, bytes, hipMemcpyDeviceToHost));
+                else memcpy(raw.data(), data, bytes);
+            }
+            if (kind == RSX_SEL_BITMAP) s->bitmap.swap(raw);
+            else {
+                s->ids.resize((size_t)n);
+                if (bytes) memcpy(s->ids.data(), raw.data(), bytes);
+                std::sort(s->ids.begin(), s->ids.end());
+                s->ids.erase(std::unique(s->ids.begin(), s->ids.end()), s->ids.end());
+            }
+        }
+        s->serial = ++g_sel_serial;
+        *out = s.release();
+    });
+}
+int rsx_selector_destroy(rsx_selector_t* sel) {
+    return guarded([&] { delete sel; });
+}
+int rsx_selector_is_member(const rsx_selector_t* sel, int64_t n, const int64_t* ids, uint8_t* out) {
+    return guarded([&] {
+        if (!sel || n < 0 || (n > 0 && (!ids || !out))) RSX_THROW(RSX_ERR_INVALID, "selector is_member: bad arguments");
+        for (int64_t i = 0; i < n; i++) out[i] = sel->contains(ids[i]) ? 1 : 0;
+    });
+}
 
 int rsx_search_prepass(rsx_index_t* h, int64_t nq, const void* q, int dtype, int k, float* D, int64_t* I, uint64_t** tau_dev,
                        int64_t* ntau) {
-    return guarded([&] {
-        if (!h || !tau_dev || !ntau) RSX_THROW(RSX_ERR_INVALID, "null pointer");
-        if (dtype != RSX_F32 && dtype != RSX_F16) RSX_THROW(RSX_ERR_INVALID, "bad dtype %d", dtype);
-        if (is_sharded(h)) RSX_THROW(RSX_ERR_UNSUPPORTED, "search_prepass: not available on a sharded handle (its shards share one process)");
-        if (nq > h->query_batch) RSX_THROW(RSX_ERR_UNSUPPORTED, "search_prepass: nq = %lld exceeds query_batch = %d (one internal batch per two-call search)", (long long)nq, h->query_batch);
-        if (!h->tc) h->tc.reset(new rsx_index::TwoCall());
-        rsx_index::TwoCall& t = *h->tc;
-        if (t.active) RSX_THROW(RSX_ERR_INVALID, "search_prepass: the previous two-call search has not been finished with rsx_search_scan");
-        t.active = true; t.parked = false; t.go = false; t.done = false; t.status = 0; t.err.clear(); t.tau = nullptr; t.ntau = 0;
-        t.th = std::thread([h, nq, q, dtype, k, D, I] {
-            rsx_index::TwoCall& tt = *h->tc;
-            { std::lock_guard<std::mutex> lk(tt.mu); tt.worker = std::this_thread::get_id(); }
-            int st_ = RSX_OK; std::string msg;
-            try { HIPCHECK(hipSetDevice(h->device)); search_impl(h, nq, q, dtype, k, D, I); }
-            catch (const RsxError& e) { st_ = e.code; msg = e.what(); }
-            catch (const std::exception& e) { st_ = RSX_ERR_INVALID; msg = e.what(); }
-            std::lock_guard<std::mutex> lk(tt.mu);
-            tt.status = st_; tt.err = msg; tt.done = true;
-            tt.cv.notify_all();
-        });
-        std::unique_lock<std::mutex> lk(t.mu);
-        t.cv.wait(lk, [&] { return t.parked || t.done; });
-        *tau_dev = t.parked ? t.tau : nullptr;       // null: this search has no threshold pre-pass (Flat, exact paths, one probe, ...)
-        *ntau = t.parked ? t.ntau : 0;
-    });
+    return search_prepass_common(h, nq, q, dtype, k, nullptr, 0, D, I, tau_dev, ntau);
+}
+int rsx_search_prepass_sel(rsx_index_t* h, int64_t nq, const void* q, int dtype, int k, const rsx_selector_t* sel, int nprobe_override,
+                           float* D, int64_t* I, uint64_t** tau_dev, int64_t* ntau) {
+    return search_prepass_common(h, nq, q, dtype, k, sel, nprobe_override, D, I, tau_dev, ntau);
 }
 int rsx_search_scan(rsx_index_t* h) {
     return guarded([&] {

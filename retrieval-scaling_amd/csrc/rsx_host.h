@@ -23,6 +23,7 @@
 
 #include "../../include/rsx.h"
 #include "rsx_internal.h"
+#include "rsx_sel.h"
 
 using namespace rsx;
 
@@ -151,6 +152,23 @@ static inline void rand_perm(int64_t n, uint64_t seed, std::vector<int64_t>& per
 // ---------------------------------------------------------------------------------------
 // the index object
 // ---------------------------------------------------------------------------------------
+// faiss.IDSelector* behind rsx_selector_t (include/rsx.h): immutable after rsx_selector_create.  serial identifies it in the slot-mask
+// cache of a handle (rsx_index::sel_*): a new selector never reuses a live one's serial.
+struct rsx_selector {
+    int kind = 0, invert = 0;
+    int64_t lo = 0, hi = 0;                 // RSX_SEL_RANGE
+    std::vector<uint8_t> bitmap;            // RSX_SEL_BITMAP
+    std::vector<int64_t> ids;               // RSX_SEL_BATCH: sorted, unique
+    uint64_t serial = 0;
+    bool contains(int64_t id) const {
+        bool m;
+        if (kind == RSX_SEL_RANGE) m = id >= lo && id < hi;
+        else if (kind == RSX_SEL_BITMAP) m = id >= 0 && (id >> 3) < (int64_t)bitmap.size() && ((bitmap[(size_t)(id >> 3)] >> (id & 7)) & 1);
+        else m = std::binary_search(ids.begin(), ids.end(), id);
+        return m != (invert != 0);
+    }
+};
+
 struct rsx_index {
     int kind = 0, d = 0, metric = 0, device = 0;
     int nlist = 1, M = 0, nbits = 8, Mpad = 0, CB = 16, dsub = 0;   // CB: code layout (rsx_internal.h), 0 = rotated
@@ -242,6 +260,13 @@ struct rsx_index {
     DevBuf w_q32, w_q16, w_coarse, w_keys1, w_probekeys, w_probelist, w_dis0, w_segstart, w_temp, w_lut, w_lutws, w_pgflags, w_state,
         w_D, w_I, w_qin, w_pairs, w_flag, w_x, w_partial, w_assign, w_dest, w_idsin, w_misc, w_lut8, w_qparam, w_uncertain, w_fbq, w_fbD, w_fbI, w_cand, w_candcnt, w_itemdesc, w_tau, w_excl, w_state2, w_addcnt, w_addstart, w_qitems, w_tiews;
     std::map<std::string, double> timing;
+
+    // filtered search (rsx_search_sel): the selector of the call in flight (null = unfiltered) and its slot mask — bit s of
+    // sel_mask = the vector in storage slot s is selected — cached per (selector, directory generation, storage)
+    const rsx_selector* sel = nullptr;
+    DevBuf sel_mask, sel_dev;               // sel_dev: the selector's bitmap / sorted ids while the mask is built
+    uint64_t sel_mask_serial = 0, sel_mask_gen = 0;
+    const void* sel_mask_of = nullptr;
 
     // Flat / IVF-Flat: largest |x|^2 ever added (certificate of the MFMA scan); device copy is the running atomic max
     float max_norm2 = 0.0f;

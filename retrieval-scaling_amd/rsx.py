@@ -42,6 +42,7 @@ ABI_SYMBOLS = [
     "rsx_get_list", "rsx_get_list_sizes", "rsx_set_nprobe", "rsx_search", "rsx_search_prepass", "rsx_search_scan", "rsx_merge_topk", "rsx_pack_topk", "rsx_merge_packed", "rsx_get",
     "rsx_set_param",
     "rsx_get_timing", "rsx_save", "rsx_load", "rsx_synth_vectors", "rsx_synth_queries",
+    "rsx_selector_create", "rsx_selector_destroy", "rsx_selector_is_member", "rsx_search_sel", "rsx_search_prepass_sel",
 ]
 
 
@@ -181,6 +182,190 @@ def _sync_producer(keep, on_dev):
         torch.cuda.current_stream(keep.device).synchronize()
 
 
+# ------------------------------------------------------------------------------------------
+# filtered search: faiss.IDSelector* and faiss.SearchParameters* (FAISS 1.8.0 names)
+# ------------------------------------------------------------------------------------------
+_SEL_RANGE, _SEL_BATCH, _SEL_BITMAP = 0, 1, 2
+
+
+class IDSelector:
+    """Base of the id selectors.  A selector is immutable; its native object (rsx_selector_create, host memory only) is built
+    on first use and cached, so a selector reused across searches keeps the slot mask an index caches for it."""
+
+    _native_h = None
+
+    def _spec(self):
+        """-> (kind, data array or None, lo, hi, invert)"""
+        raise NotImplementedError
+
+    def _native(self):
+        if self._native_h is None:
+            kind, data, lo, hi, inv = self._spec()
+            h = ctypes.c_void_p()
+            ptr = data.ctypes.data_as(ctypes.c_void_p) if data is not None and data.size else None
+            n = 0 if data is None else data.size
+            _check(lib().rsx_selector_create(kind, ptr, ctypes.c_int64(n), ctypes.c_int64(lo), ctypes.c_int64(hi), int(inv), ctypes.byref(h)))
+            self._native_h = h
+        return self._native_h
+
+    def __del__(self):
+        h = self._native_h
+        if h is not None and _lib is not None:
+            try:
+                _lib.rsx_selector_destroy(h)
+            except Exception:
+                pass
+            self._native_h = None
+
+    def is_member(self, ids):
+        """bool array: which of the int64 `ids` the selector selects (host code, no GPU)."""
+        ids = np.ascontiguousarray(np.atleast_1d(ids), dtype=np.int64)
+        out = np.zeros(ids.shape, dtype=np.uint8)
+        _check(lib().rsx_selector_is_member(self._native(), ctypes.c_int64(ids.size), ids.ctypes.data_as(ctypes.c_void_p),
+                                            out.ctypes.data_as(ctypes.c_void_p)))
+        return out.astype(bool)
+
+    def shifted(self, offset, n_local=None):
+        """The selector over LOCAL ids i of a shard whose ids are the global ids i + offset (n_local: the shard's id count, lets a
+        bitmap or batch keep only the shard's part).  Used by sharded.ShardedSearcher for id-range shards."""
+        raise NotImplementedError
+
+
+class IDSelectorRange(IDSelector):
+    """faiss.IDSelectorRange(imin, imax): ids in [imin, imax)."""
+
+    def __init__(self, imin, imax):
+        self.imin, self.imax = int(imin), int(imax)
+
+    def _spec(self):
+        return _SEL_RANGE, None, self.imin, self.imax, False
+
+    def shifted(self, offset, n_local=None):
+        return IDSelectorRange(self.imin - offset, self.imax - offset) if offset else self
+
+
+class IDSelectorBatch(IDSelector):
+    """faiss.IDSelectorBatch(ids) or (n, ids): any int64 ids; duplicates allowed, ids absent from the index ignored."""
+
+    def __init__(self, *args):
+        ids = args[-1]
+        if _is_torch(ids):
+            ids = ids.detach().cpu().numpy()
+        ids = np.ascontiguousarray(ids, dtype=np.int64).reshape(-1)
+        if len(args) == 2:
+            ids = ids[: int(args[0])]
+        elif len(args) != 1:
+            raise TypeError("IDSelectorBatch(ids) or IDSelectorBatch(n, ids)")
+        self.ids = ids
+
+    def _spec(self):
+        return _SEL_BATCH, self.ids, 0, 0, False
+
+    def shifted(self, offset, n_local=None):
+        if not offset and n_local is None:
+            return self
+        loc = self.ids - offset
+        if n_local is not None:
+            loc = loc[(loc >= 0) & (loc < n_local)]
+        return IDSelectorBatch(loc)
+
+
+class IDSelectorBitmap(IDSelector):
+    """faiss.IDSelectorBitmap(bitmap) or (n, bitmap): uint8 [n]; id i is selected when i < 8 n and bit i & 7 (least significant
+    first) of byte i >> 3 is set."""
+
+    def __init__(self, *args):
+        bm = args[-1]
+        if _is_torch(bm):
+            bm = bm.detach().cpu().numpy()
+        bm = np.ascontiguousarray(bm).reshape(-1)
+        if bm.dtype != np.uint8:
+            raise TypeError(f"IDSelectorBitmap: bitmap must be uint8, got {bm.dtype}")
+        if len(args) == 2:
+            bm = bm[: int(args[0])]
+        elif len(args) != 1:
+            raise TypeError("IDSelectorBitmap(bitmap) or IDSelectorBitmap(n, bitmap)")
+        self.bitmap = bm
+
+    def _spec(self):
+        return _SEL_BITMAP, self.bitmap, 0, 0, False
+
+    def shifted(self, offset, n_local=None):
+        if not offset and n_local is None:
+            return self
+        nbits = 8 * self.bitmap.size
+        end = nbits if n_local is None else min(nbits, offset + int(n_local))
+        if offset % 8 == 0:
+            return IDSelectorBitmap(self.bitmap[offset // 8:(end + 7) // 8] if end > offset else np.zeros(0, np.uint8))
+        if end <= max(offset, 0):
+            return IDSelectorBitmap(np.zeros(0, np.uint8))
+        lo = max(offset, 0)       # only the shard's own bits are unpacked (local ids below -offset cannot exist)
+        bits = np.unpackbits(self.bitmap[lo // 8:(end + 7) // 8], bitorder="little")[lo % 8:lo % 8 + (end - lo)]
+        if lo > offset:
+            bits = np.concatenate([np.zeros(lo - offset, np.uint8), bits])
+        return IDSelectorBitmap(np.packbits(bits, bitorder="little"))
+
+
+class IDSelectorNot(IDSelector):
+    """faiss.IDSelectorNot(sel): the complement of another selector."""
+
+    def __init__(self, sel):
+        if not isinstance(sel, IDSelector):
+            raise TypeError(f"IDSelectorNot takes an IDSelector, got {type(sel).__name__}")
+        self.sel = sel
+
+    def _spec(self):
+        kind, data, lo, hi, inv = self.sel._spec()
+        return kind, data, lo, hi, not inv
+
+    def shifted(self, offset, n_local=None):
+        # the complement must stay a complement over ALL local ids: no truncation to the shard's part
+        return IDSelectorNot(self.sel.shifted(offset, None)) if offset else self
+
+
+class SearchParameters:
+    """faiss.SearchParameters(sel=None): per-call parameters of Index.search (Flat)."""
+
+    def __init__(self, sel=None):
+        self.sel = sel
+
+
+class SearchParametersIVF(SearchParameters):
+    """faiss.SearchParametersIVF(sel=None, nprobe=1, max_codes=0): IVF-Flat / IVF-PQ.  As in FAISS 1.8.0 nprobe defaults to 1 and
+    replaces index.nprobe for the call only.  max_codes and quantizer_params are not implemented: a non-default value is refused."""
+
+    def __init__(self, sel=None, nprobe=1, max_codes=0, quantizer_params=None):
+        super().__init__(sel)
+        self.nprobe = nprobe
+        self.max_codes = max_codes
+        self.quantizer_params = quantizer_params
+
+
+def _resolve_params(params, is_ivf):
+    """-> (native selector or None, nprobe override (0 = none), keepalive).  FAISS 1.8.0's type rules: IndexIVF::search
+    refuses a params object that is not SearchParametersIVF ("IndexIVF params have incorrect type")."""
+    if not isinstance(params, SearchParameters):
+        raise TypeError(f"params must be a SearchParameters object, got {type(params).__name__}")
+    if is_ivf and not isinstance(params, SearchParametersIVF):
+        raise RuntimeError("IndexIVF params have incorrect type")
+    nprobe = 0
+    if isinstance(params, SearchParametersIVF):
+        if params.max_codes:
+            raise NotImplementedError(f"SearchParametersIVF.max_codes = {params.max_codes}: not implemented (only the default 0)")
+        if params.quantizer_params is not None:
+            raise NotImplementedError("SearchParametersIVF.quantizer_params: not implemented")
+        if is_ivf:
+            nprobe = int(params.nprobe)
+            if nprobe <= 0:
+                raise ValueError(f"SearchParametersIVF.nprobe must be positive, got {params.nprobe}")
+    sel = params.sel
+    if sel is None:
+        return None, nprobe, None
+    if not isinstance(sel, IDSelector):
+        raise TypeError(f"params.sel must be an IDSelector, got {type(sel).__name__}")
+    return sel._native(), nprobe, sel
+
+
 class Index:
     """Base handle.  Attributes follow faiss.Index: d, ntotal, is_trained, metric_type."""
 
@@ -251,26 +436,34 @@ class Index:
         assert ids.shape == (n,), "ids must have one entry per vector"
         _check(lib().rsx_add(self._h, ctypes.c_int64(n), p, dt, ids.ctypes.data_as(ctypes.c_void_p)))
 
-    def search(self, x, k):
-        """-> (D float32 [n,k], I int64 [n,k]); numpy in -> numpy out, CUDA tensor in -> CUDA tensors out."""
+    def search(self, x, k, *, params=None):
+        """-> (D float32 [n,k], I int64 [n,k]); numpy in -> numpy out, CUDA tensor in -> CUDA tensors out.
+        params: SearchParameters (Flat) / SearchParametersIVF (IVF) — a filtered search returns what the unfiltered search of an
+        index holding only the selected vectors returns (rsx_search_sel)."""
         keep, p, n, dt, on_dev = _as_matrix(x, self.d, "search")
         k = int(k)
         assert k > 0, "k must be positive"
+        if params is not None:
+            sel, nprobe, sel_keep = _resolve_params(params, isinstance(self, _IndexIVF))
+
+            def call(Dp, Ip):
+                _check(lib().rsx_search_sel(self._h, ctypes.c_int64(n), p, dt, k, sel, int(nprobe), Dp, Ip))
+        else:
+            def call(Dp, Ip):
+                _check(lib().rsx_search(self._h, ctypes.c_int64(n), p, dt, k, Dp, Ip))
         if on_dev:
             import torch
             D = torch.empty((n, k), dtype=torch.float32, device=keep.device)
             I = torch.empty((n, k), dtype=torch.int64, device=keep.device)
             _sync_producer(keep, on_dev)
-            _check(lib().rsx_search(self._h, ctypes.c_int64(n), p, dt, k, ctypes.c_void_p(D.data_ptr()),
-                                    ctypes.c_void_p(I.data_ptr())))
+            call(ctypes.c_void_p(D.data_ptr()), ctypes.c_void_p(I.data_ptr()))
             return D, I
         D = np.empty((n, k), dtype=np.float32)
         I = np.empty((n, k), dtype=np.int64)
-        _check(lib().rsx_search(self._h, ctypes.c_int64(n), p, dt, k, D.ctypes.data_as(ctypes.c_void_p),
-                                I.ctypes.data_as(ctypes.c_void_p)))
+        call(D.ctypes.data_as(ctypes.c_void_p), I.ctypes.data_as(ctypes.c_void_p))
         return D, I
 
-    def search_prepass(self, x, k):
+    def search_prepass(self, x, k, params=None):
         """First half of a two-call search (rsx_search_prepass): CUDA-tensor queries in -> a CUDA int64 tensor VIEW of the nq
         threshold keys (or None when this search has none).  The keys are unsigned 64-bit integers: flip the sign bit
         (`t ^= -2**63`) before comparing / reducing them as int64 and flip it back afterwards.  Finish with search_scan()."""
@@ -282,8 +475,14 @@ class Index:
         I = torch.empty((n, k), dtype=torch.int64, device=keep.device)
         _sync_producer(keep, on_dev)
         tau, ntau = ctypes.c_void_p(), ctypes.c_int64(0)
-        _check(lib().rsx_search_prepass(self._h, ctypes.c_int64(n), p, dt, k, ctypes.c_void_p(D.data_ptr()), ctypes.c_void_p(I.data_ptr()),
-                                        ctypes.byref(tau), ctypes.byref(ntau)))
+        if params is not None:      # (a filtered search has no threshold pre-pass: None comes back)
+            sel, nprobe, sel_keep = _resolve_params(params, isinstance(self, _IndexIVF))
+            _check(lib().rsx_search_prepass_sel(self._h, ctypes.c_int64(n), p, dt, k, sel, int(nprobe), ctypes.c_void_p(D.data_ptr()),
+                                                ctypes.c_void_p(I.data_ptr()), ctypes.byref(tau), ctypes.byref(ntau)))
+            self._two_call_sel = sel_keep      # the selector outlives the worker that reads it
+        else:
+            _check(lib().rsx_search_prepass(self._h, ctypes.c_int64(n), p, dt, k, ctypes.c_void_p(D.data_ptr()), ctypes.c_void_p(I.data_ptr()),
+                                            ctypes.byref(tau), ctypes.byref(ntau)))
         self._two_call = (keep, D, I)
         if not tau.value or ntau.value == 0:
             return None
@@ -296,7 +495,10 @@ class Index:
         """Second half: runs the scan with the (possibly raised) thresholds -> (D, I) CUDA tensors."""
         keep, D, I = self._two_call
         self._two_call = None
-        _check(lib().rsx_search_scan(self._h))
+        try:
+            _check(lib().rsx_search_scan(self._h))
+        finally:
+            self._two_call_sel = None
         return D, I
 
     # -- inspection (parity tests, writer)

@@ -101,7 +101,18 @@ class ShardedSearcher:
             self._events = []
         return out
 
-    def _search_two_call(self, q, k):
+    def local_params(self, params):
+        """params over GLOBAL ids -> the same parameters over this rank's local ids: an id-range shard stores local ids
+        [0, ntotal) for the global ids [id_offset, id_offset + ntotal), so its selector is the global one shifted by id_offset
+        (a selector object of its own: no id space is materialised).  A list shard (id_offset 0) stores global ids already."""
+        if params is None or getattr(params, "sel", None) is None or not self.id_offset:
+            return params
+        import copy
+        out = copy.copy(params)
+        out.sel = params.sel.shifted(self.id_offset, int(self.index.ntotal))
+        return out
+
+    def _search_two_call(self, q, k, params=None):
         """One all-reduce(MAX) of the per-query threshold keys between rsx_search_prepass and rsx_search_scan.  The library runs
         ONE internal batch per two-call search, so a larger batch is cut into query_batch-sized pieces (every rank holds the
         same batch and the same knob, hence issues the same sequence of collectives).  Whatever happens between the two calls
@@ -111,9 +122,10 @@ class ShardedSearcher:
         import torch.distributed as dist
         qb = int(self.index._get("query_batch"))
         if q.shape[0] > qb:
-            parts = [self._search_two_call(q[i:i + qb], k) for i in range(0, q.shape[0], qb)]
+            parts = [self._search_two_call(q[i:i + qb], k, params) for i in range(0, q.shape[0], qb)]
             return torch.cat([p[0] for p in parts], 0), torch.cat([p[1] for p in parts], 0)
-        tau = self.index.search_prepass(q, k)
+        # (a filtered search — params with a selector — has no threshold pre-pass: None, and this rank contributes "no threshold")
+        tau = self.index.search_prepass(q, k) if params is None else self.index.search_prepass(q, k, params)
         try:
             # every rank takes part in the collective, also one whose search has no pre-pass (it contributes "no threshold")
             t = (tau ^ _SIGN) if tau is not None else torch.full((q.shape[0],), _SIGN, dtype=torch.int64, device=q.device)
@@ -134,15 +146,19 @@ class ShardedSearcher:
             raise
         return self.index.search_scan()
 
-    def search(self, q, k):
+    def search(self, q, k, params=None):
         """q: [nq, d] — the SAME batch on every rank (numpy / CPU tensor / CUDA tensor).
+        params: SearchParameters(IVF) whose selector is over GLOBAL ids (local_params translates it per rank).
         Returns merged (D, I) [nq, k] on every rank, in the container type of the local result."""
         import torch
         import torch.distributed as dist
+        lp = self.local_params(params)
         if self.exchange_thresholds and torch.is_tensor(q) and q.is_cuda and self.world_size > 1:
-            D, I = self._search_two_call(q, k)
-        else:
+            D, I = self._search_two_call(q, k, lp)
+        elif lp is None:
             D, I = self.index.search(q, k)
+        else:
+            D, I = self.index.search(q, k, params=lp)
         as_numpy = not torch.is_tensor(D)
         if as_numpy:
             D, I = torch.from_numpy(np.ascontiguousarray(D)), torch.from_numpy(np.ascontiguousarray(I))

@@ -84,6 +84,9 @@ class Indexer(object):
             v = default
         return default if v is None else v
 
-    def search(self, query_embs, k=5):
-        all_scores, all_passages, db_ids = self.datastore.search(query_embs, k)
+    def search(self, query_embs, k=5, params=None):
+        if params is None:
+            all_scores, all_passages, db_ids = self.datastore.search(query_embs, k)
+        else:
+            all_scores, all_passages, db_ids = self.datastore.search(query_embs, k, params=params)
         return all_scores, all_passages, db_ids

@@ -315,10 +315,14 @@ class BackendBase:
 
     # ---- search (reference flat.py:138-141; the reference's astype(np.float32) is dropped: the
     # engine takes fp16 queries as they come out of the encoder)
-    def search(self, query_embs, k=4096):
+    def search(self, query_embs, k=4096, params=None):
         """query_embs: numpy array (the reference) or a CUDA tensor straight from the encoder (no host round trip of the
-        queries; D / I come back as tensors and only they cross PCIe)."""
-        all_scores, all_indices = self.index.search(query_embs, k)
+        queries; D / I come back as tensors and only they cross PCIe).  params: faiss.SearchParameters(IVF) with an id
+        selector (filtered search); None keeps the reference's call."""
+        if params is None:
+            all_scores, all_indices = self.index.search(query_embs, k)
+        else:
+            all_scores, all_indices = self.index.search(query_embs, k, params=params)
         if hasattr(all_indices, "is_cuda"):
             all_scores, all_indices = all_scores.cpu().numpy(), all_indices.cpu().numpy()
         all_passages, db_ids = self.get_retrieved_passages(all_indices)

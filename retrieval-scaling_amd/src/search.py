@@ -215,6 +215,26 @@ def embed_queries(args, queries, model, tokenizer, model_name_or_path):
     return embeddings
 
 
+def datastore_subsample_params(search_args, engine_index):
+    """Opt-in key evaluation.search.datastore_subsample_p (with subsample_seed, default 1000): p < 1 searches a seeded
+    Bernoulli(p) selection of the index's ids [0, ntotal) — a smaller datastore simulated INSIDE the search, which returns a
+    full n_docs from it (the reference's topk_subsample_p coin-flips the retrieved documents afterwards, :493-500, and keeps
+    fewer).  -> SearchParameters(IVF) with an IDSelectorBitmap, or None (key absent or p >= 1: the reference's call)."""
+    p = cfg_get(search_args, "datastore_subsample_p", None)
+    if p is None or float(p) >= 1.0:
+        return None
+    p = float(p)
+    if p < 0.0:
+        raise ValueError(f"evaluation.search.datastore_subsample_p = {p}: expected a probability in [0, 1]")
+    import rsx
+    seed = int(cfg_get(search_args, "subsample_seed", 1000))
+    keep = np.random.default_rng(seed).random(int(engine_index.ntotal)) < p
+    sel = rsx.IDSelectorBitmap(np.packbits(keep, bitorder="little"))
+    if hasattr(engine_index, "nprobe"):       # IVF: the index's own nprobe (SearchParametersIVF would default to 1)
+        return rsx.SearchParametersIVF(sel=sel, nprobe=int(engine_index.nprobe))
+    return rsx.SearchParameters(sel=sel)
+
+
 def search_dense_topk(cfg, data=None, questions_embedding=None, query_encoder_fn=None):
     """reference src/search.py:213-309, callable with `cfg` alone (ric/main_ric.py:27-29).
 
@@ -258,7 +278,11 @@ def search_dense_topk(cfg, data=None, questions_embedding=None, query_encoder_fn
             copied = copy.deepcopy(data)
             index = Indexer(cfg)
             # ONE call with every query, exactly like the reference (:296)
-            all_scores, all_passages, db_ids = index.search(questions_embedding, eval_args.search.n_docs)
+            params = datastore_subsample_params(eval_args.search, index.datastore.index)
+            if params is None:
+                all_scores, all_passages, db_ids = index.search(questions_embedding, eval_args.search.n_docs)
+            else:
+                all_scores, all_passages, db_ids = index.search(questions_embedding, eval_args.search.n_docs, params=params)
             add_passages_to_eval_data(copied, all_passages, all_scores, db_ids, valid_query_idx,
                                       domain=cfg_get(cfg.datastore, "domain", None))
             os.makedirs(os.path.dirname(output_path), exist_ok=True)
