@@ -137,41 +137,134 @@ static int64_t max_scan_items(rsx_index* h, int64_t nq, int nprobe, int G, int t
     return (nq * tq + G - 1) / G + all + 8;
 }
 
-
-// The IVF-PQ fast scan with in-kernel filtering and the one-launch threshold pre-pass never writes a score row (search_batch):
-// such a search needs no [nq, sum of the nprobe longest lists] score buffer, and its internal batch is not bounded by one.
-static void search_batch(rsx_index* h, int64_t nq, const void* dq, int dtype, int k, float* dD, int64_t* dI, bool allow_fast = true);
-
-static bool pq_fast_applies(const rsx_index* h, int k, bool allow_fast) {      // the ONE definition of "this search takes the 8-bit fast scan"
-    bool fast = allow_fast && h->kind == KIND_IVFPQ && h->metric == RSX_METRIC_INNER_PRODUCT && h->pq_fast != 0 && h->scan_kernel == 0 && (h->CB == 16 || pq_rot_family(h->CB)) && h->M * 255 < 65536;
-    if (fast) { int KP, BUF; kp_for(h, k, true, KP, BUF); if (KP > 4096) fast = false; }
-    // the sliced layout has ONE fast kernel: the filtered scan behind the one-launch pre-pass (every other setting takes the exact scan)
-    if (fast && h->CB == PQ_SLICED && !(std::min(h->nprobe, h->nlist) > 1 && h->pq_filter != 0 && h->pq_prepass_fused != 0)) fast = false;
-    return fast;
+// ---------------------------------------------------------------------------------------
+// the batch plan: every route decision of one internal batch, made once (plan_batch)
+// ---------------------------------------------------------------------------------------
+struct BatchPlan {
+    int64_t nq, nq_pad; int k; bool allow_fast;     // nq_pad: query tiles of 128 (k_flat_gemm) or 256 (k_flat_gemm2)
+    bool rot, sliced;          // IVF-PQ block layouts (rotated, sliced): transposed tables, work-item scans
+    bool fast;                 // the IVF-PQ 8-bit fast scan: approximate scores, certified in k_finalize
+    int KP, BUF;               // selection state: K' keys per query, the selection's buffer
+    bool certify;              // Flat / IVF-Flat: the fp16 scans are certified and the uncertain queries re-run exactly
+    bool coarse_fast, q16_direct;
+    bool pq_fused_lut, side_lut, tab_expected, lut_pass0_early;
+    bool sl_eight; int ngq;    // sliced layout: eight queries per gather; 4-query records per work item of the filtered scan
+    // the in-scan candidate filters in effect: the knobs, all off for a filtered search (h->sel), which takes the routes whose scans write
+    // complete score rows
+    int flat_filter, ivf_filter, pq_filter;
+    int nprobe, pad_to;        // IVF: probed lists per query; list padding of the score rows
+    int64_t tmax, maxlen;      // IVF: a query's score row (the nprobe longest padded lists, at least 256) and the longest of those lists
+    bool needs_score_rows;     // the IVF-PQ fast scan with in-kernel filtering and the one-launch threshold pre-pass never writes a score row
+};
+static BatchPlan plan_batch(rsx_index* h, int64_t nq, const void* dq, int dtype, int k, bool allow_fast) {
+    BatchPlan P{};
+    const bool pq = h->kind == KIND_IVFPQ;
+    P.nq = nq; P.nq_pad = nq > 128 ? round_up(nq, 256) : 128; P.k = k; P.allow_fast = allow_fast;
+    P.flat_filter = h->sel ? 0 : h->flat_filter; P.ivf_filter = h->sel ? 0 : h->ivf_filter; P.pq_filter = h->sel ? 0 : h->pq_filter;
+    P.rot = pq && pq_rot_family(h->CB); P.sliced = pq && h->CB == PQ_SLICED;
+    P.nprobe = std::min(h->nprobe, h->nlist);
+    // IVFPQ fast path: needs the 16-byte-granule layout, 16-bit integer sums, and K' <= 4096.  The sliced layout has ONE fast kernel: the
+    // filtered scan behind the one-launch pre-pass (every other setting takes the exact scan)
+    P.fast = allow_fast && pq && h->metric == RSX_METRIC_INNER_PRODUCT && h->pq_fast != 0 && h->scan_kernel == 0 && (h->CB == 16 || pq_rot_family(h->CB)) && h->M * 255 < 65536;
+    if (P.fast) { kp_for(h, k, true, P.KP, P.BUF); if (P.KP > 4096) P.fast = false; }
+    if (P.fast && P.sliced && !(P.nprobe > 1 && P.pq_filter != 0 && h->pq_prepass_fused != 0)) P.fast = false;
+    kp_for(h, k, P.fast, P.KP, P.BUF);
+    P.certify = h->kind != KIND_IVFPQ && allow_fast && h->flat_cert != 0;
+    // fast coarse quantiser (round 6): fp16 MFMA scores of all lists + exact chains of the candidates; needs the re-run machinery behind it
+    P.coarse_fast = h->kind != KIND_FLAT && allow_fast && h->coarse_fast != 0 && (pq ? P.fast : P.certify) && nq >= 32 &&
+                    P.nprobe <= CP_MAXPROBE && h->nlist <= CP_MAXLIST && h->nlist > P.nprobe && !h->h_centroids.empty() &&
+                    coarse_pick_lds(h->nlist, h->d, P.nprobe) <= 150 * 1024;
+    // ... whose fp16 operand is the caller's own batch when that is fp16, unpadded (d = ld) and whole tiles: the fp32 copy then rides in the
+    // GEMM's launch (extra grid rows) instead of a conversion launch of its own
+    // (not with the side-stream table build: it reads the fp32 copy before the GEMM has run)
+    P.q16_direct = pq && P.coarse_fast && h->overlap == 0 && dtype == RSX_F16 && h->d == h->ld && nq % 128 == 0 && ((uintptr_t)dq & 15) == 0;
+    P.pq_fused_lut = pq && P.fast && pq_lut8_fused_lds(h->M, h->Mpad, h->dsub) <= 160 * 1024 - 64;
+    P.side_lut = P.pq_fused_lut && h->overlap != 0 && h->dsub == 8 && h->lut_tiled != 0 && nq >= 64;
+    // the finalize-from-the-row kernel (k_pq_final_tab) will serve this batch: let the table builder store the fp32 tables for it
+    // (M KiB per query, 100 MB at M = 96 / batch 1024) instead of every query's workgroup re-deriving its table from the 786 KB codebook
+    P.tab_expected = P.pq_fused_lut && P.rot && h->pq_final_tab != 0 && (h->pq_final_tab == 2 || P.KP >= 512 || h->dsub > 8) &&
+                     P.nprobe > 1 && P.pq_filter != 0 && h->pq_prepass_fused != 0 && pq_final_tab_capacity(h->M, h->CB, k) > 0;
+    // the matrix-core table build will serve this batch and the fast coarse quantiser runs: its first pass rides in the probe-pick launch
+    P.lut_pass0_early = P.coarse_fast && P.pq_fused_lut && !P.side_lut && h->dsub == 8 && h->lut_tiled >= 2 && h->metric == RSX_METRIC_INNER_PRODUCT &&
+                        h->pq_lut_early != 0;
+    // sliced layout: eight queries per gather (two records per item) where lists are long and shared by several queries; a handful of
+    // queries (about one per probed list) or short lists take the four-query single-pass scan (k_pq_scan_sl4).  pq_q8: 1 = choose,
+    // 2 = always eight, 0 = always four
+    P.sl_eight = P.sliced && (h->pq_q8 == 2 || (h->pq_q8 != 0 && nq * (int64_t)P.nprobe >= (int64_t)3 * h->nlist && h->ntotal >= (int64_t)4096 * h->nlist));
+    P.ngq = P.sliced ? (P.sl_eight ? 2 : 1) : P.rot ? pq_scan_rot_ngq(h->M, true, h->pq_q8) : 1;     // (M = 16: 4)
+    if (h->kind != KIND_FLAT) {
+        P.pad_to = pq ? 64 : 16;
+        const auto padded = top_probe_sum(h, P.nprobe, P.pad_to, P.pad_to);    // the nprobe longest lists, padded: sum and maximum
+        P.tmax = std::max<int64_t>(round_up(padded.first, 256), 256); P.maxlen = padded.second;
+    }
+    // score rows [nq, tmax]: every path but the filtered IVF-PQ fast scan with the one-launch pre-pass fills (part of) them.  At the
+    // reference's nprobe 512 a row is 35 MB: allocating it unconditionally used to cut a 1024-query batch into four internal
+    // batches (round 4: 4x the fixed stages, a quarter of the queries per list group)
+    P.needs_score_rows = !(P.fast && P.nprobe > 1 && P.pq_filter != 0 && h->pq_prepass_fused != 0);
+    return P;
 }
-static bool pq_search_needs_score_rows(const rsx_index* h, int nprobe, int k) {
-    return !(pq_fast_applies(h, k, true) && nprobe > 1 && h->pq_filter != 0 && h->pq_prepass_fused != 0);
-}
-
-// Keys a query's candidate row can hold (filtered IVF-PQ fast scan).  The threshold is valid by construction, so the
-// row must hold every vector within 2 eps of the query's k-th best: ~700 keys at M = 96 / k = 10, but eps grows as the tables get
-// coarser — at M = 16 (48 dimensions per 8-bit table entry) the measured mean is 1800 and the maximum 23 000 at k = 10.  An
-// overflowing row sends its query to the exact re-run, so small M gets four times the room (8 B x nq x cap of HBM).
-static int64_t pq_cand_cap(int k, int M) {
+// Keys a query's candidate row can hold (filtered IVF-PQ fast scan, filtered IVF-Flat list scan).  The IVF-PQ threshold is valid by
+// construction, so the row must hold every vector within 2 eps of the query's k-th best: ~700 keys at M = 96 / k = 10, but
+// eps grows as the tables get coarser — at M = 16 (48 dimensions per 8-bit table entry) the measured mean is 1800 and the maximum 23 000
+// at k = 10.  An overflowing row sends its query to the exact re-run, so small M gets four times the room (8 B x nq x cap of HBM).
+// M = 0: rows of full vectors (IVF-Flat).
+static int64_t cand_row_cap(int k, int M) {
     int64_t cap = k > 512 ? 131072 : (k > 64 ? 65536 : 16384);
-    if (M <= 32) cap = std::min<int64_t>(cap * 4, 262144);
+    if (M > 0 && M <= 32) cap = std::min<int64_t>(cap * 4, 262144);
     return cap;
 }
-
+// the candidate rows [nq, cap] and their counters; returns cap (never more than a score row)
+static int alloc_cand_rows(rsx_index* h, const BatchPlan& P, int M) {
+    const int cap = (int)std::min<int64_t>(std::max<int64_t>(P.tmax, 1024), cand_row_cap(P.k, M));
+    h->w_cand.ensure((size_t)P.nq * cap * 8);
+    h->w_candcnt.ensure((size_t)P.nq * 8 * CCS);
+    return cap;
+}
+// merge key rows [nrows, cap] (row r holds cnt[r * CCS] keys) into state rows [nrows, KP]: one wave per row, the whole row one segment
+static void merge_key_rows(rsx_index* h, const void* keys, const unsigned long long* cnt, int cap, int64_t nrows, const uint64_t* init,
+                           uint64_t* out, int KP, int BUF, const int32_t* row_filter = nullptr) {
+    SelectArgs b{};
+    b.in = keys; b.in_is_keys = 1; b.row_stride = cap;
+    b.row_n = reinterpret_cast<const int64_t*>(cnt); b.row_n_stride = CCS; b.n_uniform = cap;
+    b.seg_len = round_up(cap, 256); b.nseg = 1; b.idx_base = 0;
+    b.init = init; b.out = out; b.out_row_stride = KP;
+    b.nrows = nrows; b.KP = KP; b.BUF = BUF; b.k = KP; b.row_filter = row_filter;
+    launch_select(b, h->st);
+}
+// the (query, probe) pairs of a batch grouped by list (launch_group_pairs), carved out of h->w_pairs
+struct PairArea {
+    int64_t npairs; int nlist, nprobe;
+    int32_t *pairs_sorted, *cnt, *cursor, *pair_off, *group_off, *item_off, *total_groups, *total_items;
+    PairArea(rsx_index* h, int64_t nq, int np, int nl) : npairs(nq * np), nlist(nl), nprobe(np) {
+        h->w_pairs.ensure((size_t)(npairs + 5 * (size_t)(nlist + 1) + 8) * 4);
+        pairs_sorted = h->w_pairs.as<int32_t>(); cnt = pairs_sorted + npairs; cursor = cnt + (nlist + 1); pair_off = cursor + (nlist + 1);
+        group_off = pair_off + (nlist + 1); item_off = group_off + (nlist + 1); total_groups = item_off + (nlist + 1); total_items = total_groups + 1;
+    }
+    // groups of G probing queries over the probe ranks [0, jmax); tile_rows > 0: also the (list, tile, group) work items
+    void group(rsx_index* h, int G, int tile_rows, int jmax, int tile_cap, hipStream_t st) const {
+        launch_group_pairs(h->w_probelist.as<int32_t>(), npairs, nlist, G, cnt, cursor, pair_off, group_off, total_groups, pairs_sorted,
+                           tile_rows ? h->d_len.as<int64_t>() : nullptr, tile_rows, tile_rows ? item_off : nullptr,
+                           tile_rows ? total_items : nullptr, nprobe, 0, jmax, tile_cap, st);
+    }
+};
+// what one batch's stages leave for the later ones
+struct BatchResult {
+    bool filtered = false;         // in-kernel candidate filtering: candidate rows instead of score rows
+    bool fused_pre_used = false;   // ... whose threshold came from the one-launch pre-pass (complete candidate rows: second chance)
+    int cand_cap = 0;
+    bool use_gather = false; PQGatherArgs gs{};   // ... whose candidates are gathered and selected in one launch
+    bool flag_overflows = false;   // IVF-Flat filtered scan: a few candidate rows overflowed — k_finalize sends their queries to the exact re-run
+    bool tab_fits = false, use_tab = false;     // k_pq_final_tab can settle the candidate rows / finalizes this batch
+};
+static void search_batch(rsx_index* h, int64_t nq, const void* dq, int dtype, int k, float* dD, int64_t* dI, bool allow_fast = true);
 // Queries whose certificate failed (h->w_uncertain, written by k_finalize) are re-run through the exact path of their index
 // kind and their result rows replaced — rare, and what makes the fast paths EXACT rather than "almost always right".
 // temp_bytes_per_query > 0 bounds the exact path's score buffer (Flat / IVF-Flat): the re-run proceeds in chunks.
+// coarse_live: the batch's k_coarse_pick wrote per-query flags behind the certificate's.
 static void rerun_uncertified(rsx_index* h, int64_t nq, const void* dq, int dtype, int k, float* dD, int64_t* dI,
-                              size_t temp_bytes_per_query, const std::function<void()>& second_chance = nullptr) {
+                              size_t temp_bytes_per_query, bool coarse_live, const std::function<void()>& second_chance = nullptr) {
     std::vector<int32_t> bad_v;
     const int32_t* bad;
-    const bool coarse_live = h->coarse_flags_live;
-    h->coarse_flags_live = false;
     auto read_flags = [&]() {
         // the fast coarse quantiser's per-query flags (k_coarse_pick: 2 = its candidate row overflowed or a score was not finite) sit behind the
         // certificate's [nq, 2 nq): one copy fetches both, and a flagged query goes to the exact re-run whatever the certificate said
@@ -236,101 +329,59 @@ static void rerun_uncertified(rsx_index* h, int64_t nq, const void* dq, int dtyp
         }
     }
 }
-
-static void search_batch(rsx_index* h, int64_t nq, const void* dq, int dtype, int k, float* dD, int64_t* dI, bool allow_fast) {
-    StageTimer tm(h, allow_fast ? "" : "fb_");
-    const int d = h->d, ld = h->ld;
-    // IVFPQ fast path: needs the 16-byte-granule layout, 16-bit integer sums, and K' <= 4096
-    const bool rot = h->kind == KIND_IVFPQ && pq_rot_family(h->CB);      // block layouts (rotated, sliced): transposed tables, work-item scans
-    const bool sliced = h->kind == KIND_IVFPQ && h->CB == PQ_SLICED;
-    const bool fast = pq_fast_applies(h, k, allow_fast);
-    int KP, BUF;
-    kp_for(h, k, fast, KP, BUF);
-    tm.mark("start");
-    // queries: fp32 copy (exact re-rank, coarse quantiser, LUT) [nq, ld]; fp16 copy for the scans
+// queries: fp32 copy (exact re-rank, coarse quantiser, LUT) [nq, ld]; fp16 copy for the scans
+static void convert_queries(rsx_index* h, const BatchPlan& P, const void* dq, int dtype, StageTimer& tm) {
+    const int64_t nq = P.nq; const int d = h->d, ld = h->ld;
     h->w_q32.ensure((size_t)nq * ld * 4);
-    int64_t nq_pad = nq > 128 ? round_up(nq, 256) : 128;   // query tiles: 128 (k_flat_gemm) or 256 (k_flat_gemm2)
-    const bool certify = h->kind != KIND_IVFPQ && allow_fast && h->flat_cert != 0;
-    // fast coarse quantiser (round 6): fp16 MFMA scores of all lists + exact chains of the candidates; needs the re-run machinery behind it
-    const int np0 = std::min(h->nprobe, h->nlist);
-    const bool coarse_fast = h->kind != KIND_FLAT && allow_fast && h->coarse_fast != 0 && (h->kind == KIND_IVFPQ ? fast : certify) && nq >= 32 &&
-                             np0 <= CP_MAXPROBE && h->nlist <= CP_MAXLIST && h->nlist > np0 && !h->h_centroids.empty() &&
-                             coarse_pick_lds(h->nlist, d, np0) <= 150 * 1024;
-    // ... whose fp16 operand is the caller's own batch when that is fp16, unpadded (d = ld) and whole tiles: the fp32 copy then rides in the
-    // GEMM's launch (extra grid rows) instead of a conversion launch of its own
-    // (not with the side-stream table build: it reads the fp32 copy before the GEMM has run)
-    const bool q16_direct = h->kind == KIND_IVFPQ && coarse_fast && h->overlap == 0 && dtype == RSX_F16 && d == ld && nq % 128 == 0 && ((uintptr_t)dq & 15) == 0;
-    if (q16_direct) {
-    } else if (h->kind == KIND_IVFPQ && coarse_fast) {
-        h->w_q16.ensure((size_t)round_up(nq, 128) * ld * 2);
-        launch_convert_to_f32_f16(dq, dtype == RSX_F16, d, nq, d, h->w_q32.as<float>(), h->w_q16.as<__half>(), ld, round_up(nq, 128), h->st);
+    if (h->kind == KIND_IVFPQ && P.coarse_fast) {
+        if (!P.q16_direct) {
+            h->w_q16.ensure((size_t)round_up(nq, 128) * ld * 2);
+            launch_convert_to_f32_f16(dq, dtype == RSX_F16, d, nq, d, h->w_q32.as<float>(), h->w_q16.as<__half>(), ld, round_up(nq, 128), h->st);
+        }
     } else
         launch_convert_to_f32(dq, dtype == RSX_F16, d, nq, d, h->w_q32.as<float>(), ld, h->st);
     if (h->kind != KIND_IVFPQ) {
-        h->w_q16.ensure((size_t)nq_pad * ld * 2);
-        h->w_flag.ensure(sizeof(int));
+        h->w_q16.ensure((size_t)P.nq_pad * ld * 2); h->w_flag.ensure(sizeof(int));
         HIPCHECK(hipMemsetAsync(h->w_flag.p, 0, sizeof(int), h->st));
-        launch_convert_to_f16(dq, dtype == RSX_F16, nq, d, h->w_q16.as<__half>(), ld, nq_pad, h->w_flag.as<int>(), h->st);
+        launch_convert_to_f16(dq, dtype == RSX_F16, nq, d, h->w_q16.as<__half>(), ld, P.nq_pad, h->w_flag.as<int>(), h->st);
     }
-    h->w_state.ensure((size_t)nq * KP * 8);
-    uint64_t* state = h->w_state.as<uint64_t>();
-    if (!q16_direct) tm.mark("convert");       // (nothing was launched for it otherwise: the widening rides in the coarse GEMM)
-    // Round 4 (overlap = 1, no longer the default): the 8-bit tables depend on the queries only — their build starts here on the side
-    // stream and runs beside the coarse quantiser and the probe selection; the per-query parameters (k_pq_qparam: they need the coarse
-    // scores) follow on the main stream once both have finished.  Round 6 measured the three cross-stream joins of a batch at ~12 us
-    // each (profiles/r06_fixed_cost.md): the default is one stream, with the table build, the parameters and the pair grouping in two launches.
-    const bool pq_fused_lut = h->kind == KIND_IVFPQ && fast && pq_lut8_fused_lds(h->M, h->Mpad, h->dsub) <= 160 * 1024 - 64;
-    const bool side_lut = pq_fused_lut && h->overlap != 0 && h->dsub == 8 && h->lut_tiled != 0 && nq >= 64;
-    // the finalize-from-the-row kernel (k_pq_final_tab) will serve this batch: let the table builder store the fp32 tables for it
-    // (M KiB per query, 100 MB at M = 96 / batch 1024) instead of every query's workgroup re-deriving its table from the 786 KB codebook
-    const bool tab_expected = pq_fused_lut && rot && h->pq_final_tab != 0 && (h->pq_final_tab == 2 || KP >= 512 || h->dsub > 8) &&
-                              std::min(h->nprobe, h->nlist) > 1 && h->pq_filter != 0 && h->pq_prepass_fused != 0 &&
-                              pq_final_tab_capacity(h->M, h->CB, k) > 0;
-    // the matrix-core table build will serve this batch and the fast coarse quantiser runs: its first pass rides in the probe-pick launch
-    const bool lut_pass0_early = coarse_fast && pq_fused_lut && !side_lut && h->dsub == 8 && h->lut_tiled >= 2 && h->metric == RSX_METRIC_INNER_PRODUCT &&
-                                 h->pq_lut_early != 0;
-    float* lut32_out = nullptr;
-    if (tab_expected) { h->w_lut.ensure((size_t)nq * h->Mpad * 256 * 4); lut32_out = h->w_lut.as<float>(); }
-    // everything that can refuse this search is checked BEFORE work is forked onto the side stream ...
-    if (h->kind != KIND_FLAT) {
-        const int np_ = std::min(h->nprobe, h->nlist);
-        if (np_ > 4096) RSX_THROW(RSX_ERR_UNSUPPORTED, "search: %d probed lists per query exceed this build's maximum of 4096", np_);
-        const int pad_ = (h->kind == KIND_IVFPQ) ? 64 : 16;
-        if (std::max<int64_t>(round_up(top_probe_sum(h, np_, pad_, pad_).first, 256), 256) >= ((int64_t)1 << 32))
-            RSX_THROW(RSX_ERR_UNSUPPORTED, "probed lists exceed 2^32 vectors per query");
-    }
-    // ... and whatever still throws behind the fork (an allocation) leaves through this guard: the side stream is drained before
-    // the caller can reuse or free the buffers its kernels read and write
-    struct SideJoin {
-        rsx_index* h; bool armed = false;
-        ~SideJoin() { if (armed && h->st2) (void)hipStreamSynchronize(h->st2); }
-    } side_join{h};
-    if (side_lut) {
-        ensure_side_stream(h);
-        h->w_lut8.ensure((size_t)nq * h->Mpad * 256);
-        h->w_qparam.ensure((size_t)nq * 16);
-        h->w_lutws.ensure(pq_lut8_tiled_ws(nq, h->Mpad));
-        HIPCHECK(hipEventRecord(h->ev_fork, h->st));
-        HIPCHECK(hipStreamWaitEvent(h->st2, h->ev_fork, 0));
-        launch_pq_lut8(nullptr, h->w_q32.as<float>(), ld, h->d_codebooks.as<float>(), h->dsub, nq, h->M, h->Mpad, nullptr, 0,
-                       h->w_lut8.as<uint8_t>(), h->w_qparam.p, h->w_lutws.p, sliced ? 2 : rot ? 1 : 0, h->st2, 1, lut32_out);
-        HIPCHECK(hipEventRecord(h->ev_lut, h->st2));
-        side_join.armed = true;
-    }
-
+    h->w_state.ensure((size_t)nq * P.KP * 8);
+    if (!P.q16_direct) tm.mark("convert");       // (nothing was launched for it otherwise: the widening rides in the coarse GEMM)
+}
+// the fp32 tables k_pq_final_tab reads, stored by the table builder (plan: tab_expected; search_batch sizes them)
+static float* lut32_out(rsx_index* h, const BatchPlan& P) { return P.tab_expected ? h->w_lut.as<float>() : nullptr; }
+// everything that can refuse this search is checked BEFORE work is forked onto the side stream
+static void check_supported(rsx_index* h, const BatchPlan& P) {
+    if (h->kind == KIND_FLAT) return;
+    if (P.nprobe > 4096) RSX_THROW(RSX_ERR_UNSUPPORTED, "search: %d probed lists per query exceed this build's maximum of 4096", P.nprobe);
+    if (P.tmax >= ((int64_t)1 << 32)) RSX_THROW(RSX_ERR_UNSUPPORTED, "probed lists exceed 2^32 vectors per query");
+}
+// Round 4 (overlap = 1, no longer the default): the 8-bit tables depend on the queries only — their build starts here on the side
+// stream and runs beside the coarse quantiser and the probe selection; the per-query parameters (k_pq_qparam: they need the coarse
+// scores) follow on the main stream once both have finished.  Round 6 measured the three cross-stream joins of a batch at ~12 us
+// each (profiles/r06_fixed_cost.md): the default is one stream, with the table build, the parameters and the pair grouping in two launches.
+static void fork_side_tables(rsx_index* h, const BatchPlan& P) {
+    ensure_side_stream(h);
+    h->w_lut8.ensure((size_t)P.nq * h->Mpad * 256); h->w_qparam.ensure((size_t)P.nq * 16); h->w_lutws.ensure(pq_lut8_tiled_ws(P.nq, h->Mpad));
+    HIPCHECK(hipEventRecord(h->ev_fork, h->st));
+    HIPCHECK(hipStreamWaitEvent(h->st2, h->ev_fork, 0));
+    launch_pq_lut8(nullptr, h->w_q32.as<float>(), h->ld, h->d_codebooks.as<float>(), h->dsub, P.nq, h->M, h->Mpad, nullptr, 0,
+                   h->w_lut8.as<uint8_t>(), h->w_qparam.p, h->w_lutws.p, P.sliced ? 2 : P.rot ? 1 : 0, h->st2, 1, lut32_out(h, P));
+    HIPCHECK(hipEventRecord(h->ev_lut, h->st2));
+}
+static FinalizeArgs finalize_args(rsx_index* h, const BatchPlan& P, float* dD, int64_t* dI) {
+    const int d = h->d, ld = h->ld;
     FinalizeArgs fa{};
-    fa.kind = h->kind; fa.metric = h->metric; fa.state = state; fa.KP = KP; fa.k = k; fa.nq = nq;
-    // Flat / IVF-Flat re-score rows of 2 d bytes that sit anywhere in HBM: only the k + max(8, k / 16) best approximate candidates the
-    // certificate needs, not the power of two the selection and the sort round them up to (round 5: k = 1000 re-read 2048 rows per query)
-    // (only where the certificate runs — `certify`: with flat_cert = 0 there is no second pass, and the uncertified mode keeps re-ranking all
-    //  K' candidates as it always did: ADVICE r5)
-    if (h->kind != KIND_IVFPQ && allow_fast && certify) fa.KPv = std::min(KP, k + std::max(8, k / 16));
-    fa.list_base = h->d_base.as<int64_t>();
-    fa.ids = (h->kind == KIND_FLAT && !h->custom_ids) ? nullptr : h->ids.as<int64_t>();
+    fa.kind = h->kind; fa.metric = h->metric; fa.state = h->w_state.as<uint64_t>(); fa.KP = P.KP; fa.k = P.k; fa.nq = P.nq;
+    fa.list_base = h->d_base.as<int64_t>(); fa.ids = (h->kind == KIND_FLAT && !h->custom_ids) ? nullptr : h->ids.as<int64_t>();
     fa.Q32 = h->w_q32.as<float>(); fa.ldq = ld; fa.d = d;
-    fa.X = h->data.p; fa.x_f16 = h->storage_f16; fa.ld = ld;
-    fa.D = dD; fa.I = dI;
-    if (certify) {
+    fa.X = h->data.p; fa.x_f16 = h->storage_f16; fa.ld = ld; fa.D = dD; fa.I = dI;
+    if (P.certify) {
+        // Flat / IVF-Flat re-score rows of 2 d bytes that sit anywhere in HBM: only the k + max(8, k / 16) best approximate candidates the
+        // certificate needs, not the power of two the selection and the sort round them up to (round 5: k = 1000 re-read 2048 rows per query)
+        // (only where the certificate runs: with flat_cert = 0 there is no second pass, and the uncertified mode keeps re-ranking all
+        //  K' candidates as it always did: ADVICE r5)
+        fa.KPv = std::min(P.KP, P.k + std::max(8, P.k / 16));
         // |approx - exact| of the fp16-MFMA scan for ANY stored vector (Cauchy-Schwarz on the per-element errors):
         //   fp32 accumulation of d exact products       (d + 2) 2^-24 |q| |x|
         //   fp32 rows rounded to fp16 inside the scan   2^-11 |q| |x|        (fp16 storage is lossless)
@@ -338,168 +389,149 @@ static void search_batch(rsx_index* h, int64_t nq, const void* dq, int dtype, in
         //   L2: the ranking score adds -|x|^2/2 (fp32)  (d + 4) 2^-24 |x|^2  (folded into the absolute term)
         const float u24 = 5.9604645e-8f, u11 = 4.8828125e-4f;
         const float xmax = sqrtf(h->max_norm2) * 1.0000002f;
-        h->w_uncertain.ensure((size_t)nq * 8);
-        fa.uncertain = h->w_uncertain.as<int32_t>();
-        fa.cert_xmax = xmax;
+        h->w_uncertain.ensure((size_t)P.nq * 8);
+        fa.uncertain = h->w_uncertain.as<int32_t>(); fa.cert_xmax = xmax;
         fa.cert_rel = ((float)d + 2.0f) * u24 * 1.01f + (h->storage_f16 ? 0.0f : u11 * 1.002f);
-        fa.cert_rel_qlossy = u11 * 1.002f + u11 * u11;
-        fa.cert_qflag = h->w_flag.as<int>();
+        fa.cert_rel_qlossy = u11 * 1.002f + u11 * u11; fa.cert_qflag = h->w_flag.as<int>();
         fa.cert_abs = sqrtf((float)d) * u24 + (h->metric == RSX_METRIC_L2 ? ((float)d + 4.0f) * u24 * xmax : 0.0f);
     }
-
-    if (h->kind == KIND_FLAT) {
-        const float* bias = nullptr;
-        if (h->metric == RSX_METRIC_L2) {
-            // ranking score = <q,x> - |x|^2/2 ; bias buffer holds -|x|^2/2 (derived from norms)
-            h->w_misc.ensure((size_t)h->ntotal * 4);
-            bias = h->w_misc.as<float>();
-        }
-        const int64_t N = h->ntotal;
-        if (N == 0) {
-            launch_fill_u64(state, nq * KP, 0, h->st);
-        } else if (!allow_fast) {
-            // exact mode (queries the certificate could not clear): fp64 scores of every row, rounded once = the canonical
-            // scores themselves, then the ordinary selection
-            const int64_t tstride = round_up(N, 16);
-            h->w_temp.ensure((size_t)nq * tstride * 4);
-            ExactScoreArgs ea{};
-            ea.kind = KIND_FLAT; ea.metric = h->metric; ea.nq = nq; ea.Q32 = h->w_q32.as<float>(); ea.ldq = ld; ea.d = d;
-            ea.X = h->data.p; ea.x_f16 = h->storage_f16; ea.ld = ld; ea.flat_n = N;
-            ea.temp = h->w_temp.as<float>(); ea.tstride = tstride;
-            launch_exact_scores(ea, h->st);
-            sel_apply_flat(h, h->w_temp.as<float>(), tstride, nq, N, 0);      // filtered search: the unselected rows leave the score rows
+    return fa;
+}
+// exact mode (allow_fast = false) and small batches: whole score rows, then one selection
+static void flat_score_rows(rsx_index* h, const BatchPlan& P, const float* bias, StageTimer& tm) {
+    const int64_t nq = P.nq, N = h->ntotal, tstride = round_up(N, 16); const int ld = h->ld;
+    h->w_temp.ensure((size_t)nq * tstride * 4);
+    if (!P.allow_fast) {
+        // exact mode (queries the certificate could not clear): fp64 scores of every row, rounded once = the canonical
+        // scores themselves, then the ordinary selection
+        ExactScoreArgs ea{};
+        ea.kind = KIND_FLAT; ea.metric = h->metric; ea.nq = nq; ea.Q32 = h->w_q32.as<float>(); ea.ldq = ld; ea.d = h->d;
+        ea.X = h->data.p; ea.x_f16 = h->storage_f16; ea.ld = ld; ea.flat_n = N;
+        ea.temp = h->w_temp.as<float>(); ea.tstride = tstride;
+        launch_exact_scores(ea, h->st);
+    } else {
+        // small batch: stream the database once per group of 16 queries (list-scan kernel)
+        ListScanArgs a{};
+        a.Q16 = h->w_q16.as<__half>(); a.ld = ld; a.X = h->data.p; a.x_f16 = h->storage_f16; a.bias = bias;
+        a.list_base = h->d_base.as<int64_t>(); a.list_len = h->d_len.as<int64_t>();
+        a.flat_mode = 1; a.flat_n = N; a.nq = (int)nq; a.nprobe = 1; a.nlist = 1;
+        a.temp = h->w_temp.as<float>(); a.tstride = tstride;
+        a.chunk_rows = 1024;
+        if (list_scan2_chunk_rows(h->storage_f16, ld) > 0 && round_up(N, 16) / list_scan2_chunk_rows(h->storage_f16, ld) < 65535)
+            a.chunk_rows = list_scan2_chunk_rows(h->storage_f16, ld);     // LDS-DMA streaming kernel
+        a.max_groups = (int)((nq + 15) / 16);
+        a.max_chunks = (int)((round_up(N, 16) + a.chunk_rows - 1) / a.chunk_rows);
+        if (a.max_chunks > 65535) { a.chunk_rows = (int)round_up((round_up(N, 16) + 65534) / 65535, 64); a.max_chunks = (int)((round_up(N, 16) + a.chunk_rows - 1) / a.chunk_rows); }
+        launch_list_scan(a, h->st);
+    }
+    sel_apply_flat(h, h->w_temp.as<float>(), tstride, nq, N, 0);      // filtered search: the unselected rows leave the score rows
+    tm.mark("scan");
+    // threshold = the KP-th approximate key (not the k-th): the exact re-rank needs the true top-KP
+    select_rows(h, h->w_temp.as<float>(), tstride, nullptr, 0, N, 0, nq, P.KP, P.BUF, P.KP, h->w_state.as<uint64_t>(), false);
+    tm.mark("select");
+}
+// full batches: chunked GEMM — a threshold phase through the score buffer, then filtered GEMM stages (fa: their deferred counters)
+static void flat_staged(rsx_index* h, const BatchPlan& P, const float* bias, FinalizeArgs& fa, StageTimer& tm) {
+    const int64_t nq = P.nq, N = h->ntotal, CH = 65536; const int ld = h->ld, KP = P.KP;
+    uint64_t* state = h->w_state.as<uint64_t>();
+    h->w_temp.ensure((size_t)P.nq_pad * CH * 4);
+    launch_fill_u64(state, nq * KP, 0, h->st);
+    // chunk 0 through the score buffer: its top-K' gives every query a running threshold
+    int64_t done_rows = 0;
+    auto chunk_pass = [&](int64_t v0, int64_t vend) {
+        int64_t nv = std::min<int64_t>(CH, vend - v0);
+        launch_flat_gemm(h->w_q16.as<__half>(), (int)P.nq_pad, h->data.p, h->storage_f16, v0, nv, ld, bias,
+                         h->w_temp.as<float>(), CH, h->st);
+        sel_apply_flat(h, h->w_temp.as<float>(), CH, nq, nv, v0);
+        select_rows(h, h->w_temp.as<float>(), CH, nullptr, 0, nv, (uint32_t)v0, nq, KP, P.BUF, KP, state, true);
+    };
+    // Threshold phase: the K'-th key of the first rows is a threshold for everything behind them, so a filtered pass over
+    // the rows [a, b) keeps ~K' (b - a) / a keys per query.  One 65536-row chunk is right for k = 10 (K' = 32: 5 k keys at
+    // 10M rows).  For the reference's n_docs = 1000 (K' = 2048) one chunk let 310 k keys through, overflowed every candidate row
+    // and fell back to 153 chunk passes (550 ms per batch, round 4); 160 K' rows and ONE filtered launch over the rest still
+    // emitted 62 k keys per query — 64 M atomically placed keys, the filtered GEMM 27.8 instead of 17.4 ms — behind five
+    // chunk selections of 0.93 ms.  Now: flat_pre_mult x K' rows through the score buffer (default 16, in units: below), then the rest
+    // in STAGES of geometrically growing row ranges, each one filtered launch + one selection that tightens the threshold for
+    // the next: S stages of ratio r = (N / first)^(1/S) emit ~S K' (r - 1) keys.  Measured at 10M x 768, batch 1024
+    // (profiles/r04_flat_staged_filter.md): k = 1000 36.5 -> 23.3 ms (S = 5), k = 10 18.9 -> 17.2 ms (S = 2: even 5 k keys
+    // per query cost the single filtered launch 1.6 ms), k = 100 17.8 ms.
+    // (round 6: for small K' the threshold phase and the stage boundaries count in UNITS of a quarter chunk — at K' = 32 the selection
+    //  over a full 65536-column chunk cost 0.43 ms of a 16.9 ms batch, four times what a 16384-row threshold phase needs; the
+    //  stages pass ~1.5 k keys per query instead of ~700, which the queued epilogue does not notice.  Larger K': half a chunk and 16 K' rows —
+    //  k = 1000: scan0 1.32 -> 0.62 ms, one stage more, 20.07 -> 19.68 ms per batch (profiles/r06_large_k_flat.md).  flat_pre_unit: rows, 0 = default)
+    const int64_t U = h->flat_pre_unit > 0 ? std::min<int64_t>(CH, round_up(h->flat_pre_unit, 256)) : (KP <= 64 ? CH / 4 : CH / 2);
+    const int64_t nchunks = (N + U - 1) / U;          // ... in units
+    const int64_t n0 = std::min<int64_t>(nchunks, std::max<int64_t>(1, ((int64_t)KP * std::max(1, h->flat_pre_mult) + U - 1) / U));
+    for (int64_t c = 0; c < n0; c++) chunk_pass(c * U, std::min<int64_t>(N, (c + 1) * U));
+    done_rows = std::min<int64_t>(n0 * U, N);
+    tm.mark("scan0");
+    if (done_rows < N && P.flat_filter != 0) {
+        int S = h->flat_stages;
+        if (S <= 0) S = KP <= 64 ? 2 : std::min(6, std::max(1, (int)lround(log((double)nchunks / (double)n0) / log(3.0))));
+        const double r = pow((double)nchunks / (double)n0, 1.0 / S);
+        const int cap = KP <= 64 ? 32768 : 131072;
+        h->w_cand.ensure((size_t)nq * cap * 8);
+        // With the certificate behind it (the default) a stage does not wait for its counts: every stage owns a set of per-query
+        // counters, the selection clamps an overflowed row to the buffer, and k_finalize flags a query any of whose stage rows
+        // overflowed — it joins the exact re-run like a query the certificate could not clear.  Round 6: the count read-back +
+        // host synchronisation per stage (five at the reference's n_docs = 1000) left the GPU idle between the stages.
+        // flat_cert = 0 has no re-run behind it and keeps the per-stage check (an overflowed stage is redone chunk by chunk).
+        const bool deferred = P.certify;
+        const size_t cc_stride = (size_t)nq * CCS;
+        h->w_candcnt.ensure(cc_stride * 8 * (deferred ? (size_t)S : 1));
+        if (deferred) HIPCHECK(hipMemsetAsync(h->w_candcnt.p, 0, cc_stride * 8 * (size_t)S, h->st));
+        std::vector<unsigned long long> cnts(deferred ? 0 : cc_stride);
+        int stages_run = 0;
+        for (int st_ = 0; st_ < S && done_rows < N; st_++) {
+            // stage boundaries on chunk multiples (the database tiles of the GEMM stay aligned)
+            int64_t endc = st_ == S - 1 ? nchunks : std::min<int64_t>(nchunks, std::max<int64_t>(done_rows / U + 1, (int64_t)llround((double)n0 * pow(r, st_ + 1))));
+            const int64_t end = std::min<int64_t>(N, endc * U);
+            unsigned long long* cc = h->w_candcnt.as<unsigned long long>() + (deferred ? cc_stride * (size_t)st_ : 0);
+            // ONE GEMM launch over the stage's rows whose epilogue keeps only keys beating the running K'-th key
+            if (!deferred) HIPCHECK(hipMemsetAsync(cc, 0, cc_stride * 8, h->st));
+            launch_flat_gemm_filter(h->w_q16.as<__half>(), (int)P.nq_pad, (int)nq, h->data.p, h->storage_f16, done_rows,
+                                    end - done_rows, ld, bias, state + (KP - 1), KP, h->w_cand.as<uint64_t>(), cc, cap, h->st);
             tm.mark("scan");
-            select_rows(h, h->w_temp.as<float>(), tstride, nullptr, 0, N, 0, nq, KP, BUF, KP, state, false);
-            tm.mark("select");
-        } else if (nq <= 32) {
-            // small batch: stream the database once per group of 16 queries (list-scan kernel)
-            int64_t tstride = round_up(N, 16);
-            h->w_temp.ensure((size_t)nq * tstride * 4);
-            ListScanArgs a{};
-            a.Q16 = h->w_q16.as<__half>(); a.ld = ld; a.X = h->data.p; a.x_f16 = h->storage_f16; a.bias = bias;
-            a.list_base = h->d_base.as<int64_t>(); a.list_len = h->d_len.as<int64_t>();
-            a.flat_mode = 1; a.flat_n = N; a.nq = (int)nq; a.nprobe = 1; a.nlist = 1;
-            a.temp = h->w_temp.as<float>(); a.tstride = tstride;
-            a.chunk_rows = 1024;
-            if (list_scan2_chunk_rows(h->storage_f16, ld) > 0 && round_up(N, 16) / list_scan2_chunk_rows(h->storage_f16, ld) < 65535)
-                a.chunk_rows = list_scan2_chunk_rows(h->storage_f16, ld);     // LDS-DMA streaming kernel
-            a.max_groups = (int)((nq + 15) / 16);
-            a.max_chunks = (int)((round_up(N, 16) + a.chunk_rows - 1) / a.chunk_rows);
-            if (a.max_chunks > 65535) { a.chunk_rows = (int)round_up((round_up(N, 16) + 65534) / 65535, 64); a.max_chunks = (int)((round_up(N, 16) + a.chunk_rows - 1) / a.chunk_rows); }
-            launch_list_scan(a, h->st);
-            sel_apply_flat(h, h->w_temp.as<float>(), tstride, nq, N, 0);
-            tm.mark("scan");
-            // threshold = the KP-th approximate key (not the k-th): the exact re-rank needs the true top-KP
-            select_rows(h, h->w_temp.as<float>(), tstride, nullptr, 0, N, 0, nq, KP, BUF, KP, state, false);
-            tm.mark("select");
-        } else {
-            const int64_t CH = 65536;
-            h->w_temp.ensure((size_t)nq_pad * CH * 4);
-            launch_fill_u64(state, nq * KP, 0, h->st);
-            // chunk 0 through the score buffer: its top-K' gives every query a running threshold
-            int64_t done_rows = 0;
-            auto chunk_pass = [&](int64_t v0, int64_t vend) {
-                int64_t nv = std::min<int64_t>(CH, vend - v0);
-                launch_flat_gemm(h->w_q16.as<__half>(), (int)nq_pad, h->data.p, h->storage_f16, v0, nv, ld, bias,
-                                 h->w_temp.as<float>(), CH, h->st);
-                sel_apply_flat(h, h->w_temp.as<float>(), CH, nq, nv, v0);
-                select_rows(h, h->w_temp.as<float>(), CH, nullptr, 0, nv, (uint32_t)v0, nq, KP, BUF, KP, state, true);
-            };
-            // Threshold phase: the K'-th key of the first rows is a threshold for everything behind them, so a filtered pass over
-            // the rows [a, b) keeps ~K' (b - a) / a keys per query.  One 65536-row chunk is right for k = 10 (K' = 32: 5 k keys at
-            // 10M rows).  For the reference's n_docs = 1000 (K' = 2048) one chunk let 310 k keys through, overflowed every candidate row
-            // and fell back to 153 chunk passes (550 ms per batch, round 4); 160 K' rows and ONE filtered launch over the rest still
-            // emitted 62 k keys per query — 64 M atomically placed keys, the filtered GEMM 27.8 instead of 17.4 ms — behind five
-            // chunk selections of 0.93 ms.  Now: flat_pre_mult x K' rows through the score buffer (default 16, in units: below), then the rest
-            // in STAGES of geometrically growing row ranges, each one filtered launch + one selection that tightens the threshold for
-            // the next: S stages of ratio r = (N / first)^(1/S) emit ~S K' (r - 1) keys.  Measured at 10M x 768, batch 1024
-            // (profiles/r04_flat_staged_filter.md): k = 1000 36.5 -> 23.3 ms (S = 5), k = 10 18.9 -> 17.2 ms (S = 2: even 5 k keys
-            // per query cost the single filtered launch 1.6 ms), k = 100 17.8 ms.
-            // (round 6: for small K' the threshold phase and the stage boundaries count in UNITS of a quarter chunk — at K' = 32 the selection
-            //  over a full 65536-column chunk cost 0.43 ms of a 16.9 ms batch, four times what a 16384-row threshold phase needs; the
-            //  stages pass ~1.5 k keys per query instead of ~700, which the queued epilogue does not notice.  Larger K': half a chunk and 16 K' rows —
-            //  k = 1000: scan0 1.32 -> 0.62 ms, one stage more, 20.07 -> 19.68 ms per batch (profiles/r06_large_k_flat.md).  flat_pre_unit: rows, 0 = default)
-            const int64_t U = h->flat_pre_unit > 0 ? std::min<int64_t>(CH, round_up(h->flat_pre_unit, 256)) : (KP <= 64 ? CH / 4 : CH / 2);
-            const int64_t nchunks = (N + U - 1) / U;          // ... in units
-            const int64_t n0 = std::min<int64_t>(nchunks, std::max<int64_t>(1, ((int64_t)KP * std::max(1, h->flat_pre_mult) + U - 1) / U));
-            for (int64_t c = 0; c < n0; c++) chunk_pass(c * U, std::min<int64_t>(N, (c + 1) * U));
-            done_rows = std::min<int64_t>(n0 * U, N);
-            tm.mark("scan0");
-            if (done_rows < N && h->flat_filter != 0) {
-                int S = h->flat_stages;
-                if (S <= 0) S = KP <= 64 ? 2 : std::min(6, std::max(1, (int)lround(log((double)nchunks / (double)n0) / log(3.0))));
-                const double r = pow((double)nchunks / (double)n0, 1.0 / S);
-                const int cap = KP <= 64 ? 32768 : 131072;
-                h->w_cand.ensure((size_t)nq * cap * 8);
-                // With the certificate behind it (the default) a stage does not wait for its counts: every stage owns a set of per-query
-                // counters, the selection clamps an overflowed row to the buffer, and k_finalize flags a query any of whose stage rows
-                // overflowed — it joins the exact re-run like a query the certificate could not clear.  Round 6: the count read-back +
-                // host synchronisation per stage (five at the reference's n_docs = 1000) left the GPU idle between the stages.
-                // flat_cert = 0 has no re-run behind it and keeps the per-stage check (an overflowed stage is redone chunk by chunk).
-                const bool deferred = certify;
-                const size_t cc_stride = (size_t)nq * CCS;
-                h->w_candcnt.ensure(cc_stride * 8 * (deferred ? (size_t)S : 1));
-                if (deferred) HIPCHECK(hipMemsetAsync(h->w_candcnt.p, 0, cc_stride * 8 * (size_t)S, h->st));
-                std::vector<unsigned long long> cnts(deferred ? 0 : cc_stride);
-                int stages_run = 0;
-                for (int st_ = 0; st_ < S && done_rows < N; st_++) {
-                    // stage boundaries on chunk multiples (the database tiles of the GEMM stay aligned)
-                    int64_t endc = st_ == S - 1 ? nchunks : std::min<int64_t>(nchunks, std::max<int64_t>(done_rows / U + 1, (int64_t)llround((double)n0 * pow(r, st_ + 1))));
-                    const int64_t end = std::min<int64_t>(N, endc * U);
-                    unsigned long long* cc = h->w_candcnt.as<unsigned long long>() + (deferred ? cc_stride * (size_t)st_ : 0);
-                    // ONE GEMM launch over the stage's rows whose epilogue keeps only keys beating the running K'-th key
-                    if (!deferred) HIPCHECK(hipMemsetAsync(cc, 0, cc_stride * 8, h->st));
-                    launch_flat_gemm_filter(h->w_q16.as<__half>(), (int)nq_pad, (int)nq, h->data.p, h->storage_f16, done_rows,
-                                            end - done_rows, ld, bias, state + (KP - 1), KP, h->w_cand.as<uint64_t>(), cc, cap, h->st);
-                    tm.mark("scan");
-                    bool filtered_ok = true;
-                    if (!deferred) {
-                        HIPCHECK(hipMemcpyAsync(cnts.data(), cc, cc_stride * 8, hipMemcpyDeviceToHost, h->st));
-                        HIPCHECK(hipStreamSynchronize(h->st));
-                        for (int64_t qi = 0; qi < nq; qi++) if (cnts[(size_t)qi * CCS] > (unsigned long long)cap) { filtered_ok = false; break; }
-                    }
-                    if (filtered_ok) {
-                        SelectArgs b{};
-                        b.in = h->w_cand.p; b.in_is_keys = 1; b.row_stride = cap;
-                        b.row_n = reinterpret_cast<const int64_t*>(cc); b.row_n_stride = CCS; b.n_uniform = cap;
-                        b.seg_len = cap; b.nseg = 1; b.idx_base = 0;
-                        b.init = state; b.out = state; b.out_row_stride = KP;
-                        b.nrows = nq; b.KP = KP; b.BUF = BUF; b.k = KP;
-                        launch_select(b, h->st);
-                        tm.mark("select");
-                    } else {
-                        h->timing["flat_filter_overflows"] += 1;   // adversarial order: redo this stage's rows chunk by chunk
-                        for (int64_t v0 = done_rows; v0 < end; v0 += CH) chunk_pass(v0, end);
-                        tm.mark("scan");
-                    }
-                    done_rows = end;
-                    stages_run = st_ + 1;
-                }
-                if (deferred) { fa.cand_cnt = h->w_candcnt.as<unsigned long long>(); fa.cand_cap = cap; fa.cand_cnt_n = stages_run; fa.cand_cnt_stride = (int64_t)cc_stride; }
+            bool filtered_ok = true;
+            if (!deferred) {
+                HIPCHECK(hipMemcpyAsync(cnts.data(), cc, cc_stride * 8, hipMemcpyDeviceToHost, h->st));
+                HIPCHECK(hipStreamSynchronize(h->st));
+                for (int64_t qi = 0; qi < nq; qi++) if (cnts[(size_t)qi * CCS] > (unsigned long long)cap) { filtered_ok = false; break; }
             }
-            if (done_rows < N) {       // flat_filter = 0
-                for (int64_t v0 = done_rows; v0 < N; v0 += CH) chunk_pass(v0, N);
+            if (filtered_ok) {
+                merge_key_rows(h, h->w_cand.p, cc, cap, nq, state, state, KP, P.BUF);
+                tm.mark("select");
+            } else {
+                h->timing["flat_filter_overflows"] += 1;   // adversarial order: redo this stage's rows chunk by chunk
+                for (int64_t v0 = done_rows; v0 < end; v0 += CH) chunk_pass(v0, end);
                 tm.mark("scan");
             }
+            done_rows = end;
+            stages_run = st_ + 1;
         }
-        launch_finalize(fa, h->st);
-        tm.mark("finalize");
-        tm.finish();
-        if (certify && N > 0) rerun_uncertified(h, nq, dq, dtype, k, dD, dI, (size_t)round_up(N, 16) * 4);
-        return;
+        if (deferred) { fa.cand_cnt = h->w_candcnt.as<unsigned long long>(); fa.cand_cap = cap; fa.cand_cnt_n = stages_run; fa.cand_cnt_stride = (int64_t)cc_stride; }
     }
-
-    // ---------------- IVF ----------------
-    const int nlist = h->nlist;
-    const int nprobe = std::min(h->nprobe, nlist);
-    // 1. coarse quantiser (exact fp32) + top-nprobe
+    if (done_rows < N) {       // flat_filter = 0 (or a filtered search)
+        for (int64_t v0 = done_rows; v0 < N; v0 += CH) chunk_pass(v0, N);
+        tm.mark("scan");
+    }
+}
+static void flat_scan(rsx_index* h, const BatchPlan& P, FinalizeArgs& fa, StageTimer& tm) {
+    // ranking score = <q,x> - |x|^2/2 ; bias buffer holds -|x|^2/2 (derived from norms)
+    if (h->metric == RSX_METRIC_L2) h->w_misc.ensure((size_t)h->ntotal * 4);
+    const float* bias = h->metric == RSX_METRIC_L2 ? h->w_misc.as<float>() : nullptr;
+    if (h->ntotal == 0) launch_fill_u64(h->w_state.as<uint64_t>(), P.nq * P.KP, 0, h->st);
+    else if (!P.allow_fast || P.nq <= 32) flat_score_rows(h, P, bias, tm);
+    else flat_staged(h, P, bias, fa, tm);
+}
+// coarse quantiser + the top-nprobe lists of every query: w_probelist, w_dis0, w_segstart (the fast form also writes the per-query
+// flags behind w_uncertain's certificate words that rerun_uncertified merges)
+static void coarse_quantiser(rsx_index* h, const BatchPlan& P, const void* dq, int dtype, StageTimer& tm) {
+    const int64_t nq = P.nq; const int d = h->d, ld = h->ld, nlist = h->nlist, nprobe = P.nprobe;
     const int nlp = (int)round_up(nlist, 4);   // row stride of the coarse scores: 16-byte aligned rows for k_select
-    const int pad_to = (h->kind == KIND_IVFPQ) ? 64 : 16;
-    h->w_probelist.ensure((size_t)nq * nprobe * 4);
-    h->w_dis0.ensure((size_t)nq * nprobe * 4);
-    h->w_segstart.ensure((size_t)nq * (nprobe + 1) * 8);
-    if (coarse_fast) {
-        const int64_t nqp = h->kind == KIND_IVFPQ ? round_up(nq, 128) : nq_pad;
+    h->w_probelist.ensure((size_t)nq * nprobe * 4); h->w_dis0.ensure((size_t)nq * nprobe * 4); h->w_segstart.ensure((size_t)nq * (nprobe + 1) * 8);
+    if (P.coarse_fast) {
+        const int64_t nqp = h->kind == KIND_IVFPQ ? round_up(nq, 128) : P.nq_pad;
         const int64_t nl128 = round_up(nlist, 128);
         if (h->cent16_gen != h->cent_gen || !h->cent16.p) {       // the centroids' fp16 copy + the norm bound, once per centroid set
             h->cent16.ensure((size_t)nl128 * ld * 2);
@@ -510,7 +542,7 @@ static void search_batch(rsx_index* h, int64_t nq, const void* dq, int dtype, in
             h->cent16_gen = h->cent_gen;
         }
         h->w_coarse.ensure((size_t)nqp * nlp * 4);
-        if (q16_direct) launch_coarse_approx((const __half*)dq, nqp, h->cent16.as<__half>(), nlist, ld, h->w_coarse.as<float>(), nlp, h->st, h->w_q32.as<float>(), nq * (int64_t)ld);
+        if (P.q16_direct) launch_coarse_approx((const __half*)dq, nqp, h->cent16.as<__half>(), nlist, ld, h->w_coarse.as<float>(), nlp, h->st, h->w_q32.as<float>(), nq * (int64_t)ld);
         else launch_coarse_approx(h->w_q16.as<__half>(), nqp, h->cent16.as<__half>(), nlist, ld, h->w_coarse.as<float>(), nlp, h->st);
         tm.mark("coarse");
         h->w_uncertain.ensure((size_t)nq * 8);
@@ -518,543 +550,493 @@ static void search_batch(rsx_index* h, int64_t nq, const void* dq, int dtype, in
         cp.approx = h->w_coarse.as<float>(); cp.nlp = nlp; cp.nlist = nlist; cp.Q32 = h->w_q32.as<float>(); cp.ld = ld; cp.d = d;
         cp.C = h->d_centroids.as<float>(); cp.cmax = h->cent_cmax;
         cp.ef = (dtype == RSX_F16 ? 1.0f : 2.0f) * 4.8828125e-4f;        // centroids rounded to fp16; fp32 queries as well
-        cp.nprobe = nprobe; cp.list_len = h->d_len.as<int64_t>(); cp.pad_to = pad_to;
+        cp.nprobe = nprobe; cp.list_len = h->d_len.as<int64_t>(); cp.pad_to = P.pad_to;
         cp.probe_list = h->w_probelist.as<int32_t>(); cp.dis0 = h->w_dis0.as<float>(); cp.seg_start = h->w_segstart.as<int64_t>();
         cp.bad = h->w_uncertain.as<int32_t>() + nq;
-        if (lut_pass0_early) {      // pass 0 of the table build needs the queries only: extra workgroups of this launch
+        if (P.lut_pass0_early) {      // pass 0 of the table build needs the queries only: extra workgroups of this launch
             h->w_lutws.ensure(pq_lut8_tiled_ws(nq, h->Mpad));
             cp.lp0 = LutPass0Args{h->w_q32.as<float>(), ld, h->d_codebooks.as<float>(), h->M, h->Mpad, nq, reinterpret_cast<float*>(h->w_lutws.p),
                                   pq_lut_pass0_blocks(nq, h->Mpad)};
         }
         launch_coarse_pick(cp, nq, h->st);
-        h->coarse_flags_live = true;
     } else {
         h->w_coarse.ensure((size_t)nq * nlp * 4);
         launch_gemm_exact_scores(h->w_q32.p, 0, nq, ld, h->d_centroids.as<float>(), nlist, d, h->w_coarse.as<float>(), nlp, h->st);
         tm.mark("coarse");
-        int KPp = std::max(16, pow2ceil(nprobe));
-        int BUFp = std::max(2 * KPp, 256);
+        const int KPp = std::max(16, pow2ceil(nprobe)), BUFp = std::max(2 * KPp, 256);
         h->w_probekeys.ensure((size_t)nq * KPp * 8);
         select_rows(h, h->w_coarse.as<float>(), nlp, nullptr, 0, nlist, 0, nq, KPp, BUFp, nprobe, h->w_probekeys.as<uint64_t>(), false);
-        // 2. probe set-up
-        launch_probe_setup(h->w_probekeys.as<uint64_t>(), KPp, nq, nprobe, h->d_len.as<int64_t>(), pad_to,
+        // probe set-up
+        launch_probe_setup(h->w_probekeys.as<uint64_t>(), KPp, nq, nprobe, h->d_len.as<int64_t>(), P.pad_to,
                            h->w_probelist.as<int32_t>(), h->w_dis0.as<float>(), h->w_segstart.as<int64_t>(), h->st);
     }
-    if (side_lut) HIPCHECK(hipEventRecord(h->ev_probe, h->st));
+    if (P.side_lut) HIPCHECK(hipEventRecord(h->ev_probe, h->st));
     tm.mark("select_probe");
-    if (h->profile >= 2) {
-        std::vector<int32_t> pl((size_t)nq * nprobe);
-        HIPCHECK(hipMemcpyAsync(pl.data(), h->w_probelist.p, pl.size() * 4, hipMemcpyDeviceToHost, h->st));
+}
+// profile >= 2: the vectors this batch scans
+static void count_scanned(rsx_index* h, const BatchPlan& P, StageTimer& tm) {
+    const int nlist = h->nlist;
+    std::vector<int32_t> pl((size_t)P.nq * P.nprobe);
+    HIPCHECK(hipMemcpyAsync(pl.data(), h->w_probelist.p, pl.size() * 4, hipMemcpyDeviceToHost, h->st));
+    HIPCHECK(hipStreamSynchronize(h->st));
+    double tot = 0;
+    std::vector<int32_t> pc((size_t)nlist, 0);
+    for (int32_t l : pl) if (l >= 0) { tot += (double)h->h_len[(size_t)l]; pc[(size_t)l]++; }
+    h->timing["scanned_vectors"] += tot;
+    // the same batch seen list-major: vectors of every list probed at least once (what HBM must deliver), and vectors x
+    // groups of 4 probing queries (what the IVF-PQ fast scan gathers)
+    // (queries per table gather of the scan this index takes: 8 for the sliced layout and the M = 64 eight-query form, 16 at M = 16, else 4)
+    const int gq = 4 * P.ngq;
+    double uniq = 0, grp = 0;
+    for (int l = 0; l < nlist; l++)
+        if (pc[(size_t)l]) { uniq += (double)h->h_len[(size_t)l]; grp += (double)h->h_len[(size_t)l] * ((pc[(size_t)l] + gq - 1) / gq); }
+    h->timing["scanned_unique_vectors"] += uniq; h->timing["scanned_group_vectors"] += grp; h->timing["scan_group_queries"] = (double)gq;
+    tm.mark("count");
+}
+// work-item records + run descriptors + survivor logs of the rotated-layout scan (items work items of ngq records); log_cap: keys per log
+static void* rot_scan_ws(rsx_index* h, int k, int64_t items, int ngq, int& log_cap) {
+    // the log pool = (persistent workgroups x 64 logs x log_cap keys): 1 / 2 / 4 GiB by k, never more than a quarter of the
+    // temp budget.  A log that fills up only sends the queries of its later runs to the exact re-run (counted); the pool is
+    // touched where survivors land, so its size costs nothing per batch; reported by rsx_get "workspace_bytes"
+    const int nwg = pq_scan_rot_max_wgs(h->M) * ngq;
+    int64_t pool = (int64_t)(k <= 64 ? 1 : k <= 512 ? 2 : 4) << 30;
+    pool = std::min(pool, std::max<int64_t>(h->temp_budget / 4, (int64_t)64 << 20));
+    int64_t cap = pool / 8 / ((int64_t)nwg * 64);
+    cap = std::max<int64_t>(64, cap / 16 * 16);
+    if (h->pq_log_cap > 0) cap = h->pq_log_cap;            // tests starve the logs to force the overflow path
+    log_cap = (int)std::min<int64_t>(cap, (int64_t)1 << 24);
+    h->w_itemdesc.ensure(pq_scan_rot_ws(items * ngq, log_cap, nwg));
+    return h->w_itemdesc.p;
+}
+// the 8-bit tables + per-query parameters; pg: the (query, probe) pairs grouped by list in the same launch (matrix-core form only)
+static void build_pq_tables(rsx_index* h, const BatchPlan& P, void* lut_ws, const PairGroupArgs* pg, StageTimer& tm) {
+    if (P.side_lut) HIPCHECK(hipStreamWaitEvent(h->st, h->ev_lut, 0));     // the tables were built beside the probe selection
+    launch_pq_lut8(P.pq_fused_lut ? nullptr : h->w_lut.as<float>(), h->w_q32.as<float>(), h->ld, h->d_codebooks.as<float>(), h->dsub, P.nq, h->M,
+                   h->Mpad, h->w_dis0.as<float>(), P.nprobe, h->w_lut8.as<uint8_t>(), h->w_qparam.p, lut_ws, P.sliced ? 2 : P.rot ? 1 : 0, h->st,
+                   P.side_lut ? 2 : 0, lut32_out(h, P), (lut_ws && !P.side_lut && h->lut_tiled >= 2) ? (P.lut_pass0_early ? 2 : 1) : 0, pg);
+    tm.mark("lut8");
+}
+// the fast scan's tiles and its threshold pre-pass: vectors per lane (vpl, tile_rows = 1024 vpl), the pre-pass sample and its form
+struct PqGeometry { int vpl, tile_rows, pre_vpl, pre_rows; bool fused_pre, pre4; };
+static PqGeometry pq_geometry(const rsx_index* h, const BatchPlan& P, bool filtered) {
+    const int nlist = h->nlist, k = P.k; const int64_t pairs = P.nq * P.nprobe;
+    PqGeometry g{};
+    int64_t avg_slabs = std::max<int64_t>(1, (h->ntotal / std::max(1, nlist) + 63) / 64);
+    // rotated layout: persistent workgroups draw items dynamically, so the tile is the whole (average) list — one table
+    // staging per (list, query group) — as long as that leaves a few thousand items to balance over 256 CUs
+    int vpl = 8;
+    if (P.rot) { vpl = 32; while (vpl > 8 && 16 * (vpl / 2) >= avg_slabs) vpl /= 2; }
+    if (h->scan_chunk > 0) vpl = std::max(1, std::min(P.rot ? 64 : 16, h->scan_chunk / 1024));
+    else {
+        // enough items to balance the chip: a few thousand for a full batch; for a handful of queries every (query, list)
+        // pair is its own group and each item stages a whole table, so one item per CU is the better trade
+        const int64_t groups_est = pairs <= nlist / 4 ? pairs : pairs / 4 + 1;
+        const int64_t want_items = pairs <= nlist / 4 ? 256 : 2048;
+        while (vpl > 1 && groups_est * ((avg_slabs + 16 * vpl - 1) / (16 * vpl)) < want_items) vpl /= 2;
+    }
+    if (vpl != 64 && vpl != 32 && vpl != 16 && vpl != 8 && vpl != 4 && vpl != 2) vpl = 1;
+    g.vpl = vpl; g.tile_rows = 64 * 16 * vpl;
+    // the pre-pass only has to produce a threshold: it scores a (smaller) prefix of the closest list
+    g.pre_vpl = vpl;
+    if (filtered && h->pq_pre_rows > 0) {
+        while (g.pre_vpl > 1 && 64 * 16 * g.pre_vpl > h->pq_pre_rows) g.pre_vpl /= 2;
+        while (g.pre_vpl > 1 && 64 * 16 * g.pre_vpl < P.KP * 4) g.pre_vpl *= 2;   // ... but well above K' candidates
+        if (g.pre_vpl > vpl) g.pre_vpl = vpl;
+    }
+    g.pre_rows = filtered ? 64 * 16 * g.pre_vpl : g.tile_rows;
+    // one-launch pre-pass (k_pq_prepass: score a prefix of the closest list with byte gathers on the query's own table,
+    // 16-bit integer sums in LDS, k-th largest by a radix walk -> threshold a_k - 2 eps) when its LDS footprint allows;
+    // else grouping + scan of the prefix + selection (K'-th key of the prefix as the threshold)
+    g.fused_pre = filtered && h->pq_prepass_fused != 0;
+    if (g.fused_pre) {
+        // the sample's k-th best score is the threshold: the sample must be a large part of the closest list once k is large
+        // (measured at 24k-vector lists: a 2048-vector prefix gives ~1000 candidates per query for k = 10 but ~20000 for
+        // k = 100) — 160 k vectors, at least pq_pre_rows, at most 32768 (64 KiB of 16-bit sums in LDS)
+        // (round 3, measured on the bench index at k = 10: 2048 / 4096 / 8192 / 16384 sample rows leave 1046 / 633 / 372 / 217
+        // candidates per query; the pre-pass costs 85 / 131 / 239 / 446 us and the scan 2.50 / 2.41 / 2.43 / 2.42 ms: 4096 is
+        // the best total for a full batch, a few queries keep the cheaper 2048)
+        int64_t base_rows = h->pq_pre_rows > 0 ? h->pq_pre_rows : 2048;
+        if (P.nq <= 64) base_rows = std::min<int64_t>(base_rows, 2048);
+        int64_t want_rows = std::max<int64_t>(base_rows, std::min<int64_t>(h->pq_pre_max, (int64_t)h->pq_pre_mult * k));
+        want_rows = std::min<int64_t>(round_up(want_rows, 64), round_up(std::max<int64_t>(P.maxlen, 64), 64));
+        // small k, full batch, rotated layout: the 4-queries-per-workgroup form (k_pq_prepass4) — its sample is what fits the LDS
+        // beside the four-query table image (3520 rows at M = 96)
+        g.pre4 = P.rot && h->pq_prepass4 != 0 && P.nq >= 64 && (int64_t)160 * k <= base_rows && pq_prepass4_max_rows(h->Mpad) >= 1024;
+        if (g.pre4) want_rows = std::min<int64_t>(want_rows, pq_prepass4_max_rows(h->Mpad));
+        g.pre_rows = (int)want_rows;
+        g.fused_pre = (size_t)g.pre_rows * 2 + (size_t)h->Mpad * 256 + 2048 <= 150 * 1024;
+        if (!g.fused_pre) g.pre_rows = 64 * 16 * g.pre_vpl;
+    }
+    return g;
+}
+// the one-launch threshold pre-pass behind the table build (and the pair grouping where it rides along); the two-call search parks
+// behind it.  Returns whether the pairs are grouped already
+static bool pq_prepass(rsx_index* h, const BatchPlan& P, BatchResult& R, const PairArea& pr, const PqGeometry& g, void* lut_ws, StageTimer& tm) {
+    const int64_t nq = P.nq; const int nlist = h->nlist;
+    R.cand_cap = alloc_cand_rows(h, P, h->M);
+    PQPrepassArgs pa{};
+    pa.codes = h->data.as<uint8_t>(); pa.list_base = h->d_base.as<int64_t>(); pa.list_len = h->d_len.as<int64_t>();
+    pa.probe_list = h->w_probelist.as<int32_t>(); pa.probe_dis0 = h->w_dis0.as<float>(); pa.seg_start = h->w_segstart.as<int64_t>();
+    pa.lut8 = h->w_lut8.as<uint8_t>(); pa.qparam = h->w_qparam.as<float>();
+    pa.nprobe = P.nprobe; pa.Mpad = h->Mpad; pa.pre_rows = g.pre_rows; pa.KP = P.KP; pa.CB = h->CB; pa.k = P.k;
+    pa.state = h->w_state.as<uint64_t>(); pa.cand_cnt = h->w_candcnt.as<unsigned long long>();
+    h->w_tau.ensure((size_t)nq * 8); pa.tau = h->w_tau.as<uint64_t>();
+    if (P.rot) {       // the sample's own candidates leave from the pre-pass; the scan drops that (query, list, tile 0)
+        h->w_excl.ensure((size_t)nq * 2);
+        pa.cand = h->w_cand.as<uint64_t>(); pa.cand_cap = R.cand_cap; pa.tile_rows = g.tile_rows; pa.excl = h->w_excl.as<uint16_t>();
+    }
+    const bool group_in_tables = lut_ws && !P.side_lut && h->lut_tiled >= 2 && h->pq_group_fused != 0 && pr.npairs <= PG_MAX_PAIRS &&
+                                 nlist <= PG_BLOCKS * PG_MAX_LPB;
+    PairGroupArgs pg{};
+    bool grouped = false;
+    if (group_in_tables) {      // the pairs grouped by list by extra workgroups of the table launch
+        if (!h->w_pgflags.p) { h->w_pgflags.ensure((size_t)PG_BLOCKS * 16); HIPCHECK(hipMemsetAsync(h->w_pgflags.p, 0, (size_t)PG_BLOCKS * 16, h->st)); }
+        pg.probe_list = h->w_probelist.as<int32_t>(); pg.list_len = h->d_len.as<int64_t>();
+        pg.pair_off = pr.pair_off; pg.group_off = pr.group_off; pg.item_off = pr.item_off; pg.total_groups = pr.total_groups; pg.total_items = pr.total_items;
+        pg.pairs_sorted = pr.pairs_sorted; pg.flags = h->w_pgflags.as<uint32_t>();
+        pg.npairs = (int)pr.npairs; pg.nlist = nlist; pg.G = 4 * P.ngq; pg.tile_rows = g.tile_rows; pg.tile_cap = 0; pg.nb = PG_BLOCKS;
+        if (++h->pg_epoch == 0) h->pg_epoch = 1;
+        pg.epoch = h->pg_epoch;
+        grouped = true;
+    }
+    build_pq_tables(h, P, lut_ws, group_in_tables ? &pg : nullptr, tm);
+    if (P.side_lut) {       // the (list, tile, group) work items of the scan: built beside the pre-pass (they need the probes only)
+        HIPCHECK(hipStreamWaitEvent(h->st2, h->ev_probe, 0));
+        pr.group(h, 4 * P.ngq, g.tile_rows, P.nprobe, 0, h->st2);
+        HIPCHECK(hipEventRecord(h->ev_group, h->st2));
+        grouped = true;
+    }
+    // large k: the histogram form of the four-query pre-pass (any sample size, several lists; pq_prepass4 = 2 keeps k_pq_prepass)
+    const bool pre4big = P.rot && !g.pre4 && h->pq_prepass4 == 1 && nq >= 64 && h->Mpad >= 32 && g.pre_rows <= 32768;
+    if (!(g.pre4 && launch_pq_prepass4(pa, nq, h->st) == 0) && !(pre4big && launch_pq_prepass4_big(pa, nq, h->st) == 0))
+        launch_pq_prepass(pa, nq, h->st);
+    R.fused_pre_used = true;
+    if (h->tc && h->tc->active && P.allow_fast && std::this_thread::get_id() == h->tc->worker) {
+        // two-call search: the thresholds are final on the device; hand them to the caller and wait for rsx_search_scan
         HIPCHECK(hipStreamSynchronize(h->st));
-        double tot = 0;
-        std::vector<int32_t> pc((size_t)nlist, 0);
-        for (int32_t l : pl) if (l >= 0) { tot += (double)h->h_len[(size_t)l]; pc[(size_t)l]++; }
-        h->timing["scanned_vectors"] += tot;
-        // the same batch seen list-major: vectors of every list probed at least once (what HBM must deliver), and vectors x
-        // groups of 4 probing queries (what the IVF-PQ fast scan gathers)
-        // (queries per table gather of the scan this index takes: 8 for the sliced layout and the M = 64 eight-query form, 16 at M = 16, else 4)
-        const bool sl8_ = sliced && (h->pq_q8 == 2 || (h->pq_q8 != 0 && nq * (int64_t)nprobe >= (int64_t)3 * nlist && h->ntotal >= (int64_t)4096 * nlist));
-        const int gq = h->kind == KIND_IVFPQ && pq_rot_family(h->CB) ? (sliced ? (sl8_ ? 8 : 4) : 4 * pq_scan_rot_ngq(h->M, true, h->pq_q8)) : 4;
-        double uniq = 0, grp = 0;
-        for (int l = 0; l < nlist; l++)
-            if (pc[(size_t)l]) { uniq += (double)h->h_len[(size_t)l]; grp += (double)h->h_len[(size_t)l] * ((pc[(size_t)l] + gq - 1) / gq); }
-        h->timing["scanned_unique_vectors"] += uniq; h->timing["scanned_group_vectors"] += grp; h->timing["scan_group_queries"] = (double)gq;
-        tm.mark("count");
+        rsx_index::TwoCall& t = *h->tc; std::unique_lock<std::mutex> lk(t.mu);
+        t.tau = h->w_tau.as<uint64_t>(); t.ntau = nq; t.parked = true;
+        t.cv.notify_all();
+        t.cv.wait(lk, [&] { return t.go; });
+        t.parked = false; t.tau = nullptr; t.ntau = 0;
     }
-    // host-side bound on a query's row of the score buffer: the nprobe longest (padded) lists
-    const auto padded = top_probe_sum(h, nprobe, pad_to, pad_to);    // the nprobe longest lists, padded: sum and maximum
-    int64_t tmax = padded.first, maxlen = padded.second;
-    tmax = std::max<int64_t>(round_up(tmax, 256), 256);
-    // score rows [nq, tmax]: every path but the filtered IVF-PQ fast scan with the one-launch pre-pass fills (part of) them.  At the
-    // reference's nprobe 512 a row is 35 MB: allocating it unconditionally used to cut a 1024-query batch into four internal
-    // batches (round 4: 4x the fixed stages, a quarter of the queries per list group)
-    if (allow_fast ? pq_search_needs_score_rows(h, nprobe, k) : true) h->w_temp.ensure((size_t)nq * tmax * 4);
-    bool filtered = false;   // fast path with in-kernel candidate filtering (no full score buffer)
-    bool flag_overflows = false;   // IVF-Flat filtered scan: a few candidate rows overflowed — k_finalize sends their queries to the exact re-run
-    bool use_gather = false; int gs_tmax = 0; PQGatherArgs gs{};   // ... whose candidates are gathered and selected in one launch
-    bool fused_pre_used = false;   // ... whose threshold came from the one-launch pre-pass (complete candidate rows: second chance)
-    int cand_cap = 0;
-    // the exact kernels gather fp32 table entries; the fast path builds the table in LDS (when it fits)
-    const bool fused_lut = pq_fused_lut;
-
-    if (h->kind == KIND_IVFPQ) {
-        const bool pq_l2 = h->metric == RSX_METRIC_L2;      // per-(query, list) tables, built inside the scan (k_pq_scan_l2)
-        if (!fused_lut && !pq_l2) {
-            h->w_lut.ensure((size_t)nq * h->Mpad * 256 * 4);
-            launch_pq_lut(h->w_q32.as<float>(), ld, nq, d, h->M, h->Mpad, h->d_codebooks.as<float>(), h->w_lut.as<float>(), h->st);
-            tm.mark("lut");
-        }
-        PQScanArgs a{};
-        a.codes = h->data.as<uint8_t>(); a.M = h->M; a.Mpad = h->Mpad; a.CB = h->CB;
-        a.list_base = h->d_base.as<int64_t>(); a.list_len = h->d_len.as<int64_t>();
-        a.lut = h->w_lut.as<float>(); a.probe_list = h->w_probelist.as<int32_t>(); a.probe_dis0 = h->w_dis0.as<float>();
-        a.seg_start = h->w_segstart.as<int64_t>(); a.nq = nq; a.nprobe = nprobe;
-        a.temp = h->w_temp.as<float>(); a.tstride = tmax;
-        int64_t max_slabs = std::max<int64_t>(1, maxlen / 64);
-        int64_t pairs = nq * nprobe;
-        bool done = false;
-        if (fast) {
-            // 8-bit tables, 4 queries per LDS read; approximate scores, certified in k_finalize
-            h->w_lut8.ensure((size_t)nq * h->Mpad * 256);
-            h->w_qparam.ensure((size_t)nq * 16);
-            h->w_uncertain.ensure((size_t)nq * 8);
-            void* lut_ws = nullptr;
-            if (fused_lut && h->dsub == 8 && h->lut_tiled != 0) { h->w_lutws.ensure(pq_lut8_tiled_ws(nq, h->Mpad)); lut_ws = h->w_lutws.p; }
-            // the 8-bit tables + per-query parameters; pg: the (query, probe) pairs grouped by list in the same launches (matrix-core form only).
-            // Called once the scan's tile size is known (the grouping needs it)
-            bool tables_built = false;
-            auto build_tables = [&](const PairGroupArgs* pg) {
-                if (tables_built) return;
-                tables_built = true;
-                if (side_lut) HIPCHECK(hipStreamWaitEvent(h->st, h->ev_lut, 0));     // the tables were built beside the probe selection
-                launch_pq_lut8(fused_lut ? nullptr : h->w_lut.as<float>(), h->w_q32.as<float>(), ld, h->d_codebooks.as<float>(), h->dsub, nq, h->M, h->Mpad,
-                               h->w_dis0.as<float>(), nprobe, h->w_lut8.as<uint8_t>(), h->w_qparam.p, lut_ws, sliced ? 2 : rot ? 1 : 0, h->st, side_lut ? 2 : 0,
-                               fused_lut ? lut32_out : nullptr, (lut_ws && !side_lut && h->lut_tiled >= 2) ? (lut_pass0_early ? 2 : 1) : 0, pg);
-                tm.mark("lut8");
-            };
-            const bool group_in_tables = lut_ws && !side_lut && h->lut_tiled >= 2 && h->pq_group_fused != 0 && pairs <= PG_MAX_PAIRS &&
-                                         nlist <= PG_BLOCKS * PG_MAX_LPB;
-            int rot_log_cap = 64;
-            auto rot_desc = [&](int64_t items, int ngq) -> void* {   // work-item records + run descriptors + survivor logs of the rotated-layout scan
-                // the log pool = (persistent workgroups x 64 logs x log_cap keys): 1 / 2 / 4 GiB by k, never more than a quarter of the
-                // temp budget.  A log that fills up only sends the queries of its later runs to the exact re-run (counted); the pool is
-                // touched where survivors land, so its size costs nothing per batch; reported by rsx_get "workspace_bytes"
-                const int nwg = pq_scan_rot_max_wgs(h->M) * ngq;
-                int64_t pool = (int64_t)(k <= 64 ? 1 : k <= 512 ? 2 : 4) << 30;
-                pool = std::min(pool, std::max<int64_t>(h->temp_budget / 4, (int64_t)64 << 20));
-                int64_t cap = pool / 8 / ((int64_t)nwg * 64);
-                cap = std::max<int64_t>(64, cap / 16 * 16);
-                if (h->pq_log_cap > 0) cap = h->pq_log_cap;            // tests starve the logs to force the overflow path
-                rot_log_cap = (int)std::min<int64_t>(cap, (int64_t)1 << 24);
-                h->w_itemdesc.ensure(pq_scan_rot_ws(items * ngq, rot_log_cap, nwg));
-                return h->w_itemdesc.p;
-            };
-            // sliced layout: eight queries per gather (two records per item) where lists are long and shared by several queries; a handful of
-            // queries (about one per probed list) or short lists take the four-query single-pass scan (k_pq_scan_sl4).  pq_q8: 1 = choose,
-            // 2 = always eight, 0 = always four
-            const bool sl_eight = sliced && (h->pq_q8 == 2 || (h->pq_q8 != 0 && pairs >= (int64_t)3 * nlist && h->ntotal >= (int64_t)4096 * nlist));
-            const int ngq = sliced ? (sl_eight ? 2 : 1) : rot ? pq_scan_rot_ngq(h->M, true, h->pq_q8) : 1;     // the filtered scan's 4-query records per work item (M = 16: 4)
-            int64_t avg_slabs = std::max<int64_t>(1, (h->ntotal / std::max(1, nlist) + 63) / 64);
-            // rotated layout: persistent workgroups draw items dynamically, so the tile is the whole (average) list — one table
-            // staging per (list, query group) — as long as that leaves a few thousand items to balance over 256 CUs
-            int vpl = 8;
-            if (rot) { vpl = 32; while (vpl > 8 && 16 * (vpl / 2) >= avg_slabs) vpl /= 2; }
-            if (h->scan_chunk > 0) vpl = std::max(1, std::min(rot ? 64 : 16, h->scan_chunk / 1024));
-            else {
-                // enough items to balance the chip: a few thousand for a full batch; for a handful of queries every (query, list)
-                // pair is its own group and each item stages a whole table, so one item per CU is the better trade
-                const int64_t groups_est = pairs <= nlist / 4 ? pairs : pairs / 4 + 1;
-                const int64_t want_items = pairs <= nlist / 4 ? 256 : 2048;
-                while (vpl > 1 && groups_est * ((avg_slabs + 16 * vpl - 1) / (16 * vpl)) < want_items) vpl /= 2;
-            }
-            if (vpl != 64 && vpl != 32 && vpl != 16 && vpl != 8 && vpl != 4 && vpl != 2) vpl = 1;
-            const int tile_rows = 64 * 16 * vpl;
-            h->w_pairs.ensure((size_t)(pairs + 5 * (size_t)(nlist + 1) + 8) * 4);
-            int32_t* pairs_sorted = h->w_pairs.as<int32_t>();
-            int32_t* cnt = pairs_sorted + pairs;
-            int32_t* cursor = cnt + (nlist + 1);
-            int32_t* pair_off = cursor + (nlist + 1);
-            int32_t* group_off = pair_off + (nlist + 1);
-            int32_t* item_off = group_off + (nlist + 1);
-            int32_t* total_groups = item_off + (nlist + 1);
-            int32_t* total_items = total_groups + 1;
-            // Two stages, so that only a sliver of the scores ever leaves the scan kernel:
-            //  stage 1: score ONLY the first tile of each query's closest list (probe rank 0) into the score
-            //           buffer and take its top-K' -> state0; its K'-th key is a lower bound of the query's final
-            //           K'-th best key;
-            //  stage 2: scan everything else (all probes, all tiles, minus that piece) in the multi-query groups,
-            //           appending to a small per-query candidate buffer only the keys that beat the bound
-            //           (wave-aggregated atomics); a final select merges them with state0.
-            // A full candidate buffer marks the query uncertain (-> exact fallback), so this is always exact.
-            filtered = (nprobe > 1) && (h->pq_filter != 0);
-            // the pre-pass only has to produce a threshold: it scores a (smaller) prefix of the closest list
-            int pre_vpl = vpl;
-            if (filtered && h->pq_pre_rows > 0) {
-                while (pre_vpl > 1 && 64 * 16 * pre_vpl > h->pq_pre_rows) pre_vpl /= 2;
-                while (pre_vpl > 1 && 64 * 16 * pre_vpl < KP * 4) pre_vpl *= 2;   // ... but well above K' candidates
-                if (pre_vpl > vpl) pre_vpl = vpl;
-            }
-            int pre_rows = filtered ? 64 * 16 * pre_vpl : tile_rows;
-            // one-launch pre-pass (k_pq_prepass: score a prefix of the closest list with byte gathers on the query's own table,
-            // 16-bit integer sums in LDS, k-th largest by a radix walk -> threshold a_k - 2 eps) when its LDS footprint allows;
-            // else grouping + scan of the prefix + selection (K'-th key of the prefix as the threshold)
-            bool fused_pre = filtered && h->pq_prepass_fused != 0;
-            bool pre4 = false;
-            bool grouped_early = false;
-            if (fused_pre) {
-                // the sample's k-th best score is the threshold: the sample must be a large part of the closest list once k is large
-                // (measured at 24k-vector lists: a 2048-vector prefix gives ~1000 candidates per query for k = 10 but ~20000 for
-                // k = 100) — 160 k vectors, at least pq_pre_rows, at most 32768 (64 KiB of 16-bit sums in LDS)
-                // (round 3, measured on the bench index at k = 10: 2048 / 4096 / 8192 / 16384 sample rows leave 1046 / 633 / 372 / 217
-                // candidates per query; the pre-pass costs 85 / 131 / 239 / 446 us and the scan 2.50 / 2.41 / 2.43 / 2.42 ms: 4096 is
-                // the best total for a full batch, a few queries keep the cheaper 2048)
-                int64_t base_rows = h->pq_pre_rows > 0 ? h->pq_pre_rows : 2048;
-                if (nq <= 64) base_rows = std::min<int64_t>(base_rows, 2048);
-                int64_t want_rows = std::max<int64_t>(base_rows, std::min<int64_t>(h->pq_pre_max, (int64_t)h->pq_pre_mult * k));
-                want_rows = std::min<int64_t>(round_up(want_rows, 64), round_up(std::max<int64_t>(maxlen, 64), 64));
-                // small k, full batch, rotated layout: the 4-queries-per-workgroup form (k_pq_prepass4) — its sample is what fits the LDS
-                // beside the four-query table image (3520 rows at M = 96)
-                pre4 = rot && h->pq_prepass4 != 0 && nq >= 64 && (int64_t)160 * k <= base_rows && pq_prepass4_max_rows(h->Mpad) >= 1024;
-                if (pre4) want_rows = std::min<int64_t>(want_rows, pq_prepass4_max_rows(h->Mpad));
-                pre_rows = (int)want_rows;
-                fused_pre = (size_t)pre_rows * 2 + (size_t)h->Mpad * 256 + 2048 <= 150 * 1024;
-                if (!fused_pre) pre_rows = 64 * 16 * pre_vpl;
-            }
-            if (fused_pre) {
-                cand_cap = (int)std::min<int64_t>(std::max<int64_t>(tmax, 1024), pq_cand_cap(k, h->M));
-                h->w_cand.ensure((size_t)nq * cand_cap * 8);
-                h->w_candcnt.ensure((size_t)nq * 8 * CCS);
-                PQPrepassArgs pa{};
-                pa.codes = h->data.as<uint8_t>(); pa.list_base = h->d_base.as<int64_t>(); pa.list_len = h->d_len.as<int64_t>();
-                pa.probe_list = h->w_probelist.as<int32_t>(); pa.probe_dis0 = h->w_dis0.as<float>();
-                pa.seg_start = h->w_segstart.as<int64_t>();
-                pa.lut8 = h->w_lut8.as<uint8_t>(); pa.qparam = h->w_qparam.as<float>();
-                pa.nprobe = nprobe; pa.Mpad = h->Mpad; pa.pre_rows = pre_rows; pa.KP = KP; pa.CB = h->CB;
-                pa.k = k;
-                pa.state = state; pa.cand_cnt = h->w_candcnt.as<unsigned long long>();
-                h->w_tau.ensure((size_t)nq * 8);
-                pa.tau = h->w_tau.as<uint64_t>();
-                if (rot) {       // the sample's own candidates leave from the pre-pass; the scan drops that (query, list, tile 0)
-                    h->w_excl.ensure((size_t)nq * 2);
-                    pa.cand = h->w_cand.as<uint64_t>(); pa.cand_cap = cand_cap; pa.tile_rows = tile_rows; pa.excl = h->w_excl.as<uint16_t>();
-                }
-                if (group_in_tables) {      // the pairs grouped by list by extra workgroups of the table launch
-                    if (!h->w_pgflags.p) { h->w_pgflags.ensure((size_t)PG_BLOCKS * 16); HIPCHECK(hipMemsetAsync(h->w_pgflags.p, 0, (size_t)PG_BLOCKS * 16, h->st)); }
-                    PairGroupArgs pg{};
-                    pg.probe_list = h->w_probelist.as<int32_t>(); pg.list_len = h->d_len.as<int64_t>();
-                    pg.pair_off = pair_off; pg.group_off = group_off; pg.item_off = item_off; pg.total_groups = total_groups; pg.total_items = total_items;
-                    pg.pairs_sorted = pairs_sorted; pg.flags = h->w_pgflags.as<uint32_t>();
-                    pg.npairs = (int)pairs; pg.nlist = nlist; pg.G = 4 * ngq; pg.tile_rows = tile_rows; pg.tile_cap = 0; pg.nb = PG_BLOCKS;
-                    if (++h->pg_epoch == 0) h->pg_epoch = 1;
-                    pg.epoch = h->pg_epoch;
-                    build_tables(&pg);
-                    grouped_early = true;
-                }
-                build_tables(nullptr);
-                if (side_lut) {       // the (list, tile, group) work items of the scan: built beside the pre-pass (they need the probes only)
-                    HIPCHECK(hipStreamWaitEvent(h->st2, h->ev_probe, 0));
-                    launch_group_pairs(h->w_probelist.as<int32_t>(), pairs, nlist, 4 * ngq, cnt, cursor, pair_off, group_off, total_groups,
-                                       pairs_sorted, h->d_len.as<int64_t>(), tile_rows, item_off, total_items, nprobe, 0, nprobe, 0,
-                                       h->st2);
-                    HIPCHECK(hipEventRecord(h->ev_group, h->st2));
-                    grouped_early = true;
-                }
-                // large k: the histogram form of the four-query pre-pass (any sample size, several lists; pq_prepass4 = 2 keeps k_pq_prepass)
-                const bool pre4big = rot && !pre4 && h->pq_prepass4 == 1 && nq >= 64 && h->Mpad >= 32 && pre_rows <= 32768;
-                if (!(pre4 && launch_pq_prepass4(pa, nq, h->st) == 0) && !(pre4big && launch_pq_prepass4_big(pa, nq, h->st) == 0))
-                    launch_pq_prepass(pa, nq, h->st);
-                fused_pre_used = true;
-                done = true;
-                if (h->tc && h->tc->active && allow_fast && std::this_thread::get_id() == h->tc->worker) {
-                    // two-call search: the thresholds are final on the device; hand them to the caller and wait for rsx_search_scan
-                    HIPCHECK(hipStreamSynchronize(h->st));
-                    rsx_index::TwoCall& t = *h->tc;
-                    std::unique_lock<std::mutex> lk(t.mu);
-                    t.tau = h->w_tau.as<uint64_t>(); t.ntau = nq; t.parked = true;
-                    t.cv.notify_all();
-                    t.cv.wait(lk, [&] { return t.go; });
-                    t.parked = false; t.tau = nullptr; t.ntau = 0;
-                }
-            } else {
-                build_tables(nullptr);
-                h->w_temp.ensure((size_t)nq * tmax * 4);       // this form scores a prefix / everything into the score rows
-                a.temp = h->w_temp.as<float>();
-                launch_group_pairs(h->w_probelist.as<int32_t>(), pairs, nlist, 4, cnt, cursor, pair_off, group_off, total_groups,
-                                   pairs_sorted, h->d_len.as<int64_t>(), pre_rows, item_off, total_items, nprobe, 0,
-                                   filtered ? 1 : nprobe, filtered ? 1 : 0, h->st);
-                tm.mark("group");
-                const int64_t mi = filtered ? (nq + nlist + 8) : max_scan_items(h, nq, nprobe, 4, tile_rows);
-                void* rws0 = rot ? rot_desc(mi, 1) : nullptr;
-                done = (rot ? launch_pq_scan_rot(a, h->w_lut8.as<uint8_t>(), h->w_qparam.p, pairs_sorted, pair_off, group_off,
-                                                 total_groups, item_off, total_items, nlist, mi, filtered ? pre_vpl : vpl,
-                                                 nullptr, 0, nullptr, nullptr, 0, rws0, rot_log_cap, 0, 0, nullptr, nullptr, 0, h->st)
-                            : launch_pq_scan8(a, h->w_lut8.as<uint8_t>(), h->w_qparam.p, pairs_sorted, pair_off, group_off,
-                                              total_groups, item_off, total_items, nlist, mi, filtered ? pre_vpl : vpl, h->st)) == 0;
-            }
-            if (done && filtered) {
-                tm.mark("scan0");
-                cand_cap = (int)std::min<int64_t>(std::max<int64_t>(tmax, 1024), pq_cand_cap(k, h->M));
-                h->w_cand.ensure((size_t)nq * cand_cap * 8);
-                h->w_candcnt.ensure((size_t)nq * 8 * CCS);
-                // multi-launch form: top-K' of the scored prefix of the closest list, row prefix
-                // [0, min(seg_start[q][1], pre_rows)), written as the threshold key + counter reset
-                if (!fused_pre)
-                    select_rows(h, h->w_temp.as<float>(), tmax, h->w_segstart.as<int64_t>() + 1, nprobe + 1,
-                                std::min<int64_t>(maxlen, pre_rows), 0, nq, KP, BUF, KP, state, false,
-                                h->w_candcnt.as<unsigned long long>());
-                // The pre-pass is only a threshold: keep its K'-th key and let the main scan score EVERYTHING (the
-                // prefix included), so the scan kernel carries no per-slab "already scored" test and no key can
-                // arrive twice (the prefix keys above the threshold come back through the candidate buffer).
-                // (the selection wrote only the K'-th key of each query and reset the query's candidate counter)
-                // (a stage mark is an event record: ~5 us of stream time in profile mode — none for a stage that launched nothing)
-                if (!fused_pre) tm.mark("select0");
-                if (grouped_early) { if (side_lut) HIPCHECK(hipStreamWaitEvent(h->st, h->ev_group, 0)); }
-                else launch_group_pairs(h->w_probelist.as<int32_t>(), pairs, nlist, 4 * ngq, cnt, cursor, pair_off, group_off, total_groups,
-                                        pairs_sorted, h->d_len.as<int64_t>(), tile_rows, item_off, total_items, nprobe, 0, nprobe, 0,
-                                        h->st);
-                if (!(grouped_early && !side_lut)) tm.mark("group");
-                const int64_t mi_main = max_scan_items(h, nq, nprobe, 4 * ngq, tile_rows);
-                void* rws1 = rot ? rot_desc(mi_main, ngq) : nullptr;
-                // threshold keys: one per query from the one-launch pre-pass, else the K'-th key the selection left in the state rows
-                const uint64_t* tau_ptr = fused_pre ? h->w_tau.as<uint64_t>() : state + (KP - 1);
-                const int64_t tau_stride = fused_pre ? 1 : KP;
-                // candidate gather + selection in one launch when the (probe rank, tile) table of a query is small (rsx_internal.h)
-                gs_tmax = (int)((maxlen + tile_rows - 1) / tile_rows);
-                use_gather = rot && h->pq_gather != 0 && pq_gather_select_applies(nprobe, gs_tmax, KP);
-                if (rot && h->pq_gather != 0 && !use_gather) h->timing["pq_gather_declined"] += 1;
-                if (use_gather) {
-                    h->w_qitems.ensure((size_t)nq * nprobe * gs_tmax * 4);
-                    gs.probe_list = h->w_probelist.as<int32_t>(); gs.list_len = h->d_len.as<int64_t>(); gs.nprobe = nprobe;
-                    gs.tile_rows = tile_rows; gs.tmax = gs_tmax; gs.qitems = h->w_qitems.as<int32_t>();
-                    gs.seg_desc = pq_scan_rot_ws_desc(rws1, mi_main * ngq); gs.log_keys = pq_scan_rot_ws_keys(rws1, mi_main * ngq);
-                    gs.cand = h->w_cand.as<uint64_t>(); gs.cand_cnt = h->w_candcnt.as<unsigned long long>(); gs.cand_cap = cand_cap;
-                    gs.state = state; gs.KP = KP;
-                }
-                tm.pre_scan();
-                done = (rot ? launch_pq_scan_rot(a, h->w_lut8.as<uint8_t>(), h->w_qparam.p, pairs_sorted, pair_off, group_off,
-                                                 total_groups, item_off, total_items, nlist,
-                                                 mi_main, vpl, tau_ptr, tau_stride,
-                                                 h->w_cand.as<uint64_t>(), h->w_candcnt.as<unsigned long long>(), cand_cap,
-                                                 rws1, rot_log_cap, h->pq_prune, (h->pq_pace & 0xffff), (fused_pre && rot) ? h->w_excl.as<uint16_t>() : nullptr,
-                                                 use_gather ? h->w_qitems.as<int32_t>() : nullptr, gs_tmax, h->st, sliced ? (sl_eight ? 1 : 0) : h->pq_q8)
-                            : launch_pq_scan8_filter(a, h->w_lut8.as<uint8_t>(), h->w_qparam.p, pairs_sorted, pair_off, group_off,
-                                                     total_groups, item_off, total_items, nlist,
-                                                     max_scan_items(h, nq, nprobe, 4, tile_rows), vpl, tau_ptr, tau_stride,
-                                                     h->w_cand.as<uint64_t>(), h->w_candcnt.as<unsigned long long>(), cand_cap,
-                                                     h->st)) == 0;
-            }
-            if (!done) RSX_THROW(RSX_ERR_UNSUPPORTED, "IVFPQ fast scan: no kernel for M=%d", h->M);
-        }
-        if (!done && h->scan_kernel != 1 && h->CB == 16 && !pq_l2) {
-            // v2: list-major, two queries per LDS read
-            int64_t avg_slabs = std::max<int64_t>(1, (h->ntotal / std::max(1, nlist) + 63) / 64);
-            int vpl = 8;
-            if (h->scan_chunk > 0) vpl = std::max(1, std::min(8, h->scan_chunk / 1024));
-            else while (vpl > 1 && (pairs / 2 + 1) * ((avg_slabs + 16 * vpl - 1) / (16 * vpl)) < 2048) vpl /= 2;
-            if (vpl != 8 && vpl != 4 && vpl != 2) vpl = 1;
-            const int tile_rows = 64 * 16 * vpl;
-            h->w_pairs.ensure((size_t)(pairs + 5 * (size_t)(nlist + 1) + 8) * 4);
-            int32_t* pairs_sorted = h->w_pairs.as<int32_t>();
-            int32_t* cnt = pairs_sorted + pairs;
-            int32_t* cursor = cnt + (nlist + 1);
-            int32_t* pair_off = cursor + (nlist + 1);
-            int32_t* group_off = pair_off + (nlist + 1);
-            int32_t* item_off = group_off + (nlist + 1);
-            int32_t* total_groups = item_off + (nlist + 1);
-            int32_t* total_items = total_groups + 1;
-            launch_group_pairs(h->w_probelist.as<int32_t>(), pairs, nlist, 2, cnt, cursor, pair_off, group_off, total_groups,
-                               pairs_sorted, h->d_len.as<int64_t>(), tile_rows, item_off, total_items, nprobe, 0, nprobe, 0, h->st);
-            tm.mark("group");
-            done = launch_pq_scan2(a, pairs_sorted, pair_off, group_off, total_groups, item_off, total_items, nlist,
-                                   max_scan_items(h, nq, nprobe, 2, tile_rows), vpl, h->st) == 0;
-        }
-        if (!done) {
-            int64_t spc;
-            if (h->scan_chunk > 0) spc = std::max<int64_t>(16, h->scan_chunk / 64);
-            else {
-                // enough work items to fill 256 CUs several times over, but no smaller than 32 slabs
-                int64_t want_items = 4096;
-                int64_t chunks = std::max<int64_t>(1, (want_items + pairs - 1) / pairs);
-                spc = std::max<int64_t>(32, (max_slabs + chunks - 1) / chunks);
-            }
-            a.slabs_per_chunk = (int)spc;
-            a.max_chunks = (int)((max_slabs + spc - 1) / spc);
-            if ((pq_l2 ? launch_pq_scan_l2(a, h->w_q32.as<float>(), ld, h->d_centroids.as<float>(), h->d_codebooks.as<float>(), d, h->dsub, h->st)
-                       : rot ? launch_pq_scan_rot_exact(a, h->st) : launch_pq_scan(a, h->st)) != 0)
-                RSX_THROW(RSX_ERR_UNSUPPORTED, "IVFPQ scan: no kernel for M=%d", h->M);
-        }
-        h->timing[allow_fast ? "scan_launches" : "fb_scan_launches"] += 1;
-        tm.mark("scan");
-    } else if (!allow_fast) {
-        // exact mode (see the Flat branch): fp64 scores of every row of the probed lists into the score rows
-        ExactScoreArgs ea{};
-        ea.kind = KIND_IVFFLAT; ea.metric = h->metric; ea.nq = nq; ea.Q32 = h->w_q32.as<float>(); ea.ldq = ld; ea.d = d;
-        ea.X = h->data.p; ea.x_f16 = h->storage_f16; ea.ld = ld;
-        ea.probe_list = h->w_probelist.as<int32_t>(); ea.seg_start = h->w_segstart.as<int64_t>(); ea.nprobe = nprobe;
-        ea.list_base = h->d_base.as<int64_t>(); ea.list_len = h->d_len.as<int64_t>();
-        ea.temp = h->w_temp.as<float>(); ea.tstride = tmax;
-        launch_exact_scores(ea, h->st);
-        tm.mark("scan");
-    } else {
-        // group (query, probe) pairs by list, then list-major MFMA scan
-        int64_t npairs = nq * nprobe;
-        h->w_pairs.ensure((size_t)(npairs + 5 * (size_t)(nlist + 1) + 8) * 4);
-        int32_t* pairs_sorted = h->w_pairs.as<int32_t>();
-        int32_t* cnt = pairs_sorted + npairs;
-        int32_t* cursor = cnt + (nlist + 1);
-        int32_t* pair_off = cursor + (nlist + 1);
-        int32_t* group_off = pair_off + (nlist + 1);
-        int32_t* item_off = group_off + (nlist + 1);
-        int32_t* total_groups = item_off + (nlist + 1);
-        int32_t* total_items = total_groups + 1;
-        // probing queries per group of the LDS-DMA list scans.  A group passes over its list's rows once, so the larger the group the fewer
-        // passes: 16 (k_list_scan2<_, 1>: two workgroups per CU), 64 (the 8-wave form, queries in LDS) or 128 (k_list_scan3, queries in
-        // registers: d = 384 / 512 / 768 / 1024).  Round 5, 20M x 768, inner product, batch 1024 (profiles/r05_ivfflat_wide.md): at 8 probing queries per
-        // list on average 16 wins (5.47 ms against 5.59 with 64), at 16 already 64 does (nlist 2048 / nprobe 32: 5.08 against 5.95;
-        // nlist 4096 / nprobe 64: 6.93 against 8.53), at 32 64 beats 128 (5.20 against 5.61: no list needs a second pass yet, and the
-        // 8-wave form has no barrier), at 64 and more 128 wins (6.04 against 7.23; nlist 1024 / nprobe 128: 10.6 against 11.4).  The
-        // 32-query form lost everywhere and is only reachable through the parameter.
-        int ls_qt = 1;
-        if (h->scan_chunk <= 0 && h->ivf_qtiles != 0 && list_scan2_chunk_rows(h->storage_f16, ld) > 0) {
-            const int64_t qpl = npairs / std::max(1, nlist);
-            const bool ls3 = list_scan3_applies(h->storage_f16, ld, h->metric == RSX_METRIC_L2) != 0;      // 128 queries per group, held in registers (k_list_scan3)
-            ls_qt = h->ivf_qtiles > 1 ? h->ivf_qtiles : (qpl >= 48 && ls3 ? 8 : qpl >= 12 ? 4 : 1);
-            if (ls_qt == 8 && !ls3) ls_qt = 4;
-            if (ls_qt != 8) ls_qt = std::min(ls_qt == 3 ? 2 : ls_qt, list_scan2_max_qtiles(ld));
-            if (ls_qt != 2 && ls_qt != 4 && ls_qt != 8) ls_qt = 1;
-        }
-        // (list, chunk, group) work items in list-major order for the LDS-DMA scan's XCD-aware 1-D grid (round 4): the groups of a
-        // list chunk run on one XCD at the same moment and its rows cross HBM once — at nlist 2048 / nprobe 128 half of the lists
-        // are probed by more than 64 queries, i.e. by two groups, which used to land on different XCDs (two fetches)
-        const int ls2_rows = list_scan2_chunk_rows(h->storage_f16, ld);
-        const bool ls_wide = ls_qt >= 4;     // the 8-wave forms: 1024 rows per work item
-        const int item_rows = (h->scan_chunk <= 0 && ls2_rows > 0) ? (ls_wide ? 2 * ls2_rows : ls2_rows) : 0;
-        launch_group_pairs(h->w_probelist.as<int32_t>(), npairs, nlist, 16 * ls_qt, cnt, cursor, pair_off, group_off, total_groups,
-                           pairs_sorted, item_rows ? h->d_len.as<int64_t>() : nullptr, item_rows, item_rows ? item_off : nullptr,
-                           item_rows ? total_items : nullptr, nprobe, 0, nprobe, 0, h->st);
+    return grouped;
+}
+// the main filtered scan: every (query, probe) pair, only the keys above the query's threshold reach its candidate row
+static bool pq_filtered_scan(rsx_index* h, const BatchPlan& P, BatchResult& R, PQScanArgs& a, const PairArea& pr, const PqGeometry& g,
+                             bool grouped, StageTimer& tm) {
+    const int64_t nq = P.nq; const int nlist = h->nlist, nprobe = P.nprobe, KP = P.KP;
+    uint64_t* state = h->w_state.as<uint64_t>();
+    tm.mark("scan0");
+    if (!g.fused_pre) {
+        R.cand_cap = alloc_cand_rows(h, P, h->M);
+        // multi-launch form: top-K' of the scored prefix of the closest list, row prefix
+        // [0, min(seg_start[q][1], pre_rows)), written as the threshold key + counter reset
+        select_rows(h, h->w_temp.as<float>(), P.tmax, h->w_segstart.as<int64_t>() + 1, nprobe + 1,
+                    std::min<int64_t>(P.maxlen, g.pre_rows), 0, nq, KP, P.BUF, KP, state, false,
+                    h->w_candcnt.as<unsigned long long>());
+        // The pre-pass is only a threshold: keep its K'-th key and let the main scan score EVERYTHING (the
+        // prefix included), so the scan kernel carries no per-slab "already scored" test and no key can
+        // arrive twice (the prefix keys above the threshold come back through the candidate buffer).
+        // (the selection wrote only the K'-th key of each query and reset the query's candidate counter)
+        // (a stage mark is an event record: ~5 us of stream time in profile mode — none for a stage that launched nothing)
+        tm.mark("select0");
+    }
+    if (grouped) { if (P.side_lut) HIPCHECK(hipStreamWaitEvent(h->st, h->ev_group, 0)); }
+    else pr.group(h, 4 * P.ngq, g.tile_rows, nprobe, 0, h->st);
+    if (!(grouped && !P.side_lut)) tm.mark("group");
+    const int64_t mi = max_scan_items(h, nq, nprobe, 4 * P.ngq, g.tile_rows);
+    int log_cap = 64;
+    void* rws = P.rot ? rot_scan_ws(h, P.k, mi, P.ngq, log_cap) : nullptr;
+    // threshold keys: one per query from the one-launch pre-pass, else the K'-th key the selection left in the state rows
+    const uint64_t* tau_ptr = g.fused_pre ? h->w_tau.as<uint64_t>() : state + (KP - 1);
+    const int64_t tau_stride = g.fused_pre ? 1 : KP;
+    // candidate gather + selection in one launch when the (probe rank, tile) table of a query is small (rsx_internal.h)
+    const int gs_tmax = (int)((P.maxlen + g.tile_rows - 1) / g.tile_rows);
+    R.use_gather = P.rot && h->pq_gather != 0 && pq_gather_select_applies(nprobe, gs_tmax, KP);
+    if (P.rot && h->pq_gather != 0 && !R.use_gather) h->timing["pq_gather_declined"] += 1;
+    if (R.use_gather) {
+        h->w_qitems.ensure((size_t)nq * nprobe * gs_tmax * 4);
+        PQGatherArgs& gs = R.gs;
+        gs.probe_list = h->w_probelist.as<int32_t>(); gs.list_len = h->d_len.as<int64_t>(); gs.nprobe = nprobe;
+        gs.tile_rows = g.tile_rows; gs.tmax = gs_tmax; gs.qitems = h->w_qitems.as<int32_t>();
+        gs.seg_desc = pq_scan_rot_ws_desc(rws, mi * P.ngq); gs.log_keys = pq_scan_rot_ws_keys(rws, mi * P.ngq);
+        gs.cand = h->w_cand.as<uint64_t>(); gs.cand_cnt = h->w_candcnt.as<unsigned long long>(); gs.cand_cap = R.cand_cap;
+        gs.state = state; gs.KP = KP;
+    }
+    tm.pre_scan();
+    return (P.rot ? launch_pq_scan_rot(a, h->w_lut8.as<uint8_t>(), h->w_qparam.p, pr.pairs_sorted, pr.pair_off, pr.group_off,
+                                       pr.total_groups, pr.item_off, pr.total_items, nlist, mi, g.vpl, tau_ptr, tau_stride,
+                                       h->w_cand.as<uint64_t>(), h->w_candcnt.as<unsigned long long>(), R.cand_cap,
+                                       rws, log_cap, h->pq_prune, (h->pq_pace & 0xffff), (g.fused_pre && P.rot) ? h->w_excl.as<uint16_t>() : nullptr,
+                                       R.use_gather ? h->w_qitems.as<int32_t>() : nullptr, gs_tmax, h->st, P.sliced ? (P.sl_eight ? 1 : 0) : h->pq_q8)
+                  : launch_pq_scan8_filter(a, h->w_lut8.as<uint8_t>(), h->w_qparam.p, pr.pairs_sorted, pr.pair_off, pr.group_off,
+                                           pr.total_groups, pr.item_off, pr.total_items, nlist, mi, g.vpl, tau_ptr, tau_stride,
+                                           h->w_cand.as<uint64_t>(), h->w_candcnt.as<unsigned long long>(), R.cand_cap, h->st)) == 0;
+}
+// 8-bit tables, 4 queries per LDS read; approximate scores, certified in k_finalize
+static void pq_fast_scan(rsx_index* h, const BatchPlan& P, BatchResult& R, PQScanArgs& a, StageTimer& tm) {
+    const int64_t nq = P.nq; const int nlist = h->nlist, nprobe = P.nprobe;
+    h->w_lut8.ensure((size_t)nq * h->Mpad * 256); h->w_qparam.ensure((size_t)nq * 16); h->w_uncertain.ensure((size_t)nq * 8);
+    void* lut_ws = nullptr;
+    if (P.pq_fused_lut && h->dsub == 8 && h->lut_tiled != 0) { h->w_lutws.ensure(pq_lut8_tiled_ws(nq, h->Mpad)); lut_ws = h->w_lutws.p; }
+    const PairArea pr(h, nq, nprobe, nlist);
+    // Two stages, so that only a sliver of the scores ever leaves the scan kernel:
+    //  stage 1: score ONLY the first tile of each query's closest list (probe rank 0) into the score
+    //           buffer and take its top-K' -> state0; its K'-th key is a lower bound of the query's final
+    //           K'-th best key;
+    //  stage 2: scan everything else (all probes, all tiles, minus that piece) in the multi-query groups,
+    //           appending to a small per-query candidate buffer only the keys that beat the bound
+    //           (wave-aggregated atomics); a final select merges them with state0.
+    // A full candidate buffer marks the query uncertain (-> exact fallback), so this is always exact.
+    R.filtered = nprobe > 1 && P.pq_filter != 0;
+    const PqGeometry g = pq_geometry(h, P, R.filtered);
+    bool done = true, grouped = false;
+    if (g.fused_pre) grouped = pq_prepass(h, P, R, pr, g, lut_ws, tm);
+    else {
+        build_pq_tables(h, P, lut_ws, nullptr, tm);
+        h->w_temp.ensure((size_t)nq * P.tmax * 4);       // this form scores a prefix / everything into the score rows
+        a.temp = h->w_temp.as<float>();
+        pr.group(h, 4, g.pre_rows, R.filtered ? 1 : nprobe, R.filtered ? 1 : 0, h->st);
         tm.mark("group");
-        const float* bias = nullptr;
-        if (h->metric == RSX_METRIC_L2) { bias = h->w_misc.as<float>(); }
-        ListScanArgs a{};
-        a.Q16 = h->w_q16.as<__half>(); a.ld = ld; a.X = h->data.p; a.x_f16 = h->storage_f16; a.bias = bias;
-        a.list_base = h->d_base.as<int64_t>(); a.list_len = h->d_len.as<int64_t>();
-        a.pairs_sorted = pairs_sorted; a.pair_off = pair_off; a.group_off = group_off; a.total_groups = total_groups;
-        a.probe_list = h->w_probelist.as<int32_t>(); a.seg_start = h->w_segstart.as<int64_t>();
-        a.nlist = nlist; a.nprobe = nprobe; a.flat_mode = 0; a.nq = (int)nq;
-        a.temp = h->w_temp.as<float>(); a.tstride = tmax;
-        a.max_groups = (int)std::min<int64_t>(npairs, npairs / 16 + std::min<int64_t>(nlist, npairs));
-        int64_t chunk_rows = h->scan_chunk > 0 ? round_up(h->scan_chunk, 64) : 2048;
-        int64_t want = 2048;  // work items
-        while (chunk_rows > 256 && (int64_t)a.max_groups * ((maxlen + chunk_rows - 1) / chunk_rows) < want) chunk_rows /= 2;
-        if (h->scan_chunk <= 0 && list_scan2_chunk_rows(h->storage_f16, ld) > 0) chunk_rows = list_scan2_chunk_rows(h->storage_f16, ld);
-        a.chunk_rows = (int)chunk_rows;
-        a.qtiles = ls_qt;
-        a.max_chunks = (int)std::max<int64_t>(1, (maxlen + chunk_rows - 1) / chunk_rows);
-        // Same two-stage shape as the IVF-PQ fast path when the LDS-DMA kernel applies: score a prefix of every
-        // query's closest list, take its K'-th key as the query's threshold, then scan everything with the keys
-        // above it going to a small per-query candidate buffer instead of a full score row.  A full buffer
-        // (never seen at the bench sizes) falls back to the score-buffer path, so the result is always exact.
-        // (ivf_filter: 1 = when the score rows would exceed ~2 GB — below that the second grouping pass and the
-        //  count read-back cost more than the row traffic they save; 2 = always; 0 = never)
-        // (round 4: for large k the pre-pass scores the first 4 K' rows of the closest list — up to 32 chunks — instead of giving up
-        //  the filter when K' no longer fits one chunk: k = 1000 at nlist 2048 / nprobe 128 wrote and re-read 10 GB of score rows)
-        const int64_t pre_chunks = std::max<int64_t>(1, ((int64_t)KP * std::max(1, h->ivf_pre_mult) + chunk_rows - 1) / chunk_rows);
-        bool want_filter = h->ivf_filter != 0 && nprobe > 1 && chunk_rows == list_scan2_chunk_rows(h->storage_f16, ld) &&
-                           pre_chunks <= 32 && (h->ivf_filter > 1 || nq * tmax >= (int64_t)500000000);
-        if (want_filter) {
-            // ... of the closest list — of the EIGHT closest lists when K' is large: a query whose closest list holds fewer than K'
-            // rows would get no threshold, keep every row of its 128 lists and overflow (the prefix of its score row then runs on
-            // into the next lists' first rows)
-            // (round 4: two lists, not eight — with 64 probing queries per list nearly every list is among some query's eight closest,
-            //  and the 'sample' read 26 of the 31 GB: 3.4 + 0.8 ms of a 13.2 ms batch at nlist 2048 / nprobe 128 / k 1000; two lists
-            //  leave 11.3 ms and as few candidates; ONE list overflows the queries whose closest list is short: profiles/r04_n_docs_1000.md)
-            // ivf_pre_lists = 0 (default): the query's TWO closest lists.  ONE list is not enough even when it is long: at nlist 2048 /
-            // nprobe 128 its K'-th key lets > 131072 keys of some queries through (the score-row pass follows: 27 instead of 11.7 ms); at
-            // 100M / nprobe 32 it would do (28.7 against 29.8 ms) — two is the setting that is safe at both (profiles/r04_n_docs_1000.md).
-            // (a per-query list count — two, and up to two more where the closest lists are short — cost 1-2 % on the bench configs and was
-            //  removed in round 5: profiles/r04_n_docs_1000.md)
-            const int pre_want = h->ivf_pre_lists > 0 ? h->ivf_pre_lists : 2;
-            const int pre_lists = (KP >= 256 && (int64_t)pre_want * pre_chunks * chunk_rows <= tmax) ? std::min(pre_want, nprobe) : 1;
-            a.max_chunks = (int)pre_chunks;                        // the first chunk(s) of ...
-            a.qtiles = 1;                                          // (groups of 16 there: most lists are the closest of at most a few queries)
-            const int64_t pre_stride = pre_lists > 1 ? pre_chunks * chunk_rows : 0;    // several lists: one slice of the sample buffer each
-            if (pre_stride) {
-                a.pre_stride = pre_stride; a.tstride = pre_lists * pre_stride;
-                launch_fill_f32(h->w_temp.as<float>(), nq * a.tstride, -INFINITY, h->st);
-            }
-            launch_group_pairs(h->w_probelist.as<int32_t>(), npairs, nlist, 16, cnt, cursor, pair_off, group_off, total_groups,
-                               pairs_sorted, nullptr, 0, nullptr, nullptr, nprobe, 0, pre_lists, 0, h->st);   // ... the closest list(s) only
-            launch_list_scan(a, h->st);
-            tm.mark("scan0");
-            cand_cap = (int)std::min<int64_t>(std::max<int64_t>(tmax, 1024), k > 512 ? 131072 : (k > 64 ? 65536 : 16384));
-            h->w_cand.ensure((size_t)nq * cand_cap * 8);
-            h->w_candcnt.ensure((size_t)nq * 8 * CCS);
-            // the pre-pass is only a threshold (see the IVF-PQ path): the K'-th key, candidate counters reset
-            if (pre_stride) {
-                select_rows(h, h->w_temp.as<float>(), a.tstride, nullptr, 0, a.tstride, 0,
-                            nq, KP, BUF, KP, state, false, h->w_candcnt.as<unsigned long long>());
-                a.pre_stride = 0; a.tstride = tmax;
-            } else
-            select_rows(h, h->w_temp.as<float>(), tmax, h->w_segstart.as<int64_t>() + 1, nprobe + 1,
-                        std::min<int64_t>(maxlen, pre_chunks * chunk_rows), 0, nq, KP, BUF, KP, state, false,
-                        h->w_candcnt.as<unsigned long long>());
-            tm.mark("select0");
-            launch_group_pairs(h->w_probelist.as<int32_t>(), npairs, nlist, 16 * ls_qt, cnt, cursor, pair_off, group_off, total_groups,
-                               pairs_sorted, item_rows ? h->d_len.as<int64_t>() : nullptr, item_rows, item_rows ? item_off : nullptr,
-                               item_rows ? total_items : nullptr, nprobe, 0, nprobe, 0, h->st);
-            tm.mark("group");
-            a.qtiles = ls_qt;
-            if (ls_wide) { chunk_rows *= 2; a.chunk_rows = (int)chunk_rows; }      // 8 waves, 1024 rows per work item
-            a.max_chunks = (int)std::max<int64_t>(1, (maxlen + chunk_rows - 1) / chunk_rows);
-            if (item_rows == (int)chunk_rows) { a.item_off = item_off; a.total_items = total_items; a.max_items = (int)max_scan_items(h, nq, nprobe, 16 * ls_qt, item_rows); }
-            a.tau_key = state + (KP - 1); a.tau_stride = KP;
-            a.cand = h->w_cand.as<uint64_t>(); a.cand_cnt = h->w_candcnt.as<unsigned long long>(); a.cand_cap = cand_cap;
-            launch_list_scan(a, h->st);
-            tm.mark("scan");
-            std::vector<unsigned long long> cnts((size_t)nq * CCS);
-            HIPCHECK(hipMemcpyAsync(cnts.data(), h->w_candcnt.p, (size_t)nq * 8 * CCS, hipMemcpyDeviceToHost, h->st));
-            HIPCHECK(hipStreamSynchronize(h->st));
-            filtered = true;
-            // A few overflowed rows (a query between clusters whose sample gave a weak threshold) no longer send the whole batch through the
-            // unfiltered scan (10 -> 25 ms at nlist 2048 / nprobe 128 / k 1000 for ONE such query): with the certificate behind the search
-            // k_finalize flags them (cand_cnt > cand_cap) and they alone join the exact re-run (~1.1 ms per query at that size with k_exact_scores_f16: up to nq / 128
-            // of them are cheaper than the rescan); more overflows mean the threshold failed for this data, and the batch is rescanned
-            int64_t n_over = 0;
-            for (int64_t qi = 0; qi < nq; qi++) n_over += cnts[(size_t)qi * CCS] > (unsigned long long)cand_cap;
-            if (n_over > 0 && !(certify && n_over <= (h->ivf_overflow_max > 0 ? (int64_t)h->ivf_overflow_max : std::max<int64_t>(2, nq / 128)))) filtered = false;
-            if (filtered && n_over > 0) { flag_overflows = true; h->timing["ivf_filter_overflow_queries"] += (double)n_over; }
-            a.tau_key = nullptr; a.cand = nullptr; a.cand_cnt = nullptr; a.cand_cap = 0;
-        }
-        if (!filtered) {
-            if (ls_wide && a.chunk_rows == list_scan2_chunk_rows(h->storage_f16, ld)) {     // 8 waves, 1024 rows per work item
-                a.chunk_rows *= 2;
-                a.max_chunks = (int)std::max<int64_t>(1, (maxlen + a.chunk_rows - 1) / a.chunk_rows);
-            }
-            if (!want_filter && item_rows > 0 && item_rows == a.chunk_rows) {     // (after a filtered attempt the grouping in place is the filtered scan's: same items)
-                a.item_off = item_off; a.total_items = total_items; a.max_items = (int)max_scan_items(h, nq, nprobe, 16 * ls_qt, item_rows);
-            }
-            launch_list_scan(a, h->st);
-            tm.mark("scan");
-        }
+        const int64_t mi = R.filtered ? (nq + nlist + 8) : max_scan_items(h, nq, nprobe, 4, g.tile_rows);
+        int log_cap = 64;
+        void* rws = P.rot ? rot_scan_ws(h, P.k, mi, 1, log_cap) : nullptr;
+        const int vpl = R.filtered ? g.pre_vpl : g.vpl;
+        done = (P.rot ? launch_pq_scan_rot(a, h->w_lut8.as<uint8_t>(), h->w_qparam.p, pr.pairs_sorted, pr.pair_off, pr.group_off,
+                                           pr.total_groups, pr.item_off, pr.total_items, nlist, mi, vpl,
+                                           nullptr, 0, nullptr, nullptr, 0, rws, log_cap, 0, 0, nullptr, nullptr, 0, h->st)
+                      : launch_pq_scan8(a, h->w_lut8.as<uint8_t>(), h->w_qparam.p, pr.pairs_sorted, pr.pair_off, pr.group_off,
+                                        pr.total_groups, pr.item_off, pr.total_items, nlist, mi, vpl, h->st)) == 0;
     }
+    if (done && R.filtered) done = pq_filtered_scan(h, P, R, a, pr, g, grouped, tm);
+    if (!done) RSX_THROW(RSX_ERR_UNSUPPORTED, "IVFPQ fast scan: no kernel for M=%d", h->M);
+    // rotated layout, threshold by construction: finalize straight from the complete candidate row (k_pq_final_tab) when K'
+    // is large or a table entry is a long chain (M = 16: dsub 48) — the K' cut, its certificate and the second chance disappear
+    R.tab_fits = R.filtered && R.fused_pre_used && P.rot && h->pq_final_tab != 0 && pq_final_tab_capacity(h->M, h->CB, P.k) > 0;
+    R.use_tab = R.tab_fits && (h->pq_final_tab == 2 || P.KP >= 512 || h->dsub > 8);
+}
+static void pq_exact_scan(rsx_index* h, const BatchPlan& P, PQScanArgs& a, StageTimer& tm) {
+    const int64_t nq = P.nq, pairs = nq * P.nprobe; const int nlist = h->nlist;
+    const bool pq_l2 = h->metric == RSX_METRIC_L2;      // per-(query, list) tables, built inside the scan (k_pq_scan_l2)
+    if (h->scan_kernel != 1 && h->CB == 16 && !pq_l2) {
+        // v2: list-major, two queries per LDS read
+        int64_t avg_slabs = std::max<int64_t>(1, (h->ntotal / std::max(1, nlist) + 63) / 64);
+        int vpl = 8;
+        if (h->scan_chunk > 0) vpl = std::max(1, std::min(8, h->scan_chunk / 1024));
+        else while (vpl > 1 && (pairs / 2 + 1) * ((avg_slabs + 16 * vpl - 1) / (16 * vpl)) < 2048) vpl /= 2;
+        if (vpl != 8 && vpl != 4 && vpl != 2) vpl = 1;
+        const int tile_rows = 64 * 16 * vpl;
+        const PairArea pr(h, nq, P.nprobe, nlist);
+        pr.group(h, 2, tile_rows, P.nprobe, 0, h->st);
+        tm.mark("group");
+        if (launch_pq_scan2(a, pr.pairs_sorted, pr.pair_off, pr.group_off, pr.total_groups, pr.item_off, pr.total_items, nlist,
+                            max_scan_items(h, nq, P.nprobe, 2, tile_rows), vpl, h->st) == 0) return;
+    }
+    const int64_t max_slabs = std::max<int64_t>(1, P.maxlen / 64); int64_t spc;
+    if (h->scan_chunk > 0) spc = std::max<int64_t>(16, h->scan_chunk / 64);
+    else {
+        // enough work items to fill 256 CUs several times over, but no smaller than 32 slabs
+        const int64_t want_items = 4096, chunks = std::max<int64_t>(1, (want_items + pairs - 1) / pairs);
+        spc = std::max<int64_t>(32, (max_slabs + chunks - 1) / chunks);
+    }
+    a.slabs_per_chunk = (int)spc;
+    a.max_chunks = (int)((max_slabs + spc - 1) / spc);
+    if ((pq_l2 ? launch_pq_scan_l2(a, h->w_q32.as<float>(), h->ld, h->d_centroids.as<float>(), h->d_codebooks.as<float>(), h->d, h->dsub, h->st)
+               : P.rot ? launch_pq_scan_rot_exact(a, h->st) : launch_pq_scan(a, h->st)) != 0)
+        RSX_THROW(RSX_ERR_UNSUPPORTED, "IVFPQ scan: no kernel for M=%d", h->M);
+}
+static void pq_scan(rsx_index* h, const BatchPlan& P, BatchResult& R, StageTimer& tm) {
+    // the exact kernels gather fp32 table entries; the fast path builds the table in LDS (when it fits)
+    if (!P.pq_fused_lut && h->metric != RSX_METRIC_L2) {
+        h->w_lut.ensure((size_t)P.nq * h->Mpad * 256 * 4);
+        launch_pq_lut(h->w_q32.as<float>(), h->ld, P.nq, h->d, h->M, h->Mpad, h->d_codebooks.as<float>(), h->w_lut.as<float>(), h->st);
+        tm.mark("lut");
+    }
+    PQScanArgs a{};
+    a.codes = h->data.as<uint8_t>(); a.M = h->M; a.Mpad = h->Mpad; a.CB = h->CB;
+    a.list_base = h->d_base.as<int64_t>(); a.list_len = h->d_len.as<int64_t>();
+    a.lut = h->w_lut.as<float>(); a.probe_list = h->w_probelist.as<int32_t>(); a.probe_dis0 = h->w_dis0.as<float>();
+    a.seg_start = h->w_segstart.as<int64_t>(); a.nq = P.nq; a.nprobe = P.nprobe;
+    a.temp = h->w_temp.as<float>(); a.tstride = P.tmax;
+    if (P.fast) pq_fast_scan(h, P, R, a, tm);
+    else pq_exact_scan(h, P, a, tm);
+    h->timing[P.allow_fast ? "scan_launches" : "fb_scan_launches"] += 1;
+    tm.mark("scan");
+}
+// exact mode (see the Flat path): fp64 scores of every row of the probed lists into the score rows
+static void ivf_flat_exact(rsx_index* h, const BatchPlan& P, StageTimer& tm) {
+    ExactScoreArgs ea{};
+    ea.kind = KIND_IVFFLAT; ea.metric = h->metric; ea.nq = P.nq; ea.Q32 = h->w_q32.as<float>(); ea.ldq = h->ld; ea.d = h->d;
+    ea.X = h->data.p; ea.x_f16 = h->storage_f16; ea.ld = h->ld; ea.temp = h->w_temp.as<float>(); ea.tstride = P.tmax;
+    ea.probe_list = h->w_probelist.as<int32_t>(); ea.seg_start = h->w_segstart.as<int64_t>(); ea.nprobe = P.nprobe;
+    ea.list_base = h->d_base.as<int64_t>(); ea.list_len = h->d_len.as<int64_t>();
+    launch_exact_scores(ea, h->st);
+    tm.mark("scan");
+}
+// Same two-stage shape as the IVF-PQ fast path when the LDS-DMA kernel applies: score a prefix of every
+// query's closest list, take its K'-th key as the query's threshold, then scan everything with the keys
+// above it going to a small per-query candidate buffer instead of a full score row.  A full buffer
+// (never seen at the bench sizes) falls back to the score-buffer path, so the result is always exact.
+// Returns whether the batch was filtered; a holds the unfiltered scan's arguments again either way.
+static bool ivf_flat_filtered(rsx_index* h, const BatchPlan& P, BatchResult& R, ListScanArgs& a, const PairArea& pr, int ls_qt, int item_rows,
+                              int64_t pre_chunks, StageTimer& tm) {
+    const int64_t nq = P.nq, tmax = P.tmax; const int nprobe = P.nprobe, KP = P.KP;
+    uint64_t* state = h->w_state.as<uint64_t>();
+    int64_t chunk_rows = a.chunk_rows;
+    // ... of the closest list — of the EIGHT closest lists when K' is large: a query whose closest list holds fewer than K'
+    // rows would get no threshold, keep every row of its 128 lists and overflow (the prefix of its score row then runs on
+    // into the next lists' first rows)
+    // (round 4: two lists, not eight — with 64 probing queries per list nearly every list is among some query's eight closest,
+    //  and the 'sample' read 26 of the 31 GB: 3.4 + 0.8 ms of a 13.2 ms batch at nlist 2048 / nprobe 128 / k 1000; two lists
+    //  leave 11.3 ms and as few candidates; ONE list overflows the queries whose closest list is short: profiles/r04_n_docs_1000.md)
+    // ivf_pre_lists = 0 (default): the query's TWO closest lists.  ONE list is not enough even when it is long: at nlist 2048 /
+    // nprobe 128 its K'-th key lets > 131072 keys of some queries through (the score-row pass follows: 27 instead of 11.7 ms); at
+    // 100M / nprobe 32 it would do (28.7 against 29.8 ms) — two is the setting that is safe at both (profiles/r04_n_docs_1000.md).
+    // (a per-query list count — two, and up to two more where the closest lists are short — cost 1-2 % on the bench configs and was
+    //  removed in round 5: profiles/r04_n_docs_1000.md)
+    const int pre_want = h->ivf_pre_lists > 0 ? h->ivf_pre_lists : 2;
+    const int pre_lists = (KP >= 256 && (int64_t)pre_want * pre_chunks * chunk_rows <= tmax) ? std::min(pre_want, nprobe) : 1;
+    a.max_chunks = (int)pre_chunks;                        // the first chunk(s) of ...
+    a.qtiles = 1;                                          // (groups of 16 there: most lists are the closest of at most a few queries)
+    const int64_t pre_stride = pre_lists > 1 ? pre_chunks * chunk_rows : 0;    // several lists: one slice of the sample buffer each
+    if (pre_stride) {
+        a.pre_stride = pre_stride; a.tstride = pre_lists * pre_stride;
+        launch_fill_f32(h->w_temp.as<float>(), nq * a.tstride, -INFINITY, h->st);
+    }
+    pr.group(h, 16, 0, pre_lists, 0, h->st);       // ... the closest list(s) only
+    launch_list_scan(a, h->st);
+    tm.mark("scan0");
+    R.cand_cap = alloc_cand_rows(h, P, 0);
+    // the pre-pass is only a threshold (see the IVF-PQ path): the K'-th key, candidate counters reset
+    if (pre_stride) {
+        select_rows(h, h->w_temp.as<float>(), a.tstride, nullptr, 0, a.tstride, 0,
+                    nq, KP, P.BUF, KP, state, false, h->w_candcnt.as<unsigned long long>());
+        a.pre_stride = 0; a.tstride = tmax;
+    } else
+        select_rows(h, h->w_temp.as<float>(), tmax, h->w_segstart.as<int64_t>() + 1, nprobe + 1,
+                    std::min<int64_t>(P.maxlen, pre_chunks * chunk_rows), 0, nq, KP, P.BUF, KP, state, false,
+                    h->w_candcnt.as<unsigned long long>());
+    tm.mark("select0");
+    pr.group(h, 16 * ls_qt, item_rows, nprobe, 0, h->st);
+    tm.mark("group");
+    a.qtiles = ls_qt;
+    if (ls_qt >= 4) { chunk_rows *= 2; a.chunk_rows = (int)chunk_rows; }      // 8 waves, 1024 rows per work item
+    a.max_chunks = (int)std::max<int64_t>(1, (P.maxlen + chunk_rows - 1) / chunk_rows);
+    if (item_rows == (int)chunk_rows) { a.item_off = pr.item_off; a.total_items = pr.total_items; a.max_items = (int)max_scan_items(h, nq, nprobe, 16 * ls_qt, item_rows); }
+    a.tau_key = state + (KP - 1); a.tau_stride = KP;
+    a.cand = h->w_cand.as<uint64_t>(); a.cand_cnt = h->w_candcnt.as<unsigned long long>(); a.cand_cap = R.cand_cap;
+    launch_list_scan(a, h->st);
+    tm.mark("scan");
+    std::vector<unsigned long long> cnts((size_t)nq * CCS);
+    HIPCHECK(hipMemcpyAsync(cnts.data(), h->w_candcnt.p, (size_t)nq * 8 * CCS, hipMemcpyDeviceToHost, h->st));
+    HIPCHECK(hipStreamSynchronize(h->st));
+    bool filtered = true;
+    // A few overflowed rows (a query between clusters whose sample gave a weak threshold) no longer send the whole batch through the
+    // unfiltered scan (10 -> 25 ms at nlist 2048 / nprobe 128 / k 1000 for ONE such query): with the certificate behind the search
+    // k_finalize flags them (cand_cnt > cand_cap) and they alone join the exact re-run (~1.1 ms per query at that size with k_exact_scores_f16: up to nq / 128
+    // of them are cheaper than the rescan); more overflows mean the threshold failed for this data, and the batch is rescanned
+    int64_t n_over = 0;
+    for (int64_t qi = 0; qi < nq; qi++) n_over += cnts[(size_t)qi * CCS] > (unsigned long long)R.cand_cap;
+    if (n_over > 0 && !(P.certify && n_over <= (h->ivf_overflow_max > 0 ? (int64_t)h->ivf_overflow_max : std::max<int64_t>(2, nq / 128)))) filtered = false;
+    if (filtered && n_over > 0) { R.flag_overflows = true; h->timing["ivf_filter_overflow_queries"] += (double)n_over; }
+    a.tau_key = nullptr; a.cand = nullptr; a.cand_cnt = nullptr; a.cand_cap = 0;
+    return filtered;
+}
+// group (query, probe) pairs by list, then list-major MFMA scan
+static void ivf_flat_scan(rsx_index* h, const BatchPlan& P, BatchResult& R, StageTimer& tm) {
+    const int64_t nq = P.nq, npairs = nq * P.nprobe; const int nlist = h->nlist, nprobe = P.nprobe, ld = h->ld;
+    const PairArea pr(h, nq, nprobe, nlist);
+    // probing queries per group of the LDS-DMA list scans.  A group passes over its list's rows once, so the larger the group the fewer
+    // passes: 16 (k_list_scan2<_, 1>: two workgroups per CU), 64 (the 8-wave form, queries in LDS) or 128 (k_list_scan3, queries in
+    // registers: d = 384 / 512 / 768 / 1024).  Round 5, 20M x 768, inner product, batch 1024 (profiles/r05_ivfflat_wide.md): at 8 probing queries per
+    // list on average 16 wins (5.47 ms against 5.59 with 64), at 16 already 64 does (nlist 2048 / nprobe 32: 5.08 against 5.95;
+    // nlist 4096 / nprobe 64: 6.93 against 8.53), at 32 64 beats 128 (5.20 against 5.61: no list needs a second pass yet, and the
+    // 8-wave form has no barrier), at 64 and more 128 wins (6.04 against 7.23; nlist 1024 / nprobe 128: 10.6 against 11.4).  The
+    // 32-query form lost everywhere and is only reachable through the parameter.
+    int ls_qt = 1;
+    if (h->scan_chunk <= 0 && h->ivf_qtiles != 0 && list_scan2_chunk_rows(h->storage_f16, ld) > 0) {
+        const int64_t qpl = npairs / std::max(1, nlist);
+        const bool ls3 = list_scan3_applies(h->storage_f16, ld, h->metric == RSX_METRIC_L2) != 0;      // 128 queries per group, held in registers (k_list_scan3)
+        ls_qt = h->ivf_qtiles > 1 ? h->ivf_qtiles : (qpl >= 48 && ls3 ? 8 : qpl >= 12 ? 4 : 1);
+        if (ls_qt == 8 && !ls3) ls_qt = 4;
+        if (ls_qt != 8) ls_qt = std::min(ls_qt == 3 ? 2 : ls_qt, list_scan2_max_qtiles(ld));
+        if (ls_qt != 2 && ls_qt != 4 && ls_qt != 8) ls_qt = 1;
+    }
+    // (list, chunk, group) work items in list-major order for the LDS-DMA scan's XCD-aware 1-D grid (round 4): the groups of a
+    // list chunk run on one XCD at the same moment and its rows cross HBM once — at nlist 2048 / nprobe 128 half of the lists
+    // are probed by more than 64 queries, i.e. by two groups, which used to land on different XCDs (two fetches)
+    const int ls2_rows = list_scan2_chunk_rows(h->storage_f16, ld);
+    const bool ls_wide = ls_qt >= 4;     // the 8-wave forms: 1024 rows per work item
+    const int item_rows = (h->scan_chunk <= 0 && ls2_rows > 0) ? (ls_wide ? 2 * ls2_rows : ls2_rows) : 0;
+    pr.group(h, 16 * ls_qt, item_rows, nprobe, 0, h->st);
+    tm.mark("group");
+    ListScanArgs a{};
+    a.Q16 = h->w_q16.as<__half>(); a.ld = ld; a.X = h->data.p; a.x_f16 = h->storage_f16;
+    a.bias = h->metric == RSX_METRIC_L2 ? h->w_misc.as<float>() : nullptr;
+    a.list_base = h->d_base.as<int64_t>(); a.list_len = h->d_len.as<int64_t>();
+    a.pairs_sorted = pr.pairs_sorted; a.pair_off = pr.pair_off; a.group_off = pr.group_off; a.total_groups = pr.total_groups;
+    a.probe_list = h->w_probelist.as<int32_t>(); a.seg_start = h->w_segstart.as<int64_t>();
+    a.nlist = nlist; a.nprobe = nprobe; a.flat_mode = 0; a.nq = (int)nq;
+    a.temp = h->w_temp.as<float>(); a.tstride = P.tmax;
+    a.max_groups = (int)std::min<int64_t>(npairs, npairs / 16 + std::min<int64_t>(nlist, npairs));
+    int64_t chunk_rows = h->scan_chunk > 0 ? round_up(h->scan_chunk, 64) : 2048;
+    int64_t want = 2048;  // work items
+    while (chunk_rows > 256 && (int64_t)a.max_groups * ((P.maxlen + chunk_rows - 1) / chunk_rows) < want) chunk_rows /= 2;
+    if (h->scan_chunk <= 0 && ls2_rows > 0) chunk_rows = ls2_rows;
+    a.chunk_rows = (int)chunk_rows;
+    a.qtiles = ls_qt;
+    a.max_chunks = (int)std::max<int64_t>(1, (P.maxlen + chunk_rows - 1) / chunk_rows);
+    // (ivf_filter: 1 = when the score rows would exceed ~2 GB — below that the second grouping pass and the
+    //  count read-back cost more than the row traffic they save; 2 = always; 0 = never)
+    // (round 4: for large k the pre-pass scores the first 4 K' rows of the closest list — up to 32 chunks — instead of giving up
+    //  the filter when K' no longer fits one chunk: k = 1000 at nlist 2048 / nprobe 128 wrote and re-read 10 GB of score rows)
+    const int64_t pre_chunks = std::max<int64_t>(1, ((int64_t)P.KP * std::max(1, h->ivf_pre_mult) + chunk_rows - 1) / chunk_rows);
+    const bool want_filter = P.ivf_filter != 0 && nprobe > 1 && chunk_rows == ls2_rows &&
+                             pre_chunks <= 32 && (P.ivf_filter > 1 || nq * P.tmax >= (int64_t)500000000);
+    if (want_filter) R.filtered = ivf_flat_filtered(h, P, R, a, pr, ls_qt, item_rows, pre_chunks, tm);
+    if (!R.filtered) {
+        if (ls_wide && a.chunk_rows == ls2_rows) {     // 8 waves, 1024 rows per work item
+            a.chunk_rows *= 2;
+            a.max_chunks = (int)std::max<int64_t>(1, (P.maxlen + a.chunk_rows - 1) / a.chunk_rows);
+        }
+        if (!want_filter && item_rows > 0 && item_rows == a.chunk_rows) {     // (after a filtered attempt the grouping in place is the filtered scan's: same items)
+            a.item_off = pr.item_off; a.total_items = pr.total_items; a.max_items = (int)max_scan_items(h, nq, nprobe, 16 * ls_qt, item_rows);
+        }
+        launch_list_scan(a, h->st);
+        tm.mark("scan");
+    }
+}
+// per-query k-selection over the score rows (after a filtered search's selector mask) or the candidate rows
+static void select_stage(rsx_index* h, const BatchPlan& P, const BatchResult& R, StageTimer& tm) {
+    const int64_t nq = P.nq; uint64_t* state = h->w_state.as<uint64_t>();
     if (h->sel) {
-        // filtered search (search_impl turned the in-scan candidate filters off): the scans above wrote complete score rows —
+        // filtered search (the plan turned the in-scan candidate filters off): the scans above wrote complete score rows —
         // approximate (certified fast scans) or exact — and the unselected rows leave them before the selection
-        if (filtered) RSX_THROW(RSX_ERR_INVALID, "filtered search reached a scan without score rows");
+        if (R.filtered) RSX_THROW(RSX_ERR_INVALID, "filtered search reached a scan without score rows");
         SelApplyArgs sa{};
-        sa.temp = h->w_temp.as<float>(); sa.tstride = tmax; sa.nq = nq; sa.mask = h->sel_mask.as<uint32_t>(); sa.flat_n = -1;
-        sa.probe_list = h->w_probelist.as<int32_t>(); sa.seg_start = h->w_segstart.as<int64_t>(); sa.nprobe = nprobe;
+        sa.temp = h->w_temp.as<float>(); sa.tstride = P.tmax; sa.nq = nq; sa.mask = h->sel_mask.as<uint32_t>(); sa.flat_n = -1;
+        sa.probe_list = h->w_probelist.as<int32_t>(); sa.seg_start = h->w_segstart.as<int64_t>(); sa.nprobe = P.nprobe;
         sa.list_base = h->d_base.as<int64_t>(); sa.list_len = h->d_len.as<int64_t>();
         launch_sel_apply(sa, h->st);
         tm.mark("sel_apply");
     }
-    // IVF-PQ, rotated layout, threshold by construction: finalize straight from the complete candidate row (k_pq_final_tab) when K'
-    // is large or a table entry is a long chain (M = 16: dsub 48) — the K' cut, its certificate and the second chance disappear
-    const int tabP = (fast && filtered && fused_pre_used && rot && h->pq_final_tab != 0) ? pq_final_tab_capacity(h->M, h->CB, k) : 0;
-    const bool use_tab = tabP > 0 && (h->pq_final_tab == 2 || KP >= 512 || h->dsub > 8);
-    // 3. per-query k-selection over the score rows
-    if (filtered && use_gather) {
-        if (use_tab) gs.KP = 0;        // gather only
+    if (R.filtered && R.use_gather) {
+        PQGatherArgs gs = R.gs; if (R.use_tab) gs.KP = 0;        // gather only
         launch_pq_gather_select(gs, nq, h->st);
-    } else if (filtered && use_tab) {
+    } else if (R.filtered && R.use_tab) {
         // the compaction has laid the survivors end to end in the candidate rows already
-    } else if (filtered) {
-        // merge the filtered candidates (keys) into state0: one wave per query, the whole buffer in one segment
-        SelectArgs b{};
-        b.in = h->w_cand.p; b.in_is_keys = 1; b.row_stride = cand_cap;
-        b.row_n = reinterpret_cast<const int64_t*>(h->w_candcnt.p); b.row_n_stride = CCS; b.n_uniform = cand_cap;
-        b.seg_len = round_up(cand_cap, 256); b.nseg = 1; b.idx_base = 0;
-        b.init = state; b.out = state; b.out_row_stride = KP;
-        b.nrows = nq; b.KP = KP; b.BUF = BUF; b.k = KP;
-        launch_select(b, h->st);
+    } else if (R.filtered) {
+        // merge the filtered candidates (keys) into state0
+        merge_key_rows(h, h->w_cand.p, h->w_candcnt.as<unsigned long long>(), R.cand_cap, nq, state, state, P.KP, P.BUF);
     } else {
         // fast scan: the certificate needs the TRUE top-K' by approximate score, so the selection threshold
         // is the K'-th key, not the k-th
-        select_rows(h, h->w_temp.as<float>(), tmax, h->w_segstart.as<int64_t>() + nprobe, nprobe + 1, tmax, 0, nq, KP, BUF,
-                    (fast || h->kind == KIND_IVFFLAT) ? KP : k, state, false);
+        select_rows(h, h->w_temp.as<float>(), P.tmax, h->w_segstart.as<int64_t>() + P.nprobe, P.nprobe + 1, P.tmax, 0, nq, P.KP, P.BUF,
+                    (P.fast || h->kind == KIND_IVFFLAT) ? P.KP : P.k, state, false);
     }
     tm.mark("select");
-    if (filtered && h->profile >= 2) {   // diagnostics: keys that passed the in-kernel filter
+    if (R.filtered && h->profile >= 2) {   // diagnostics: keys that passed the in-kernel filter
         std::vector<unsigned long long> cnts((size_t)nq * CCS);
         HIPCHECK(hipMemcpyAsync(cnts.data(), h->w_candcnt.p, (size_t)nq * 8 * CCS, hipMemcpyDeviceToHost, h->st));
         HIPCHECK(hipStreamSynchronize(h->st));
@@ -1062,43 +1044,48 @@ static void search_batch(rsx_index* h, int64_t nq, const void* dq, int dtype, in
         for (int64_t qi = 0; qi < nq; qi++) { const double c = (double)cnts[(size_t)qi * CCS]; tot += c; mx = std::max(mx, c); }
         h->timing["cand_keys"] += tot; h->timing["cand_keys_max"] = std::max(h->timing["cand_keys_max"], mx);
     }
-    fa.probe_list = h->w_probelist.as<int32_t>(); fa.seg_start = h->w_segstart.as<int64_t>(); fa.nprobe = nprobe;
-    if (flag_overflows) { fa.cand_cnt = h->w_candcnt.as<unsigned long long>(); fa.cand_cap = cand_cap; }     // IVF-Flat: certify_rows flags the overflowed rows' queries
-    if (fast) {
-        fa.pq_rescore = 1; fa.codes = h->data.as<uint8_t>(); fa.M = h->M; fa.Mpad = h->Mpad; fa.CB = h->CB;
-        // large K' (the reference's n_docs = 100 ... 2000): thousands of candidates per query are re-scored, and in the scan layouts a candidate's
-        // M code bytes are M / 16 pieces in as many 64-byte sectors — the finalize then runs at the HBM's random-sector rate.  A row-major copy
-        // of the codes (pq_plain_stride(M) bytes per vector more — 128 at M = 96, so that a row is ONE 128-byte line: 288 GB of HBM hold it); built on the first such search of an
-        // index state, dropped by the next add.  rsx_set_param "pq_plain_codes" = 0 turns it off.
-        if (rot && KP >= 256 && h->pq_plain_codes != 0 && h->M >= 32 && h->M % 16 == 0 && h->M == h->Mpad) {
-            if (h->plain_gen != h->dir_gen || h->plain_of != h->data.p) {
-                const size_t need = (size_t)std::max<int64_t>(h->total_cap, 1) * (size_t)pq_plain_stride(h->M);
-                size_t fr = 0, tot = 0;
-                h->plain_of = nullptr;
-                if (hipMemGetInfo(&fr, &tot) == hipSuccess && (h->codes_plain.bytes >= need || fr > need + need / 8 + ((size_t)8 << 30))) {
-                    h->codes_plain.ensure(need);
-                    launch_pq_plain_rows(h->data.as<uint8_t>(), h->total_cap, h->M, h->CB, h->codes_plain.as<uint8_t>(), h->st);
-                    h->plain_gen = h->dir_gen; h->plain_of = h->data.p;
-                    h->timing["plain_codes_builds"] += 1;
-                }
-            }
-            if (h->plain_of == h->data.p && h->plain_gen == h->dir_gen) { fa.codes_plain = h->codes_plain.as<uint8_t>(); fa.plain_stride = pq_plain_stride(h->M); }
+}
+// large K' (the reference's n_docs = 100 ... 2000): thousands of candidates per query are re-scored, and in the scan layouts a candidate's
+// M code bytes are M / 16 pieces in as many 64-byte sectors — the finalize then runs at the HBM's random-sector rate.  A row-major copy
+// of the codes (pq_plain_stride(M) bytes per vector more — 128 at M = 96, so that a row is ONE 128-byte line: 288 GB of HBM hold it); built on the first such search of an
+// index state, dropped by the next add.  rsx_set_param "pq_plain_codes" = 0 turns it off.
+static void plain_codes(rsx_index* h, const BatchPlan& P, FinalizeArgs& fa) {
+    if (!(P.rot && P.KP >= 256 && h->pq_plain_codes != 0 && h->M >= 32 && h->M % 16 == 0 && h->M == h->Mpad)) return;
+    if (h->plain_gen != h->dir_gen || h->plain_of != h->data.p) {
+        const size_t need = (size_t)std::max<int64_t>(h->total_cap, 1) * (size_t)pq_plain_stride(h->M);
+        size_t fr = 0, tot = 0;
+        h->plain_of = nullptr;
+        if (hipMemGetInfo(&fr, &tot) == hipSuccess && (h->codes_plain.bytes >= need || fr > need + need / 8 + ((size_t)8 << 30))) {
+            h->codes_plain.ensure(need);
+            launch_pq_plain_rows(h->data.as<uint8_t>(), h->total_cap, h->M, h->CB, h->codes_plain.as<uint8_t>(), h->st);
+            h->plain_gen = h->dir_gen; h->plain_of = h->data.p;
+            h->timing["plain_codes_builds"] += 1;
         }
-        fa.lut32 = fused_lut ? nullptr : h->w_lut.as<float>(); fa.codebooks = h->d_codebooks.as<float>(); fa.dsub = h->dsub;
+    }
+    if (h->plain_of == h->data.p && h->plain_gen == h->dir_gen) { fa.codes_plain = h->codes_plain.as<uint8_t>(); fa.plain_stride = pq_plain_stride(h->M); }
+}
+static void finalize_stage(rsx_index* h, const BatchPlan& P, const BatchResult& R, FinalizeArgs& fa, StageTimer& tm) {
+    const int64_t nq = P.nq;
+    fa.probe_list = h->w_probelist.as<int32_t>(); fa.seg_start = h->w_segstart.as<int64_t>(); fa.nprobe = P.nprobe;
+    if (R.flag_overflows) { fa.cand_cnt = h->w_candcnt.as<unsigned long long>(); fa.cand_cap = R.cand_cap; }     // IVF-Flat: certify_rows flags the overflowed rows' queries
+    if (P.fast) {
+        fa.pq_rescore = 1; fa.codes = h->data.as<uint8_t>(); fa.M = h->M; fa.Mpad = h->Mpad; fa.CB = h->CB;
+        plain_codes(h, P, fa);
+        fa.lut32 = P.pq_fused_lut ? nullptr : h->w_lut.as<float>(); fa.codebooks = h->d_codebooks.as<float>(); fa.dsub = h->dsub;
         fa.probe_dis0 = h->w_dis0.as<float>(); fa.qparam = h->w_qparam.p;
         fa.uncertain = h->w_uncertain.as<int32_t>();
-        if (filtered) { fa.cand_cnt = h->w_candcnt.as<unsigned long long>(); fa.cand_cap = cand_cap; }
+        if (R.filtered) { fa.cand_cnt = h->w_candcnt.as<unsigned long long>(); fa.cand_cap = R.cand_cap; }
     }
-    // (the tie scratch is allocated where k_pq_final_tab actually runs, not whenever it is a possible second chance)
-    if (use_tab) h->w_tiews.ensure((size_t)nq * cand_cap * 8);
-    if (use_tab) {
-        FinalizeArgs ft = fa; if (lut32_out) ft.lut32 = lut32_out;
+    if (R.use_tab) {
+        // (the tie scratch is allocated where k_pq_final_tab actually runs, not whenever it is a possible second chance)
+        h->w_tiews.ensure((size_t)nq * R.cand_cap * 8);
+        FinalizeArgs ft = fa; if (lut32_out(h, P)) ft.lut32 = lut32_out(h, P);
         if (h->profile >= 2) {      // diagnostics: how many candidates the 2 eps cut of k_pq_final_tab leaves to the exact re-score
             h->w_flag.ensure(16);
             HIPCHECK(hipMemsetAsync(h->w_flag.p, 0, 16, h->st));
             ft.stat = reinterpret_cast<unsigned long long*>(h->w_flag.p);
         }
-        launch_pq_final_tab(ft, h->w_cand.as<uint64_t>(), cand_cap, h->w_tiews.as<uint64_t>(), h->st);
+        launch_pq_final_tab(ft, h->w_cand.as<uint64_t>(), R.cand_cap, h->w_tiews.as<uint64_t>(), h->st);
         if (h->profile >= 2) {
             unsigned long long v = 0;
             HIPCHECK(hipMemcpyAsync(&v, h->w_flag.p, 8, hipMemcpyDeviceToHost, h->st));
@@ -1108,42 +1095,65 @@ static void search_batch(rsx_index* h, int64_t nq, const void* dq, int dtype, in
     }
     else launch_finalize(fa, h->st);
     tm.mark("finalize");
+}
+// the second chance of rerun_uncertified (flag 1): after the one-launch pre-pass the flagged queries' candidate rows are complete
+static std::function<void()> pq_second_chance(rsx_index* h, const BatchPlan& P, const BatchResult& R, const FinalizeArgs& fa) {
+    if (!(P.fast && R.filtered && R.fused_pre_used && !R.use_tab)) return nullptr;
+    if (R.tab_fits)
+        return [h, P, R, fa]() {       // settle them from there (k_pq_final_tab)
+            h->timing["rescore_all_launches"] += 1;
+            FinalizeArgs fr = fa; fr.row_filter = h->w_uncertain.as<int32_t>();
+            h->w_tiews.ensure((size_t)P.nq * R.cand_cap * 8);
+            launch_pq_final_tab(fr, h->w_cand.as<uint64_t>(), R.cand_cap, h->w_tiews.as<uint64_t>(), h->st);
+        };
+    return [h, P, R, fa]() {
+        // the flagged queries' candidate rows are complete (threshold by construction) and did not overflow: score every
+        // candidate exactly in place, then the best K2 >= k + 64 of them by (exact score, index) go through k_finalize for
+        // the (score, id) order — no certificate needed, no exact scan
+        h->timing["rescore_all_launches"] += 1;
+        FinalizeArgs fr = fa; fr.row_filter = h->w_uncertain.as<int32_t>();
+        launch_pq_rescore_all(fr, h->w_cand.as<uint64_t>(), R.cand_cap, h->st);
+        const int KP2 = std::min(4096, std::max(128, pow2ceil(P.k + 64)));
+        h->w_state2.ensure((size_t)P.nq * KP2 * 8);
+        merge_key_rows(h, h->w_cand.p, h->w_candcnt.as<unsigned long long>(), R.cand_cap, P.nq, nullptr, h->w_state2.as<uint64_t>(),
+                       KP2, 2 * KP2, h->w_uncertain.as<int32_t>());
+        FinalizeArgs f2 = fa;
+        f2.state = h->w_state2.as<uint64_t>(); f2.KP = KP2; f2.row_filter = h->w_uncertain.as<int32_t>(); f2.no_cert = 1;
+        launch_finalize(f2, h->st);
+    };
+}
+// one internal batch: queries -> (coarse quantiser, probes) -> scan -> selection -> finalize -> certificate re-runs
+static void search_batch(rsx_index* h, int64_t nq, const void* dq, int dtype, int k, float* dD, int64_t* dI, bool allow_fast) {
+    StageTimer tm(h, allow_fast ? "" : "fb_");
+    const BatchPlan P = plan_batch(h, nq, dq, dtype, k, allow_fast);
+    tm.mark("start");
+    convert_queries(h, P, dq, dtype, tm);
+    if (P.tab_expected) h->w_lut.ensure((size_t)nq * h->Mpad * 256 * 4);      // (lut32_out)
+    check_supported(h, P);
+    // whatever still throws behind the fork (an allocation) leaves through this guard: the side stream is drained before
+    // the caller can reuse or free the buffers its kernels read and write
+    struct SideJoin { rsx_index* h; bool armed = false; ~SideJoin() { if (armed && h->st2) (void)hipStreamSynchronize(h->st2); } } side_join{h};
+    if (P.side_lut) { fork_side_tables(h, P); side_join.armed = true; }
+    FinalizeArgs fa = finalize_args(h, P, dD, dI);
+    if (h->kind == KIND_FLAT) {
+        flat_scan(h, P, fa, tm);
+        launch_finalize(fa, h->st); tm.mark("finalize"); tm.finish();
+        if (P.certify && h->ntotal > 0) rerun_uncertified(h, nq, dq, dtype, k, dD, dI, (size_t)round_up(h->ntotal, 16) * 4, false);
+        return;
+    }
+    coarse_quantiser(h, P, dq, dtype, tm);
+    if (h->profile >= 2) count_scanned(h, P, tm);
+    if (P.needs_score_rows) h->w_temp.ensure((size_t)nq * P.tmax * 4);
+    BatchResult R;
+    if (h->kind == KIND_IVFPQ) pq_scan(h, P, R, tm);
+    else if (!allow_fast) ivf_flat_exact(h, P, tm);
+    else ivf_flat_scan(h, P, R, tm);
+    select_stage(h, P, R, tm);
+    finalize_stage(h, P, R, fa, tm);
     tm.finish();
     side_join.armed = false;      // st has waited on every side-stream event of this batch
-    std::function<void()> second;
-    if (fast && filtered && fused_pre_used && !use_tab && tabP > 0) {
-        second = [&]() {       // the flagged queries' candidate rows are complete: settle them from there (k_pq_final_tab)
-            h->timing["rescore_all_launches"] += 1;
-            FinalizeArgs fr = fa;
-            fr.row_filter = h->w_uncertain.as<int32_t>();
-            h->w_tiews.ensure((size_t)nq * cand_cap * 8);
-            launch_pq_final_tab(fr, h->w_cand.as<uint64_t>(), cand_cap, h->w_tiews.as<uint64_t>(), h->st);
-        };
-    } else if (fast && filtered && fused_pre_used && !use_tab) {
-        second = [&]() {
-            // the flagged queries' candidate rows are complete (threshold by construction) and did not overflow: score every
-            // candidate exactly in place, then the best K2 >= k + 64 of them by (exact score, index) go through k_finalize for
-            // the (score, id) order — no certificate needed, no exact scan
-            h->timing["rescore_all_launches"] += 1;
-            FinalizeArgs fr = fa;
-            fr.row_filter = h->w_uncertain.as<int32_t>();
-            launch_pq_rescore_all(fr, h->w_cand.as<uint64_t>(), cand_cap, h->st);
-            const int KP2 = std::min(4096, std::max(128, pow2ceil(k + 64)));
-            h->w_state2.ensure((size_t)nq * KP2 * 8);
-            SelectArgs b{};
-            b.in = h->w_cand.p; b.in_is_keys = 1; b.row_stride = cand_cap;
-            b.row_n = reinterpret_cast<const int64_t*>(h->w_candcnt.p); b.row_n_stride = CCS; b.n_uniform = cand_cap;
-            b.seg_len = round_up(cand_cap, 256); b.nseg = 1; b.idx_base = 0;
-            b.init = nullptr; b.out = h->w_state2.as<uint64_t>(); b.out_row_stride = KP2;
-            b.nrows = nq; b.KP = KP2; b.BUF = 2 * KP2; b.k = KP2;
-            b.row_filter = h->w_uncertain.as<int32_t>();
-            launch_select(b, h->st);
-            FinalizeArgs f2 = fa;
-            f2.state = h->w_state2.as<uint64_t>(); f2.KP = KP2; f2.row_filter = h->w_uncertain.as<int32_t>(); f2.no_cert = 1;
-            launch_finalize(f2, h->st);
-        };
-    }
-    if (fast || certify) rerun_uncertified(h, nq, dq, dtype, k, dD, dI, (size_t)tmax * 4, second);     // the re-run fills score rows: chunked by the budget
+    // (the re-run fills score rows: chunked by the budget; the fast coarse quantiser's flags are this batch's)
+    if (P.fast || P.certify) rerun_uncertified(h, nq, dq, dtype, k, dD, dI, (size_t)P.tmax * 4, P.coarse_fast, pq_second_chance(h, P, R, fa));
 }
 
 // L2 ranking bias  -|x|^2/2  from the stored squared norms
@@ -1202,25 +1212,13 @@ void search_impl(rsx_index* h, int64_t nq, const void* q, int dtype, int k, floa
         hipLaunchKernelGGL(k_bias_from_norms, dim3((unsigned)((rows + 255) / 256)), dim3(256), 0, h->st, h->norms.as<float>(),
                            h->w_misc.as<float>(), rows);
     }
-    // A filtered search takes the routes whose scans write complete score rows: the in-scan candidate filters (Flat staged
-    // GEMM, IVF-Flat filtered list scan, IVF-PQ threshold pre-pass + filtered scans) are off for the call, restored on any exit
-    struct RouteOverride {
-        rsx_index* h; int ff, iff, pf;
-        explicit RouteOverride(rsx_index* hh) : h(hh), ff(hh->flat_filter), iff(hh->ivf_filter), pf(hh->pq_filter) {
-            if (h->sel) { h->flat_filter = 0; h->ivf_filter = 0; h->pq_filter = 0; }
-        }
-        ~RouteOverride() { h->flat_filter = ff; h->ivf_filter = iff; h->pq_filter = pf; }
-    } route_override(h);
     if (h->sel) ensure_sel_mask(h);
-    // batch size: bounded by the knob and by the score-buffer budget
+    // batch size: bounded by the knob and by the score-buffer budget (the plan's row sizes depend on neither nq nor the query buffer)
     int64_t qb = std::max(1, h->query_batch);
     if (h->kind != KIND_FLAT) {
-        const int nprobe = std::min(h->nprobe, h->nlist);
-        const int pad_to = (h->kind == KIND_IVFPQ) ? 64 : 16;
-        int64_t tmax = top_probe_sum(h, nprobe, pad_to, pad_to).first;
-        tmax = std::max<int64_t>(round_up(tmax, 256), 256);
-        if (h->sel || pq_search_needs_score_rows(h, nprobe, k)) qb = std::max<int64_t>(1, std::min<int64_t>(qb, h->temp_budget / (tmax * 4)));
-        else qb = std::max<int64_t>(1, std::min<int64_t>(qb, h->temp_budget / (pq_cand_cap(k, h->M) * 16)));      // candidate row + tie scratch
+        const BatchPlan P = plan_batch(h, nq, nullptr, dtype, k, true);
+        if (P.needs_score_rows) qb = std::max<int64_t>(1, std::min<int64_t>(qb, h->temp_budget / (P.tmax * 4)));
+        else qb = std::max<int64_t>(1, std::min<int64_t>(qb, h->temp_budget / (cand_row_cap(k, h->M) * 16)));      // candidate row + tie scratch
     } else if (nq <= 32) {
         qb = 32;
     }

@@ -199,7 +199,6 @@ struct rsx_index {
     uint64_t cent_gen = 0, cent16_gen = 0;   // set_centroids counts; the copy belongs to cent16_gen
     float cent_cmax = 0.0f;   // >= the largest centroid norm (with the copy)
     int coarse_fast = 1;      // coarse quantiser: fp16 MFMA scores + exact re-score of the candidates (k_coarse_pick), 0 = the exact GEMM for all lists
-    bool coarse_flags_live = false;   // this batch's k_coarse_pick wrote per-query flags behind w_uncertain's
 
     // storage.  PQ: slab layout bytes.  Flat/IVFFlat: rows of ld elements (fp16 or fp32).
     int ld = 0;               // row stride (elements) of flat rows: d rounded up to 64
