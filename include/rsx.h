@@ -256,6 +256,27 @@ int rsx_search_sel(rsx_index_t* h, int64_t nq, const void* q, int dtype, int k, 
 int rsx_search_prepass_sel(rsx_index_t* h, int64_t nq, const void* q, int dtype, int k, const rsx_selector_t* sel,
                            int nprobe_override, float* D, int64_t* I, uint64_t** tau_dev, int64_t* ntau);
 
+/* ---- removal (FAISS Index::remove_ids) --------------------------------------------- */
+
+/* index.remove_ids(sel) -> number of vectors removed (*nremoved), FAISS 1.8.0 semantics:
+ *   IVF-Flat / IVF-PQ  IndexIVF::remove_ids -> DirectMap::remove_ids (NoMap): per list, each removed entry j takes the
+ *                      list's last entry (j = 0, l = len; while j < l: if sel(ids[j]) entry[j] = entry[--l] else j++) —
+ *                      the in-list order get_list and write_index see is the one FAISS leaves;
+ *   Flat               IndexFlatCodes::remove_ids: sel tests the POSITION, the kept rows are compacted in order and the ids
+ *                      renumbered 0 .. ntotal - 1;  Flat with explicit ids (IndexIDMap::remove_ids): sel tests the stored
+ *                      id, rows and ids are compacted in order.
+ * Later adds without ids number from the new ntotal, as in FAISS; on an IVF index those ids can equal surviving ones (FAISS
+ * behaves the same way).  Trained parameters, list capacities and the storage dtype do not change; the vacated slots are
+ * reset to zero bytes.  Removing nothing returns 0 and leaves the index untouched.  Runs on the GPU: slot mask (k_sel_mask),
+ * per-list plan and one in-place move pass (IVF) or a stable compaction staged through at most max(256 MiB, payload / 16)
+ * of device memory (Flat); rsx_get_timing "remove_calls", "removed", "remove_ms" (host wall time).
+ * The reference drops documents after every search instead — subsampling (src/search.py:493-500) and decontamination /
+ * short chunks (src/search.py:519-527): removing them once keeps all n_docs slots for the remaining documents.
+ * Sharded handles (rsx_sharded_create / rsx_load_sharded) remove on every shard in parallel: IVF kinds, and Flat when its
+ * adds carried ids.  Refused (RSX_ERR_UNSUPPORTED): a sharded Flat handle of sequential ids (faiss.IndexShards has no
+ * remove_ids), a list shard ("add_list_mod" > 1).  Refused (RSX_ERR_INVALID): NULL arguments, an open two-call search. */
+int rsx_remove_ids(rsx_index_t* h, const rsx_selector_t* sel, int64_t* nremoved);
+
 /* ---- persistence ------------------------------------------------------------------- */
 
 /* faiss.write_index(index, path) / faiss.read_index(path)

@@ -78,6 +78,7 @@ void sharded_add(rsx_index* h, int64_t n, const void* x, int dtype, const int64_
     });
     h->ntotal += n;
     if (!ids) h->sh_next_id += n;
+    else if (h->kind == KIND_FLAT) h->custom_ids = true;      // (rsx_remove_ids: a Flat handle of explicit ids can remove per shard)
 }
 
 void sharded_search(rsx_index* h, int64_t nq, const void* q, int dtype, int k, float* D, int64_t* I) {
@@ -173,7 +174,7 @@ void sharded_reserve(rsx_index* h, const int64_t* counts) {      // exact when e
 void sharded_save(rsx_index* h, const char* path) {
     FILE* f = fopen(path, "wb");
     if (!f) RSX_THROW(RSX_ERR_IO, "cannot open %s for writing", path);
-    int32_t hdr[4] = {0, 1, (int32_t)h->shards.size(), 0};
+    int32_t hdr[4] = {0, 1, (int32_t)h->shards.size(), h->custom_ids ? 1 : 0};     // hdr[3]: a Flat handle of explicit ids
     memcpy(hdr, "RSXS", 4);
     int64_t next = h->sh_next_id;
     bool ok = fwrite(hdr, 1, sizeof(hdr), f) == sizeof(hdr) && fwrite(&next, 1, 8, f) == 8;
@@ -294,7 +295,7 @@ rsx_index* sharded_load(const char* path, int ndev, const int* devices) {
     rsx_index* c0 = p->shards[0];
     p->kind = c0->kind; p->d = c0->d; p->metric = c0->metric; p->device = c0->device;
     p->nlist = c0->nlist; p->M = c0->M; p->nbits = c0->nbits; p->Mpad = c0->Mpad; p->CB = c0->CB; p->dsub = c0->dsub; p->ld = c0->ld;
-    p->trained = c0->trained; p->nprobe = c0->nprobe; p->sh_next_id = next;
+    p->trained = c0->trained; p->nprobe = c0->nprobe; p->sh_next_id = next; p->custom_ids = hdr[3] != 0;
     for (auto* c : p->shards) p->ntotal += c->ntotal;
     HIPCHECK(hipSetDevice(p->device));
     HIPCHECK(hipStreamCreateWithFlags(&p->st, hipStreamNonBlocking));

@@ -60,7 +60,7 @@ static int search_prepass_common(rsx_index_t* h, int64_t nq, const void* q, int 
 extern "C" {
 
 const char* rsx_last_error(void) { return g_err.c_str(); }
-int rsx_version(void) { return 1001; }     // 1001: filtered search (rsx_selector_*, rsx_search_sel, rsx_search_prepass_sel)
+int rsx_version(void) { return 1002; }     // 1001: filtered search (rsx_selector_*, rsx_search_sel, rsx_search_prepass_sel); 1002: rsx_remove_ids
 
 int rsx_device_count(int* n) {
     return guarded([&] {
@@ -325,6 +325,17 @@ int rsx_search_sel(rsx_index_t* h, int64_t nq, const void* q, int dtype, int k, 
     });
 }
 
+int rsx_remove_ids(rsx_index_t* h, const rsx_selector_t* sel, int64_t* nremoved) {
+    return guarded([&] {
+        if (!h || !sel || !nremoved) RSX_THROW(RSX_ERR_INVALID, "null pointer");
+        refuse_while_two_call(h, "remove_ids");
+        *nremoved = 0;
+        if (is_sharded(h)) { *nremoved = sharded_remove(h, sel); return; }
+        use_device(h);
+        *nremoved = remove_impl(h, sel);
+    });
+}
+
 static std::atomic<uint64_t> g_sel_serial{0};
 int rsx_selector_create(int kind, const void* data, int64_t n, int64_t lo, int64_t hi, int invert, rsx_selector_t** out) {
     return guarded([&] {
@@ -542,7 +553,7 @@ int rsx_get_timing(rsx_index_t* h, const char* key, double* ms) {
         if (is_sharded(h)) {     // stage times: the slowest shard; counters: the sum
             *ms = 0.0;
             const std::string ks(key);
-            const bool sum = ks.find("queries") != std::string::npos || ks.find("launches") != std::string::npos || ks.find("vectors") != std::string::npos;
+            const bool sum = ks.find("queries") != std::string::npos || ks.find("launches") != std::string::npos || ks.find("vectors") != std::string::npos || ks == "removed";
             for (auto* c : h->shards) { auto it = c->timing.find(key); double v = it == c->timing.end() ? 0.0 : it->second; *ms = sum ? *ms + v : std::max(*ms, v); }
             return;
         }

@@ -3,6 +3,7 @@
 //   api_build.hip    HBM layout management, add / train, list import / export, persistence
 //   api_search.hip   the search drivers (search_batch = one internal batch, search_impl = one rsx_search call)
 //   api_sharded.hip  the single-process multi-GPU handle
+//   api_remove.hip   rsx_remove_ids: the removal plan and compaction (k_remove.hip) on a handle and on the shards of one
 //   rsx_api.hip      the extern "C" entry points
 // Host control plane only; all search arithmetic is in the k_*.hip kernels.  There is no CPU search path.
 #pragma once
@@ -204,7 +205,8 @@ struct rsx_index {
     int ld = 0;               // row stride (elements) of flat rows: d rounded up to 64
     int storage_f16 = 1;
     bool storage_decided = false;
-    bool custom_ids = false;  // Flat: ids array only when the caller supplied ids
+    bool custom_ids = false;  // Flat: ids array only when the caller supplied ids (sharded Flat handle: its adds carried ids; the shards
+                              // always store the logical ids)
     DevBuf data, ids, norms;
     DevBuf codes_plain;               // IVF-PQ, block layouts: row-major copy of the codes for large-K' finalizes, built on demand (api_search.hip)
     uint64_t plain_gen = ~0ull; const void* plain_of = nullptr;
@@ -352,6 +354,26 @@ void sharded_reserve(rsx_index* h, const int64_t* counts);
 void sharded_save(rsx_index* h, const char* path);
 void destroy_handle(rsx_index* h);
 rsx_index* sharded_load(const char* path, int ndev, const int* devices);
+int64_t remove_impl(rsx_index* h, const rsx_selector* s);
+int64_t sharded_remove(rsx_index* h, const rsx_selector* s);
+
+// k_remove.hip: the removal kernels (mask: k_sel_mask, bit s = slot s is removed; slots of the moves are uint32: < 2^32 storage rows)
+namespace rsx {
+void launch_rm_ivf_plan_counts(const uint32_t* mask, const int64_t* base, const int64_t* len, int nlist, int64_t* new_len, int64_t* nmoves,
+                               int64_t* move_off /* [nlist + 1] */, hipStream_t st);
+void launch_rm_ivf_plan_moves(const uint32_t* mask, const int64_t* base, const int64_t* len, const int64_t* new_len, const int64_t* nmoves,
+                              const int64_t* move_off, int nlist, uint32_t* move_src, uint32_t* move_dst, hipStream_t st);
+void launch_rm_ivf_move(const uint32_t* move_src, const uint32_t* move_dst, const int64_t* nmoves_total, int64_t max_moves, uint8_t* data,
+                        int64_t row_bytes, int pq, int Mpad, int CB, int64_t* ids, float* norms, hipStream_t st);
+void launch_rm_clear(const int64_t* runs /* [nruns][first slot, count <= 256] */, int64_t nruns, uint8_t* data, int64_t row_bytes, int pq,
+                     int Mpad, int CB, int64_t* ids, float* norms, hipStream_t st);
+int64_t rm_flat_blocks(int64_t n);      // Flat: scan blocks of rm_flat_unit() slots
+int64_t rm_flat_unit();
+void launch_rm_flat_scan(const uint32_t* mask, int64_t n, int32_t* word_pre /* [ceil(n / 32)] */, int64_t* blk_cnt /* [blocks] */,
+                         int64_t* blk_off /* [blocks + 1] */, hipStream_t st);
+void launch_rm_flat_chunk(const uint32_t* mask, const int32_t* word_pre, const int64_t* blk_off, int64_t lo, int64_t hi, uint8_t* data,
+                          int64_t row_bytes, int64_t* ids, float* norms, uint8_t* stage, int64_t* stage_ids, float* stage_norms, hipStream_t st);
+}  // namespace rsx
 
 static inline bool is_sharded(const rsx_index* h) { return !h->shards.empty(); }
 

@@ -43,6 +43,7 @@ ABI_SYMBOLS = [
     "rsx_set_param",
     "rsx_get_timing", "rsx_save", "rsx_load", "rsx_synth_vectors", "rsx_synth_queries",
     "rsx_selector_create", "rsx_selector_destroy", "rsx_selector_is_member", "rsx_search_sel", "rsx_search_prepass_sel",
+    "rsx_remove_ids",
 ]
 
 
@@ -323,6 +324,20 @@ class IDSelectorNot(IDSelector):
         return IDSelectorNot(self.sel.shifted(offset, None)) if offset else self
 
 
+def _remove_selector(x):
+    """Index.remove_ids argument -> IDSelector: a selector as is, a 1-D integer array as IDSelectorBatch(x)."""
+    if isinstance(x, IDSelector):
+        return x
+    if _is_torch(x):
+        x = x.detach().cpu().numpy()
+    a = np.asarray(x)
+    if a.ndim != 1:
+        raise ValueError(f"remove_ids: expected an IDSelector or a 1-D array of ids, got an array of shape {a.shape}")
+    if a.size and not np.issubdtype(a.dtype, np.integer):
+        raise TypeError(f"remove_ids: ids must be integers, got {a.dtype}")
+    return IDSelectorBatch(a.astype(np.int64))
+
+
 class SearchParameters:
     """faiss.SearchParameters(sel=None): per-call parameters of Index.search (Flat)."""
 
@@ -435,6 +450,15 @@ class Index:
         ids = np.ascontiguousarray(ids, dtype=np.int64)
         assert ids.shape == (n,), "ids must have one entry per vector"
         _check(lib().rsx_add(self._h, ctypes.c_int64(n), p, dt, ids.ctypes.data_as(ctypes.c_void_p)))
+
+    def remove_ids(self, x):
+        """faiss.Index.remove_ids(x) -> int, the number of vectors removed.  x: an IDSelector, or a 1-D integer array of ids (made
+        an IDSelectorBatch, as FAISS's replacement_remove_ids does; duplicates and absent ids are allowed).  IVF lists fill each
+        hole with their last entry (FAISS's in-list order); Flat compacts in order, renumbering sequential ids (rsx_remove_ids)."""
+        sel = _remove_selector(x)
+        n = ctypes.c_int64(0)
+        _check(lib().rsx_remove_ids(self._h, sel._native(), ctypes.byref(n)))
+        return int(n.value)
 
     def search(self, x, k, *, params=None):
         """-> (D float32 [n,k], I int64 [n,k]); numpy in -> numpy out, CUDA tensor in -> CUDA tensors out.
