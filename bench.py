@@ -4,17 +4,21 @@
 Workload (BASELINE.json metric / configs[3]): 100M x 768 IVF-PQ, M = 96, nbits = 8, nlist = 4096,
 nprobe = 32, batch = 1024 queries, k = 10, synthetic Gaussian-mixture fp16 embeddings.
 One "step" = one rsx_search call over one batch of 1024 queries that is already resident in HBM,
-results left in HBM (`value`); the same loop with host-resident queries/results is reported beside it as
-`pcie_inclusive`, never as `value`.
+results left in HBM (`value`); with --full the same loop with host-resident queries/results is reported beside it
+as `pcie_inclusive`, never as `value`.
 
-At N = 1 the line also carries (rank 0, after the timed region, each on its own index): `configs` = BASELINE configs 2
-and 3 (Flat 10M batch 1024; IVF-Flat 100M nlist 4096 nprobe 32) with ms/step, roofline and an oracle spot check,
-`recall_informative` = recall@10 on a second mixture whose neighbours PQ can resolve, the list-length histogram and
-the CPU baseline (the oracle on all host cores, all 1024 queries, three repeats).  --no-configs / --cpu-queries 0 /
---no-recall switch the extras off for experiments.
+A plain run builds the index, warms up, times the K steps and prints the headline line (metric, value, unit, ms_per_step,
+dtype, the workload) and nothing else.  --full adds everything else after the timed region: recall@10 against an exact
+streaming ground truth (built beside the index), the per-stage breakdown, roofline, the host-resident and one-call loops,
+the first timed batch's sha256, and at N = 1 (rank 0, each on its own index): `configs` = BASELINE configs 2 and 3 (Flat
+10M batch 1024; IVF-Flat 100M nlist 4096 nprobe 32) with ms/step, roofline and an oracle spot check, `recall_informative`
+= recall@10 on a second mixture whose neighbours PQ can resolve, the list-length histogram and the CPU baseline (the
+oracle on all host cores, all 1024 queries, three repeats).  Within --full, --no-configs / --cpu-queries 0 / --no-recall
+switch extras off for experiments.
 
   python bench.py --gpus 1 --steps 10 --warmup 3
   python bench.py --gpus 1 --steps 10 --warmup 3 --dump-outputs DIR     # + the last timed step's D / I as DIR/*.npy
+  python bench.py --gpus 1 --steps 10 --warmup 3 --full                 # + recall, stages, roofline, configs, baselines
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
          bench.py --gpus N --steps K --warmup W
 
@@ -60,10 +64,14 @@ def main():
     ap.add_argument("--batch", type=int, default=1024)
     ap.add_argument("--k", type=int, default=10)
     ap.add_argument("--chunk", type=int, default=1_000_000, help="vectors synthesised per add call")
-    ap.add_argument("--cpu-queries", type=int, default=1024, help="queries timed on the CPU baseline (0 = skip)")
-    ap.add_argument("--no-recall", action="store_true", help="skip the exact ground truth (recall = null)")
-    ap.add_argument("--no-configs", action="store_true", help="skip BASELINE configs 2/3 and the second recall figure")
-    ap.add_argument("--no-faiss", action="store_true", help="skip the opportunistic FAISS leg (it only runs when `import faiss` works)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also measure and check everything beside the headline: recall (exact ground truth "
+                         "streamed during the add), stages, roofline, host-resident and one-call loops, other k, distributions, "
+                         "BASELINE configs, CPU and FAISS baselines")
+    ap.add_argument("--cpu-queries", type=int, default=1024, help="--full: queries timed on the CPU baseline (0 = skip)")
+    ap.add_argument("--no-recall", action="store_true", help="--full: skip the exact ground truth (recall = null)")
+    ap.add_argument("--no-configs", action="store_true", help="--full: skip BASELINE configs 2/3 and the second recall figure")
+    ap.add_argument("--no-faiss", action="store_true", help="--full: skip the opportunistic FAISS leg (it only runs when `import faiss` works)")
     ap.add_argument("--diag", action="store_true", help="print a fast-vs-exact comparison of the first timed batch and exit")
     ap.add_argument("--shard", choices=["vectors", "lists"], default="vectors",
                     help="multi-GPU partition of the index: by contiguous id ranges (the reference's shards; default) or by "
@@ -71,7 +79,7 @@ def main():
                          "two calls of the search, see DESIGN.md section 6)")
     ap.add_argument("--param", action="append", default=[], metavar="NAME=VALUE",
                     help="engine parameter for an experiment (rsx_set_param), e.g. pq_filter=0; not for the reported line")
-    ap.add_argument("--ab", action="store_true", help="also time the per-pair v1 scan kernel (same process, same index)")
+    ap.add_argument("--ab", action="store_true", help="--full: also time the per-pair v1 scan kernel (same process, same index)")
     ap.add_argument("--dist-backend", choices=["nccl", "gloo"], default="nccl",
                     help="torch.distributed backend for N > 1: nccl (= RCCL over xGMI, the default) or gloo (the same collectives routed "
                          "through the host — what lets N ranks share one GPU in the dry-run test; RCCL refuses two ranks per device)")
@@ -87,6 +95,8 @@ def main():
     args = ap.parse_args()
     if args.steps < 1 or args.warmup < 0:
         ap.error("--steps must be >= 1 and --warmup >= 0")
+    if args.ab and not args.full:
+        ap.error("--ab runs after the timed steps: it needs --full")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(self_launch(args.gpus))
@@ -182,7 +192,7 @@ def main():
     # ---------------- add (+ streaming exact ground truth with the Flat engine)
     t0 = time.time()
     buf = torch.empty((args.chunk, D), dtype=torch.float16, device=dev)
-    flat = None if args.no_recall else rsx.IndexFlatIP(D, device=local_rank)
+    flat = None if args.no_recall or not args.full else rsx.IndexFlatIP(D, device=local_rank)
     gtD = gtI = None
     if list_shards:   # every rank streams the whole id range through add (assignment + its own lists' codes)
         for c0 in range(0, n_total, args.chunk):
@@ -302,8 +312,46 @@ def main():
         scan_ms = index.get_timing("scan")
         scan_launches = index.get_timing("scan_launches")
         stages_in_timed_region = True
+    if world > 1:
+        t = torch.tensor([elapsed], dtype=torch.float64, device="cpu" if on_host else dev)
+        dist.all_reduce(t, op=dist.ReduceOp.MAX)
+        elapsed = float(t.item())
     # what the last timed step returned, to the host now: the passes below search the same batches again
     last_out = (out[0].cpu().numpy(), out[1].cpu().numpy()) if args.dump_outputs and rank == 0 else None
+    layout = index._get("pq_layout")                              # 2 = sliced (M = 96 default), 1 = rotated, 0 = granule
+    line = {
+        "metric": "queries/sec + recall@10, 100M x 768 IVF-PQ nprobe=32 batch=1024",
+        "value": round(args.steps * nq / elapsed, 2),
+        "unit": "queries/s",
+        "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+        "ms_per_step": round(elapsed / args.steps * 1e3, 4),
+        "higher_is_better": True,
+        "scaling": args.scaling if world > 1 else "strong",
+        "vs_baseline": None,
+        "dtype": "u8 codes; i8-table integer scan (MFMA-i8 adder tree), exact f32-table re-rank (certified)",
+        "data": "synthetic",
+        "config": {"workload": f"{n_total}x{D} IVF-PQ M={args.m} nbits=8 nlist={args.nlist} nprobe={args.nprobe} "
+                               f"batch={nq} k={k}, inner product, by_residual",
+                   "vectors_per_gpu": n_local, "code_layout": {2: "sliced", 1: "rotated"}.get(layout, "granule"),
+                   "parallelism": (f"index sharded by inverted lists (l % {world} == rank) over {world} GPU(s)" if list_shards
+                                   else f"index sharded by id range over {world} GPU(s)"),
+                   "dist_backend": (args.dist_backend if world > 1 else None)},
+        "settle_batches": SETTLE,
+    }
+
+    def finish(res):                   # rank 0 prints the line and dumps the last timed step's result
+        if rank == 0:
+            print(json.dumps(res), flush=True)
+            if last_out is not None:
+                dump_outputs(args.dump_outputs, *last_out)
+        if world > 1:
+            dist.barrier()
+            dist.destroy_process_group()
+
+    if not args.full:
+        finish(line)
+        return
+
     fallbacks_timed = index.get_timing("fallback_queries") / max(1.0, index.get_timing("fast_queries"))
     if not stages_in_timed_region:
         index.set_param("profile", 1)
@@ -313,10 +361,6 @@ def main():
         barrier()
     stage_ms = {s: round(index.get_timing(s) / args.steps, 4) for s in
                 ("convert", "coarse", "select_probe", "lut", "lut8", "group", "scan0", "select0", "scan", "select", "finalize", "total")}
-    if world > 1:
-        t = torch.tensor([elapsed], dtype=torch.float64, device="cpu" if on_host else dev)
-        dist.all_reduce(t, op=dist.ReduceOp.MAX)
-        elapsed = float(t.item())
     fallbacks = fallbacks_timed
     index.set_param("profile", 0)
     if searcher is not None:           # the exchange of this rank (rank 0's are printed): where a multi-GPU step's time goes beside the search
@@ -386,7 +430,6 @@ def main():
     launches_per_step = max(1.0, scan_launches / args.steps)
     ms_per_launch = scan_ms / max(1.0, scan_launches)
     sec = ms_per_launch * 1e-3
-    layout = index._get("pq_layout")                              # 2 = sliced (M = 96 default), 1 = rotated, 0 = granule
     rot = layout in (1, 2)
     kernel = "k_pq_scan_sl8" if layout == 2 else "k_pq_scan_rot" if rot else "k_pq_scan8"
 
@@ -597,26 +640,11 @@ def main():
                       "cu (lds gather issue): one instruction per 4-clock issue turn on every SIMD, LDS 0.61, MFMA 0.30 busy "
                       "(profiles/r05_scan_plateau.md)" if kernel == "k_pq_scan_rot" else "lds bank conflicts (granule layout)")
         res = {
-            "metric": "queries/sec + recall@10, 100M x 768 IVF-PQ nprobe=32 batch=1024",
-            "value": round(args.steps * nq / elapsed, 2),
-            "unit": "queries/s",
-            "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-            "ms_per_step": round(elapsed / args.steps * 1e3, 4),
-            "higher_is_better": True,
-            "scaling": args.scaling if world > 1 else "strong",
-            "vs_baseline": None,
-            "dtype": "u8 codes; i8-table integer scan (MFMA-i8 adder tree), exact f32-table re-rank (certified)",
-            "data": "synthetic",
+            **line,
             "recall_at_10": recall,
             "first_timed_batch_sha256": result_sha,
             "recall_low_noise_queries": recall_low,
             "recall_informative": recall2,
-            "config": {"workload": f"{n_total}x{D} IVF-PQ M={args.m} nbits=8 nlist={args.nlist} nprobe={args.nprobe} "
-                                   f"batch={nq} k={k}, inner product, by_residual",
-                       "vectors_per_gpu": n_local, "code_layout": {2: "sliced", 1: "rotated"}.get(layout, "granule"),
-                       "parallelism": (f"index sharded by inverted lists (l % {world} == rank) over {world} GPU(s)" if list_shards
-                                       else f"index sharded by id range over {world} GPU(s)"),
-                       "dist_backend": (args.dist_backend if world > 1 else None)},
             "roofline": {"bound": "hbm" if kernel != "k_pq_scan_rot" else "cu (lds gather issue)", "bound_by_counters": bound_note, "kernel": kernel, "achieved": round(achieved, 2), "peak": HBM_PEAK_GBS,
                          "unit": "GB/s", "frac": round(achieved / HBM_PEAK_GBS, 4), "traffic": traffic,
                          "algorithmic_bytes_per_launch": alg_bytes, "ms_per_launch": round(ms_per_launch, 4),
@@ -644,7 +672,6 @@ def main():
             "pcie_inclusive": pcie,
             "one_call_all_queries": one_call,
             "list_length_histogram": hist,
-            "settle_batches": SETTLE,
             "stage_ms_per_step": stage_ms,
             "stage_ms_note": ("stages marked inside the timed region (profile 1)" if stages_in_timed_region else
                               "the timed region carries HIP events around the scan launch only (profile -1: roofline.ms_per_launch); this per-stage breakdown is a "
@@ -659,12 +686,7 @@ def main():
             "cpu_parity_ids_and_scores_bit_exact": parity,
             "faiss_baseline": faiss_res,
         }
-        print(json.dumps(res), flush=True)
-        if last_out is not None:
-            dump_outputs(args.dump_outputs, *last_out)
-    if world > 1:
-        dist.barrier()
-        dist.destroy_process_group()
+    finish(res if rank == 0 else None)
 
 
 def dump_outputs(path, D, I, seed=0):

@@ -69,6 +69,12 @@ def test_bench_refuses_zero_timed_steps():
     assert r.returncode == 2 and "--steps must be >= 1" in r.stderr, r.stderr
 
 
+def test_bench_refuses_ab_without_full():
+    """--ab times other kernels after the timed steps, which only a --full run goes on to."""
+    r = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--ab"], capture_output=True, text=True, timeout=120)
+    assert r.returncode == 2 and "needs --full" in r.stderr, r.stderr
+
+
 def test_dump_outputs_writes_the_step_result(tmp_path, monkeypatch):
     """bench.py --dump-outputs: scores as float32, ids as float64, every query row of a small result; a result over the byte
     cap keeps the same seeded sample of rows every time, under the cap."""

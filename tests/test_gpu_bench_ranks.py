@@ -27,10 +27,11 @@ COMMON = ["--n", "1600000", "--nlist", "256", "--chunk", "200000", "--steps", "2
 MAX_RANKS = 4
 
 
-def _run(extra):
+def _run(extra, full=True):
     env = dict(os.environ)
     env.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
-    p = subprocess.run([sys.executable, os.path.join(REPO, "bench.py")] + COMMON + extra, capture_output=True, text=True, timeout=900, env=env)
+    p = subprocess.run([sys.executable, os.path.join(REPO, "bench.py")] + COMMON + (["--full"] if full else []) + extra,
+                       capture_output=True, text=True, timeout=900, env=env)
     assert p.returncode == 0, f"bench.py {extra} failed:\n{p.stderr[-3000:]}"
     lines = [l for l in p.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1, f"expected ONE JSON line from rank 0, got {len(lines)}:\n{p.stdout[-2000:]}"
@@ -48,7 +49,7 @@ def _run_ranks(n, extra, tmp_path):
         env = dict(os.environ, WORLD_SIZE=str(n), RANK=str(r), LOCAL_RANK=str(r), MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port))
         env.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
         out, err = open(tmp_path / f"rank{r}.out", "w"), open(tmp_path / f"rank{r}.err", "w")
-        procs.append(subprocess.Popen([sys.executable, os.path.join(REPO, "bench.py")] + COMMON + extra +
+        procs.append(subprocess.Popen([sys.executable, os.path.join(REPO, "bench.py")] + COMMON + ["--full"] + extra +
                                       ["--gpus", str(n), "--share-gpu", "--dist-backend", "gloo"], stdout=out, stderr=err, env=env))
         out.close(); err.close()
     try:
@@ -124,3 +125,28 @@ def test_dump_outputs_is_the_timed_result(gpu, single, tmp_path):
     _run(["--steps", "1", "--dump-outputs", str(tmp_path / "again")])
     for f in ("scores.npy", "ids.npy", "rows.npy"):
         assert np.array_equal(np.load(tmp_path / "one" / f), np.load(tmp_path / "again" / f)), f
+
+
+HEADLINE = {"metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline", "dtype",
+            "data", "config", "settle_batches"}
+
+
+@pytest.mark.parametrize("ngpu", [1, 2])
+def test_plain_run_prints_the_headline_of_the_same_steps(gpu, single, ngpu, tmp_path):
+    """Without --full the line holds the headline keys only, each meaning what it means in a --full line, and the last timed
+    step returns what it returns there: at --steps 1 the first timed batch, whose sha256 the --full line reports."""
+    import hashlib
+    import numpy as np
+    extra = ["--steps", "1", "--dump-outputs", str(tmp_path / "plain")]
+    if ngpu > 1:
+        extra += ["--gpus", str(ngpu), "--share-gpu", "--dist-backend", "gloo"]
+    r = _run(extra, full=False)
+    assert set(r) == HEADLINE, sorted(set(r) ^ HEADLINE)
+    assert r["n_gpus"] == ngpu and r["steps"] == 1 and r["warmup"] == 1
+    for key in ("metric", "unit", "higher_is_better", "scaling", "vs_baseline", "dtype", "data", "settle_batches"):
+        assert r[key] == single[key], key
+    assert r["config"]["workload"] == single["config"]["workload"]
+    assert abs(r["value"] - 1024 / (r["ms_per_step"] * 1e-3)) / r["value"] < 0.01
+    D = np.load(tmp_path / "plain" / "scores.npy")
+    I = np.load(tmp_path / "plain" / "ids.npy")
+    assert hashlib.sha256(D.tobytes() + I.astype(np.int64).tobytes()).hexdigest() == single["first_timed_batch_sha256"]

@@ -4,7 +4,7 @@
 #   env        box facts (GPU, cores, RAM, import faiss)
 #   tests      pytest -m gpu (stop at first failure; PYTEST_ARGS narrows it)     tests_all: without -x
 #   smoke      __graft_entry__.smoke()
-#   bench      the default bench line (all configs)                               bench_fast: headline only
+#   bench      the --full bench line (all configs)                                bench_fast: --full without configs, recall, CPU baseline
 #   prof       rocprofv3 --kernel-trace --stats of the headline bench  -> ${TAG}_rocprof_stats_ivfpq100M.md + ${TAG}_timeline.md (last batch)
 #   pmc_fetch  FETCH_SIZE pass -> ${TAG}_pmc_fetch_size.md + stamped pmc_traffic.json
 #   stamp      copy the pmc_fetch stage's pmc_traffic.json over profiles/pmc_traffic.json ON THE BOX, so that a later bench stage of the same call reads it
@@ -23,7 +23,7 @@ mkdir -p gpurun_out
 export TMPDIR=/tmp
 TAG=${TAG:-r06}
 O=$PWD/gpurun_out
-FAST="--cpu-queries 0 --no-recall --no-configs"
+FAST="--full --cpu-queries 0 --no-recall --no-configs"
 for s in "$@"; do
   case $s in
     env)
@@ -37,7 +37,7 @@ for s in "$@"; do
     smoke)
       timeout 600 python -c "import __graft_entry__ as g; g.smoke()" > $O/${TAG}_smoke.log 2>&1; echo "smoke exit $?" >> $O/${TAG}_smoke.log ;;
     bench)
-      timeout 1500 python bench.py --steps ${STEPS:-20} --warmup 5 ${BENCH_ARGS:-} > $O/${TAG}_bench_ivfpq100M.json 2> $O/${TAG}_bench.log; echo "exit $?" >> $O/${TAG}_bench.log ;;
+      timeout 1500 python bench.py --full --steps ${STEPS:-20} --warmup 5 ${BENCH_ARGS:-} > $O/${TAG}_bench_ivfpq100M.json 2> $O/${TAG}_bench.log; echo "exit $?" >> $O/${TAG}_bench.log ;;
     bench_fast)
       timeout 600 python bench.py --steps ${STEPS:-20} --warmup 5 $FAST ${BENCH_ARGS:-} > $O/${TAG}_bench_fast.json 2> $O/${TAG}_bench_fast.log; echo "exit $?" >> $O/${TAG}_bench_fast.log
       python tools/show_bench.py $O/${TAG}_bench_fast.json ;;

@@ -26,7 +26,7 @@ kernel = "k_pq_scan_sl8" if "k_pq_scan_sl8" in name else "k_pq_scan_rot" if "k_p
 res = {"kernel": kernel, "kernel_name": name.split("(")[0].replace("void ", ""), "n": n, "n_gpus": ng,
        "hbm_bytes_per_launch": val * 1024.0 * 2.0, "fetch_size_kib_avg": val, "dispatches": cnt, "avg_us_under_pmc": dur / 1e3,
        "source_sha256": kernel_source_hash(), "date": datetime.date.today().isoformat(),
-       "method": "rocprofv3 --kernel-trace --pmc FETCH_SIZE -- python bench.py --steps 2 --warmup 1 --cpu-queries 0 --no-recall --no-configs; "
+       "method": "rocprofv3 --kernel-trace --pmc FETCH_SIZE -- python bench.py --full --steps 2 --warmup 1 --cpu-queries 0 --no-recall --no-configs; "
                  "bytes = FETCH_SIZE[KiB] * 1024 * 2 (gfx950 halves 16-B/lane streaming reads)"}
 if len(sys.argv) > 5:
     c2 = sqlite3.connect(sys.argv[5]).cursor()
