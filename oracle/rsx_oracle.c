@@ -254,19 +254,39 @@ static inline float orc_dot_f32(int d, const float* a, const float* b) {
     return s;
 }
 
+/* Centroids regrouped in blocks of ORC_LANES rows, interleaved by dimension: blk[b][t][j] = c[b * ORC_LANES + j][t], rows past k
+ * zero.  The assignment loops below then run ORC_LANES independent chains per point side by side (SIMD lanes): each lane is the
+ * same sequential fmaf chain over t as orc_dot_f32, so the bits do not change, only the chains' latency overlaps. */
+#define ORC_LANES 16
+static float* orc_interleave(int d, int k, const float* c) {
+    int nb = (k + ORC_LANES - 1) / ORC_LANES;
+    float* blk = (float*)calloc((size_t)nb * d * ORC_LANES, sizeof(float));
+    for (int r = 0; r < k; r++)
+        for (int t = 0; t < d; t++) blk[((int64_t)(r / ORC_LANES) * d + t) * ORC_LANES + r % ORC_LANES] = c[(int64_t)r * d + t];
+    return blk;
+}
+
 /* assign[i] = argmax_c <x_i, centroid_c>, first maximum on ties (FAISS quantizer->assign). */
 void orc_assign_ip(int d, int nlist, const float* centroids, int64_t n, const float* x,
                    int32_t* assign, float* best_out) {
+    float* blk = orc_interleave(d, nlist, centroids);
 #pragma omp parallel for schedule(static)
     for (int64_t i = 0; i < n; i++) {
+        const float* xi = x + i * d;
         float best = -INFINITY; int bi = 0;
-        for (int c = 0; c < nlist; c++) {
-            float s = orc_dot_f32(d, x + i * d, centroids + (int64_t)c * d);
-            if (s > best) { best = s; bi = c; }
+        for (int c0 = 0; c0 < nlist; c0 += ORC_LANES) {
+            const float* b = blk + (int64_t)(c0 / ORC_LANES) * d * ORC_LANES;
+            float s[ORC_LANES] = { 0.0f };
+            for (int t = 0; t < d; t++)
+#pragma omp simd
+                for (int j = 0; j < ORC_LANES; j++) s[j] = fmaf(xi[t], b[t * ORC_LANES + j], s[j]);
+            for (int j = 0; j < ORC_LANES && c0 + j < nlist; j++)
+                if (s[j] > best) { best = s[j]; bi = c0 + j; }
         }
         assign[i] = bi;
         if (best_out) best_out[i] = best;
     }
+    free(blk);
 }
 
 /* probe_ids/probe_scores [nq,nprobe]: quantizer->search(nq, x, nprobe), best first,
@@ -535,17 +555,26 @@ static void orc_renorm(int d, int k, float* c) {
     }
 }
 
+/* nearest centroid by squared L2 (sequential fmaf chain of squared differences), first minimum on ties; ORC_LANES centroids'
+ * chains side by side as in orc_assign_ip. */
 static void orc_assign_l2(int d, int k, const float* c, int64_t n, const float* x, int32_t* assign) {
+    float* blk = orc_interleave(d, k, c);
 #pragma omp parallel for schedule(static)
     for (int64_t i = 0; i < n; i++) {
+        const float* xi = x + i * d;
         float best = INFINITY; int bi = 0;
-        for (int j = 0; j < k; j++) {
-            float acc = 0.0f;
-            for (int t = 0; t < d; t++) { float df = x[i * d + t] - c[(int64_t)j * d + t]; acc = fmaf(df, df, acc); }
-            if (acc < best) { best = acc; bi = j; }
+        for (int c0 = 0; c0 < k; c0 += ORC_LANES) {
+            const float* b = blk + (int64_t)(c0 / ORC_LANES) * d * ORC_LANES;
+            float acc[ORC_LANES] = { 0.0f };
+            for (int t = 0; t < d; t++)
+#pragma omp simd
+                for (int j = 0; j < ORC_LANES; j++) { float df = xi[t] - b[t * ORC_LANES + j]; acc[j] = fmaf(df, df, acc[j]); }
+            for (int j = 0; j < ORC_LANES && c0 + j < k; j++)
+                if (acc[j] < best) { best = acc[j]; bi = c0 + j; }
         }
         assign[i] = bi;
     }
+    free(blk);
 }
 
 /* x [n,d] f32 (already subsampled/ordered by the caller through orc_kmeans_sample);

@@ -185,6 +185,10 @@ rsx_index* create_common(int kind, int d, int nlist, int M, int nbits, int metri
         if (pq_rot_applies(M) && want != 0) h->CB = 0;
         if (pq_sliced_applies(M) && want == 2) h->CB = PQ_SLICED;
         if ((size_t)h->Mpad * 1024 > 160 * 1024) RSX_THROW(RSX_ERR_UNSUPPORTED, "IVFPQ: M = %d needs more than 160 KiB of LDS for the look-up table", M);
+        // k_pq_encode (training and add) stages one sub-quantiser's 256 codewords in LDS; a workgroup can hold 160 KiB (dsub 160 is
+        // tested), past that the launch is refused and the codes would be whatever the buffer held (dsub 192 was measured so)
+        if ((size_t)h->dsub * 256 * 4 > 160 * 1024)
+            RSX_THROW(RSX_ERR_UNSUPPORTED, "IVFPQ: d / M = %d needs more than 160 KiB of LDS for a sub-quantiser's codewords (d / M <= 160)", h->dsub);
     }
     HIPCHECK(hipSetDevice(device));
     HIPCHECK(hipStreamCreateWithFlags(&h->st, hipStreamNonBlocking));
@@ -409,6 +413,8 @@ static void kmeans_update_gpu(rsx_index* h, KmeansWs& ws, const float* dx, int64
 void train_impl(rsx_index* h, int64_t n, const void* x, int dtype) {
     if (h->kind == KIND_FLAT) return;
     if (n < h->nlist) RSX_THROW(RSX_ERR_INVALID, "train: %lld training points for %d centroids", (long long)n, h->nlist);
+    if (h->kind == KIND_IVFPQ && n < 256) RSX_THROW(RSX_ERR_INVALID, "train: %lld points cannot train 256 PQ codewords", (long long)n);
+    // the handle's parameters change only once both trainings have succeeded: a failed train leaves the index as it was
     const int d = h->d;
     // training set as fp32 on the host (the reference passes host numpy: ivf_flat.py:135)
     std::vector<float> hx((size_t)n * d);
@@ -420,6 +426,8 @@ void train_impl(rsx_index* h, int64_t n, const void* x, int dtype) {
         HIPCHECK(hipStreamSynchronize(h->st));
     }
     const uint64_t seed = 1234;
+    std::vector<float> cen((size_t)h->nlist * d), cb;
+    DevBuf dcen;                                  // the new centroids on the device, for the PQ stage
     // ---- coarse quantiser: k-means, IP assignment, spherical centroids, niter 10, <=256 pts/centroid
     {
         const int k = h->nlist;
@@ -433,13 +441,12 @@ void train_impl(rsx_index* h, int64_t n, const void* x, int dtype) {
             for (int64_t i = 0; i < keep; i++) memcpy(&xs[(size_t)i * d], &hx[(size_t)perm[(size_t)i] * d], sizeof(float) * (size_t)d);
             xt = xs.data(); nt = keep;
         }
-        std::vector<float> cen((size_t)k * d);
         std::vector<int64_t> perm; rand_perm(nt, seed + 1, perm);
         for (int j = 0; j < k; j++) memcpy(&cen[(size_t)j * d], xt + (size_t)perm[(size_t)(j % nt)] * d, sizeof(float) * (size_t)d);
         renorm_rows(d, k, cen.data());
         DevBuf dxt; dxt.ensure((size_t)nt * d * 4);
         HIPCHECK(hipMemcpyAsync(dxt.p, xt, (size_t)nt * d * 4, hipMemcpyHostToDevice, h->st));
-        DevBuf dcen; dcen.ensure((size_t)k * d * 4);
+        dcen.ensure((size_t)k * d * 4);
         int ct = (k + 127) / 128;
         h->w_partial.ensure((size_t)nt * 2 * ct * 8);
         h->w_assign.ensure((size_t)nt * 4);
@@ -454,7 +461,8 @@ void train_impl(rsx_index* h, int64_t n, const void* x, int dtype) {
             kmeans_update_gpu(h, kws, dxt.as<float>(), d, 0, d, k, 1, nt, assign.data(), 0, 1, cen.data());
             renorm_rows(d, k, cen.data());
         }
-        set_centroids(h, cen.data());
+        HIPCHECK(hipGetLastError());          // a rejected launch fails this train (not the next call that checks)
+        HIPCHECK(hipMemcpyAsync(dcen.p, cen.data(), (size_t)k * d * 4, hipMemcpyHostToDevice, h->st));
     }
     // ---- PQ codebooks on residuals: <=65536 points, per-subspace L2 k-means, niter 25
     if (h->kind == KIND_IVFPQ) {
@@ -469,21 +477,20 @@ void train_impl(rsx_index* h, int64_t n, const void* x, int dtype) {
             for (int64_t i = 0; i < keep; i++) memcpy(&xs[(size_t)i * d], &hx[(size_t)perm[(size_t)i] * d], sizeof(float) * (size_t)d);
             xt = xs.data(); nt = keep;
         }
-        if (nt < 256) RSX_THROW(RSX_ERR_INVALID, "train: %lld points cannot train 256 PQ codewords", (long long)nt);
         DevBuf dxt, dres;
         dxt.ensure((size_t)nt * d * 4); dres.ensure((size_t)nt * d * 4);
         HIPCHECK(hipMemcpyAsync(dxt.p, xt, (size_t)nt * d * 4, hipMemcpyHostToDevice, h->st));
         int ct = (h->nlist + 127) / 128;
         h->w_partial.ensure((size_t)nt * 2 * ct * 8);
         h->w_assign.ensure((size_t)nt * 4);
-        launch_gemm_exact_argmax(dxt.p, 0, nt, d, h->d_centroids.as<float>(), h->nlist, d, h->w_partial.as<uint64_t>(),
+        launch_gemm_exact_argmax(dxt.p, 0, nt, d, dcen.as<float>(), h->nlist, d, h->w_partial.as<uint64_t>(),
                                  h->w_assign.as<int32_t>(), nullptr, h->st);
-        launch_residuals(dxt.as<float>(), nt, d, h->d_centroids.as<float>(), h->w_assign.as<int32_t>(), dres.as<float>(), h->st);
+        launch_residuals(dxt.as<float>(), nt, d, dcen.as<float>(), h->w_assign.as<int32_t>(), dres.as<float>(), h->st);
         std::vector<float> res((size_t)nt * d);
         HIPCHECK(hipMemcpyAsync(res.data(), dres.p, (size_t)nt * d * 4, hipMemcpyDeviceToHost, h->st));
         HIPCHECK(hipStreamSynchronize(h->st));
 
-        std::vector<float> cb((size_t)M * 256 * dsub);
+        cb.resize((size_t)M * 256 * dsub);
         for (int m = 0; m < M; m++) {
             std::vector<int64_t> perm; rand_perm(nt, seed + (uint64_t)m + 1, perm);
             for (int j = 0; j < 256; j++)
@@ -505,8 +512,10 @@ void train_impl(rsx_index* h, int64_t n, const void* x, int dtype) {
             // all M sub-spaces in one accumulation launch (M x 256 x dsub chains over the residuals on the device)
             kmeans_update_gpu(h, kws, dres.as<float>(), d, dsub, dsub, 256, M, nt, a32.data(), nt, 1, cb.data());
         }
-        set_codebooks(h, cb.data());
+        HIPCHECK(hipGetLastError());
     }
+    set_centroids(h, cen.data());
+    if (h->kind == KIND_IVFPQ) set_codebooks(h, cb.data());
     update_trained(h);
 }
 
