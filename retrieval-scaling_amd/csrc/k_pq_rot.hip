@@ -20,6 +20,14 @@
 //      queue in LDS and are appended with one reservation per work item and query.
 //    Bound: HBM (each code byte is read once per query GROUP; LDS 2 clk, VALU 1 op, MFMA 1/4 op per gather stay under
 //    it).  Measured stand-alone (tools/proto/rot_gather.hip): 5.9 TB/s of code bytes on MI355X.
+//  k_pq_scan_rot16, k_pq_scan_sl4, k_pq_scan_sl8 : the same scan for sixteen queries at M = 16 and on the sliced layout (four /
+//                        eight queries per gather); each is described at its definition.
+//  The four scans share one ITEM SKELETON, written once below PQRotItem: ItemDraw (a workgroup's items: XCD range, counter,
+//  stealing), load_records / publish_records (an item's G records into the LDS slot), readfirstlane64, append_survivors (the
+//  wave-private survivor logs) and run_descriptor (what k_pq_gather_select / k_pq_rot_compact read), and one host launcher,
+//  launch_item_scan (attribute, workspace carving, k_pq_rot_items, grid clamp, k_pq_rot_compact).  A new scan kernel supplies
+//  its table staging, its look-up loop, the moment it draws the next item (ItemDraw::draw / resolve — on purpose different per
+//  kernel), its dynamic LDS size and its trailing arguments; the item protocol it gets from the skeleton.
 //  k_pq_scan_rot_exact : per-(query, list) exact scan (fp32 table in LDS, sequential sums in m order = oracle bits) for the
 //                        certificate fallback, scan_kernel = 1/2 and pq_fast = 0 on this layout.  Byte loads through
 //                        pq_code_addr: slow and simple on purpose, it runs for ~1e-4 of the queries.
@@ -37,9 +45,6 @@ typedef int v4i __attribute__((ext_vector_type(4)));
 #endif
 #ifndef SL8_NB
 #define SL8_NB 16              // k_pq_scan_sl8: blocks of 32 vectors per wave and sub-tile (their partial sums are parked in 4 VGPRs each)
-#endif
-#ifndef SL8_VAR
-#define SL8_VAR 0
 #endif
 #ifndef SL8_AUX
 #define SL8_AUX 0             // ... cache policy of the code loads (2 = non-temporal)
@@ -113,6 +118,111 @@ struct __attribute__((aligned(16))) PQRotItem {
     int32_t cinit[4];      // MFMA accumulator init = -(integer threshold), see k_pq_scan_rot
 };
 static_assert(sizeof(PQRotItem) == 176, "PQRotItem is copied as 11 x 16 bytes");
+
+// ---------------------------------------------------------------------------------------
+// The item skeleton of the four work-item scans (k_pq_scan_rot, k_pq_scan_rot16, k_pq_scan_sl4, k_pq_scan_sl8), written once:
+// how a workgroup draws items, how the G records of an item reach its LDS slot, how a survivor leaves the scan and how an
+// item's runs are described to k_pq_gather_select / k_pq_rot_compact.  A scan kernel supplies its table staging, its look-up
+// loop and the moment it draws the next item; everything it shares with the others about the item protocol is here.
+// ---------------------------------------------------------------------------------------
+constexpr int ITEM_NONE = 0x7fffffff;      // "no item": every range is exhausted
+
+// The workgroup's items: XCD b % 8 owns a contiguous range of the list-major item order (the query groups of a list tile stay
+// on one XCD, close together in time); its workgroups draw items from one counter.  Only wave 0 talks to the counter: draw()
+// issues the atomic, resolve() turns its result into an item index — the kernel decides how far apart the two are.
+struct ItemDraw {
+    const int ti, per_xcd;       // work items of the launch; items per XCD range
+    uint32_t* const xcd_ctr;
+    int xlo, xhi;                // the range being drawn from — the workgroup's own XCD's, then (work stealing) the others' in turn
+    int cx, hops;
+    uint32_t* ctr;
+    unsigned drawn;              // wave 0, lane 0: the counter value of the last draw
+    __device__ __forceinline__ ItemDraw(uint32_t* xcd_ctr_, int ti_) : ti(ti_), per_xcd((ti_ + 7) >> 3), xcd_ctr(xcd_ctr_) {
+        cx = blockIdx.x & 7; hops = 0; drawn = 0;
+        xlo = cx * per_xcd;
+        xhi = xlo + per_xcd; if (xhi > ti) xhi = ti;
+        ctr = xcd_ctr + cx * 32;
+    }
+    __device__ __forceinline__ bool empty() const { return xlo >= xhi; }
+    __device__ __forceinline__ void draw(int lane) { if (lane == 0) drawn = atomicAdd(ctr, 1u); }
+    // turn the last draw into an item index; when the range is exhausted move on to the next XCD's range and draw there (the
+    // ranges hold equal item COUNTS, not equal work: measured finish times of the 8 XCDs spread by 10 % of the kernel; a stolen
+    // item loses its L2 neighbourhood, which only matters for the last few)
+    __device__ __forceinline__ int resolve(int lane) {
+        for (;;) {
+            const int i = xlo + (int)__builtin_amdgcn_readfirstlane(drawn);
+            if (i < xhi) return i;
+            if (hops >= 7) return ITEM_NONE;
+            hops++;
+            cx = (cx + 1) & 7;
+            xlo = cx * per_xcd;
+            xhi = xlo + per_xcd; if (xhi > ti) xhi = ti;
+            ctr = xcd_ctr + cx * 32;
+            if (xlo >= xhi) { drawn = 0u; xlo = 0; xhi = 0; continue; }
+            draw(lane);
+        }
+    }
+};
+
+// lanes 0 .. 11 G - 1 of wave 0: the item's G records, 16 bytes per lane; no item: the end marker (l = -1) ...
+__device__ __forceinline__ uint4 end_marker() { return make_uint4(0xffffffffu, 0, 0, 0); }
+template <int G>
+__device__ __forceinline__ uint4 load_records(const PQRotItem* items, int item, int lane) {
+    uint4 r = end_marker();
+    if (lane < 11 * G && item != ITEM_NONE) r = reinterpret_cast<const uint4*>(&items[(size_t)item * G])[lane];
+    return r;
+}
+// ... and their way into an LDS slot, with the item's index in the first record's pad0; the waves read them behind the next barrier
+template <int G>
+__device__ __forceinline__ void publish_records(PQRotItem* slot, uint4 rec, int item, int lane) {
+    if (lane < 11 * G) reinterpret_cast<uint4*>(slot)[lane] = rec;
+    if (lane == 0) slot->pad0 = item;
+}
+
+__device__ __forceinline__ int64_t readfirstlane64(int64_t v) {
+    return ((int64_t)__builtin_amdgcn_readfirstlane((int)(v >> 32)) << 32) | (uint32_t)__builtin_amdgcn_readfirstlane((int)v);
+}
+
+// Survivors leave the scan with PLAIN stores into WAVE-PRIVATE LOGS (round 4): every (workgroup, wave, query slot) owns one
+// append-only log of log_cap keys in HBM for the whole launch; the survivors of an item's query k go to the end of the wave's
+// log k — slot = the wave's running count plus the survivor's rank among this step's survivors of the same query (ballot +
+// mbcnt) — and one 8-byte descriptor {first key, count} per (item, wave, query) tells k_pq_gather_select / k_pq_rot_compact
+// where the item's run lies.  Rounds 2-3 gave every (item, wave, query) its own fixed segment of seg_cap keys: with 8.4 M
+// segments (the reference's nprobe 512) the pool allowed 128 keys each, and a query whose closest list is dense — 12 % of the
+// queries at M = 16, every query at k >= 1000 — overflowed and was re-run exactly.  A log only overflows when ONE wave
+// collects more than log_cap survivors of one slot in the whole launch (tens of thousands; counted, dropped, its queries
+// re-run exactly — never silently lost).  Nothing here returns a value: an LDS ds_add_rtn costs ~300 clk of the whole CU's
+// LDS pipe, and a returning global atomic sits in the wave's in-order vmcnt queue in front of the next item's table loads
+// (measured: 0.6 ms of a 3.8 ms scan for 1.9 M survivors).
+// One step of a wave (every lane calls it): rec = the record of the lane's query column in LDS (its score parameters are read
+// here, where a survivor is scored — rare — instead of living in ~9 VGPRs through the look-up loop), nq4 its slot in the record,
+// sum = the lane's integer sum of (u8 - 128) over the M sub-quantisers, cnd = it passed the integer threshold (and whatever else
+// the kernel asks of the block), pos / len = the vector's position in the list and the list's length (the comparison stays
+// here, behind the parameter loads: made by the caller ahead of them it cost k_pq_scan_rot16 20 B of scratch per lane),
+// QM = the lanes of the lane's query, log / lcur = the lane's log and the keys appended to it so far (equal in all lanes of a
+// query slot; persists across items: rot16 keeps one count per record).
+template <int M, typename P>
+__device__ __forceinline__ void append_survivors(const PQRotItem* rec, int nq4, int sum, bool cnd, P pos, P len, uint64_t QM,
+                                                 uint64_t* log, uint32_t& lcur, int log_cap) {
+    const float p_dis0 = rec->dis0[nq4], p_scale = rec->scale[nq4], p_bias = rec->bias[nq4];
+    const int64_t p_off = rec->off[nq4];
+    const uint64_t p_tau = rec->tau[nq4];
+    const float sc = p_dis0 + __fmaf_rn(p_scale, (float)(sum + 128 * M), p_bias);
+    const uint64_t key = (cnd && pos < len) ? make_key(sc, (uint32_t)p_off + (uint32_t)pos) : 0ull;
+    const bool pass = key > p_tau;
+    const uint64_t mq = __builtin_amdgcn_ballot_w64(pass) & QM;      // this step's survivors of MY query
+    if (pass) {
+        const uint32_t slot = lcur + __builtin_amdgcn_mbcnt_hi((uint32_t)(mq >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mq, 0u));
+        if (slot < (uint32_t)log_cap) log[slot] = key;   // beyond: counted, dropped -> the query is re-run exactly
+    }
+    lcur += (uint32_t)__builtin_popcountll(mq);
+}
+// the descriptor of the run [qstart, lcur) an item appended to log log_i: first key of the run in the log pool, keys stored,
+// bit 31 = the log was full and keys were dropped (only a run that itself lost keys is flagged)
+__device__ __forceinline__ uint2 run_descriptor(size_t log_i, uint32_t qstart, uint32_t lcur, int log_cap) {
+    const uint32_t c0 = qstart < (uint32_t)log_cap ? qstart : (uint32_t)log_cap, c1 = lcur < (uint32_t)log_cap ? lcur : (uint32_t)log_cap;
+    return make_uint2((uint32_t)(log_i * (size_t)log_cap) + c0, (c1 - c0) | ((lcur > (uint32_t)log_cap && lcur > qstart) ? 0x80000000u : 0u));
+}
 
 // ngq = records per work item: 1, or — M = 16, filtered scan (k_pq_scan_rot16) — 4: a work item is then a group of up to 16 probing
 // queries of a list tile, described by four consecutive 4-query records (a record without queries has np = 0).
@@ -253,35 +363,10 @@ __global__ __launch_bounds__(1024) void k_pq_scan_rot(PQScan8Args A, const PQRot
     const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int g = lane >> 4, i = lane & 15, n = lane & 15, nq4 = n & 3;
 
-    // ---- the workgroup's items: XCD b % 8 owns the contiguous item range [xlo, xhi) of the list-major order (the query groups
-    // of a list tile stay on one XCD, close together in time); its workgroups draw items from one counter.  Only wave 0
-    // talks to the counter, one item ahead, and publishes each item's record (or an end marker) through LDS.
-    const int ti = *A.total_items;
-    const int per_xcd = (ti + 7) >> 3;
-    const int xcd = blockIdx.x & 7;
-    int xlo = xcd * per_xcd;
-    int xhi = xlo + per_xcd; if (xhi > ti) xhi = ti;
-    if (xlo >= xhi) return;
-    uint32_t* ctr = xcd_ctr + xcd * 32;
-    int cx = xcd, hops = 0;      // wave 0: the range being drawn from — its own XCD's, then (work stealing) the others' in turn
-    unsigned drawn = 0;          // wave 0, lane 0: the counter value of the last draw
-    // wave 0: turn the last draw into an item index; when the range is exhausted move on to the next XCD's range and draw
-    // there (the ranges hold equal item COUNTS, not equal work: measured finish times of the 8 XCDs spread by 10 % of the
-    // kernel; a stolen item loses its L2 neighbourhood, which only matters for the last few)
-    auto resolve_draw = [&]() -> int {
-        for (;;) {
-            const int i = xlo + (int)__builtin_amdgcn_readfirstlane(drawn);
-            if (i < xhi) return i;
-            if (hops >= 7) return 0x7fffffff;
-            hops++;
-            cx = (cx + 1) & 7;
-            xlo = cx * per_xcd;
-            xhi = xlo + per_xcd; if (xhi > ti) xhi = ti;
-            ctr = xcd_ctr + cx * 32;
-            if (xlo >= xhi) { drawn = 0u; xlo = 0; xhi = 0; continue; }
-            if (lane == 0) drawn = atomicAdd(ctr, 1u);
-        }
-    };
+    // ---- the workgroup's items (ItemDraw): wave 0 draws them and publishes each item's record (or an end marker) through LDS
+    ItemDraw items_of(xcd_ctr, *A.total_items);
+    if (items_of.empty()) return;
+    const int ti = items_of.ti, per_xcd = items_of.per_xcd;
     // ---- per-lane constants, once per workgroup: rotation bytes, the one-hot B operand, the survivor-queue geometry
     uint32_t R0[NR0 > 0 ? NR0 : 1], R1[NR1 > 0 ? NR1 : 1];
 #pragma unroll
@@ -317,17 +402,7 @@ __global__ __launch_bounds__(1024) void k_pq_scan_rot(PQScan8Args A, const PQRot
     const int bsel_hi = G == 2 ? ((n >= 4 && n < 8) ? (1 << (8 * (n & 3))) : 0) : bsel;
     const v4i Bm = {bsel, bsel_hi, bsel, bsel_hi};
     const int vo16 = lane * 16, vo8 = lane * 8;
-    // Survivors leave the scan with PLAIN stores into WAVE-PRIVATE LOGS (round 4): every (workgroup, wave, query slot) owns one
-    // append-only log of log_cap keys in HBM for the whole launch; the survivors of an item's query k go to the end of the wave's
-    // log k — slot = the wave's running count plus the survivor's rank among this step's survivors of the same query (ballot +
-    // mbcnt) — and one 8-byte descriptor {first key, count} per (item, wave, query) tells k_pq_gather_select / k_pq_rot_compact
-    // where the item's run lies.  Rounds 2-3 gave every (item, wave, query) its own fixed segment of seg_cap keys: with 8.4 M
-    // segments (the reference's nprobe 512) the pool allowed 128 keys each, and a query whose closest list is dense — 12 % of the
-    // queries at M = 16, every query at k >= 1000 — overflowed and was re-run exactly.  A log only overflows when ONE wave
-    // collects more than log_cap survivors of one slot in the whole launch (tens of thousands; counted, dropped, its queries
-    // re-run exactly — never silently lost).  Nothing here returns a value: an LDS ds_add_rtn costs ~300 clk of the whole CU's
-    // LDS pipe, and a returning global atomic sits in the wave's in-order vmcnt queue in front of the next item's table loads
-    // (measured: 0.6 ms of a 3.8 ms scan for 1.9 M survivors).
+    // survivors: the wave-private logs of append_survivors()
     const uint64_t QM = NQ ? (0x1111111111111111ull << (n & 3))         // M = 16: every lane with n & 3 == query
                            : (n < 4 * G ? (0x0001000100010001ull << n) : 0ull);   // the four lanes that own query n (G = 2: n = 4 record + slot)
     const int rq = G == 2 ? (n >> 2) & 1 : 0;                                // the record of the item this lane's query column belongs to
@@ -337,12 +412,9 @@ __global__ __launch_bounds__(1024) void k_pq_scan_rot(PQScan8Args A, const PQRot
     uint32_t lcur = 0;                    // keys appended to the lane's log so far (equal in all lanes of a query slot); persists across items
     int item = 0;
     if (w == 0) {
-        if (lane == 0) { drawn = atomicAdd(ctr, 1u); }
-        item = resolve_draw();
-        uint4 r0 = make_uint4(0xffffffffu, 0, 0, 0);       // l = -1: end marker
-        if (lane < 11 * G && item != 0x7fffffff) r0 = reinterpret_cast<const uint4*>(&items[(size_t)item * G])[lane];
-        if (lane < 11 * G) reinterpret_cast<uint4*>(&islot[0])[lane] = r0;
-        if (lane == 0) islot[0].pad0 = item;
+        items_of.draw(lane);
+        item = items_of.resolve(lane);
+        publish_records<G>(&islot[0], load_records<G>(items, item, lane), item, lane);
     }
     int buf = 0;
 #pragma unroll 1
@@ -355,8 +427,7 @@ __global__ __launch_bounds__(1024) void k_pq_scan_rot(PQScan8Args A, const PQRot
         const bool skip_item = item_l < -1;         // pruned: no survivors possible, only the bookkeeping below runs
         const int np_raw = __builtin_amdgcn_readfirstlane(it->np);
         const int np = np_raw & 15;
-        const int64_t len = ((int64_t)__builtin_amdgcn_readfirstlane((int)(it->len >> 32)) << 32) | (uint32_t)__builtin_amdgcn_readfirstlane((int)it->len);
-        const int64_t base_row = ((int64_t)__builtin_amdgcn_readfirstlane((int)(it->base_row >> 32)) << 32) | (uint32_t)__builtin_amdgcn_readfirstlane((int)it->base_row);
+        const int64_t len = readfirstlane64(it->len), base_row = readfirstlane64(it->base_row);
         const int nblk = NQ ? (int)((len + 63) >> 6) : (int)(((len + 63) >> 6) << 2);     // code blocks of the list, slab padding included
         const int tb0 = __builtin_amdgcn_readfirstlane(it->tile) * (16 * bpw);
         const uint8_t* lp = a.codes + (base_row / BV) * (int64_t)BB;
@@ -482,8 +553,8 @@ __global__ __launch_bounds__(1024) void k_pq_scan_rot(PQScan8Args A, const PQRot
         // and scattered the siblings in time: L2 hit rate 21 %, 19.4 GB from the fabric for 9.6 GB of unique code bytes.
         // Wave 0 issues the draw three loop iterations before the end of its share, the record load one iteration before the
         // end: both latencies hide behind the last blocks of the scan.
-        uint4 pre = make_uint4(0xffffffffu, 0, 0, 0);
-        int i1 = 0x7fffffff;
+        uint4 pre = end_marker();
+        int i1 = ITEM_NONE;
         int dstate = 0;                       // wave 0: 0 = not drawn, 1 = draw in flight, 2 = record requested
         int nit0 = 0;                         // loop iterations of wave 0 for this item
         {
@@ -614,12 +685,8 @@ __global__ __launch_bounds__(1024) void k_pq_scan_rot(PQScan8Args A, const PQRot
                     if (lane == 0)
                         __hip_atomic_store(&prog[item], (uint32_t)(rowA + 1) | (wrapA ? 0x40000000u : 0u), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
                 }
-                if (dstate == 1 && nA >= nch - 16) {
-                    i1 = resolve_draw();
-                    if (lane < 11 * G && i1 != 0x7fffffff) pre = reinterpret_cast<const uint4*>(&items[(size_t)i1 * G])[lane];
-                    dstate = 2;
-                }
-                if (dstate == 0 && nA >= nch - 48) { if (lane == 0) drawn = atomicAdd(ctr, 1u); dstate = 1; }
+                if (dstate == 1 && nA >= nch - 16) { i1 = items_of.resolve(lane); pre = load_records<G>(items, i1, lane); dstate = 2; }
+                if (dstate == 0 && nA >= nch - 48) { items_of.draw(lane); dstate = 1; }
             }
 #pragma unroll
             for (int dd = 0; dd < RD; dd++) {
@@ -710,19 +777,8 @@ __global__ __launch_bounds__(1024) void k_pq_scan_rot(PQScan8Args A, const PQRot
                         for (int r = 0; r < 4; r++) {
                             const bool cnd = C[r] >= 0;
                             if (__builtin_amdgcn_ballot_w64(cnd)) {
-                                const float p_dis0 = itq->dis0[nq4], p_scale = itq->scale[nq4], p_bias = itq->bias[nq4];
-                                const int64_t p_off = itq->off[nq4];
-                                const uint64_t p_tau = itq->tau[nq4];
                                 const int64_t pos = NQ ? ((int64_t)b << 6) + 16 * (n >> 2) + 4 * g + r : ((int64_t)b << 4) + 4 * g + r;
-                                const float sc = p_dis0 + __fmaf_rn(p_scale, (float)(C[r] - cinit + 128 * M), p_bias);
-                                const uint64_t key = (cnd && pos < len && b - tb0 < 16 * bpw) ? make_key(sc, (uint32_t)p_off + (uint32_t)pos) : 0ull;
-                                const bool pass = key > p_tau;
-                                const uint64_t mq = __builtin_amdgcn_ballot_w64(pass) & QM;      // this step's survivors of MY query
-                                if (pass) {
-                                    const uint32_t slot = lcur + __builtin_amdgcn_mbcnt_hi((uint32_t)(mq >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mq, 0u));
-                                    if (slot < (uint32_t)log_cap) mylog[slot] = key;   // beyond: counted, dropped -> the query is re-run exactly
-                                }
-                                lcur += (uint32_t)__builtin_popcountll(mq);
+                                append_survivors<M>(itq, nq4, C[r] - cinit, cnd && b - tb0 < 16 * bpw, pos, len, QM, mylog, lcur, log_cap);
                             }
                         }
                     }
@@ -745,10 +801,8 @@ __global__ __launch_bounds__(1024) void k_pq_scan_rot(PQScan8Args A, const PQRot
         // run in the log pool, keys stored, bit 31 = the log was full and keys were dropped; wave 0 parks the next record (or the
         // end marker) and draws the index of the item after it
         __builtin_amdgcn_s_setprio(0);
-        if (FILTER && lane < 4 * G) {      // lane = 4 record + slot = its own query column n (g = 0)
-            const uint32_t c0 = qstart < (uint32_t)log_cap ? qstart : (uint32_t)log_cap, c1 = lcur < (uint32_t)log_cap ? lcur : (uint32_t)log_cap;
-            seg_desc[(((size_t)item * G + (size_t)(lane >> 2)) * 16 + w) * 4 + (lane & 3)] = make_uint2((uint32_t)(mylog_i * (size_t)log_cap) + c0, (c1 - c0) | ((lcur > (uint32_t)log_cap && lcur > qstart) ? 0x80000000u : 0u));   // only a run that itself lost keys is flagged
-        }
+        if (FILTER && lane < 4 * G)        // lane = 4 record + slot = its own query column n (g = 0)
+            seg_desc[(((size_t)item * G + (size_t)(lane >> 2)) * 16 + w) * 4 + (lane & 3)] = run_descriptor(mylog_i, qstart, lcur, log_cap);
 #ifdef RSX_MEASURE
         if (lane == 0 && item < 16384) g_rot_wave[16 * item + w] = (uint32_t)(wall_clock64() - t_scan0);
         if (tid == 0 && item < 65536) g_rot_trace[4 * item + 1] = wall_clock64();
@@ -756,13 +810,9 @@ __global__ __launch_bounds__(1024) void k_pq_scan_rot(PQScan8Args A, const PQRot
         if (w == 0 && lane == 0 && join_on)       // done: no sibling joins this item any more
             __hip_atomic_store(&prog[item], 0x7fffffffu, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
         if (w == 0) {
-            if (dstate == 0) { if (lane == 0) drawn = atomicAdd(ctr, 1u); dstate = 1; }     // empty / pruned / one-iteration items
-            if (dstate == 1) {
-                i1 = resolve_draw();
-                if (lane < 11 * G && i1 != 0x7fffffff) pre = reinterpret_cast<const uint4*>(&items[(size_t)i1 * G])[lane];
-            }
-            if (lane < 11 * G) reinterpret_cast<uint4*>(&islot[(buf ^ 1) * G])[lane] = pre;
-            if (lane == 0) islot[(buf ^ 1) * G].pad0 = i1;
+            if (dstate == 0) { items_of.draw(lane); dstate = 1; }     // empty / pruned / one-iteration items
+            if (dstate == 1) { i1 = items_of.resolve(lane); pre = load_records<G>(items, i1, lane); }
+            publish_records<G>(&islot[(buf ^ 1) * G], pre, i1, lane);
         }
     }
 }
@@ -793,31 +843,8 @@ __global__ __launch_bounds__(1024) void k_pq_scan_rot16(PQScan8Args A, const PQR
     const int tid = threadIdx.x, lane = tid & 63;
     const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int g = lane >> 4, i = lane & 15, n = lane & 15, nq4 = n & 3;
-    // ---- items: XCD b % 8 owns a contiguous range of the list-major item order, its workgroups draw from one counter, an exhausted
-    // range steals from the next XCD's (as k_pq_scan_rot)
-    const int ti = *A.total_items;
-    const int per_xcd = (ti + 7) >> 3;
-    const int xcd = blockIdx.x & 7;
-    int xlo = xcd * per_xcd;
-    int xhi = xlo + per_xcd; if (xhi > ti) xhi = ti;
-    if (xlo >= xhi) return;
-    uint32_t* ctr = xcd_ctr + xcd * 32;
-    int cx = xcd, hops = 0;
-    unsigned drawn = 0;
-    auto resolve_draw = [&]() -> int {
-        for (;;) {
-            const int i2 = xlo + (int)__builtin_amdgcn_readfirstlane(drawn);
-            if (i2 < xhi) return i2;
-            if (hops >= 7) return 0x7fffffff;
-            hops++;
-            cx = (cx + 1) & 7;
-            xlo = cx * per_xcd;
-            xhi = xlo + per_xcd; if (xhi > ti) xhi = ti;
-            ctr = xcd_ctr + cx * 32;
-            if (xlo >= xhi) { drawn = 0u; xlo = 0; xhi = 0; continue; }
-            if (lane == 0) drawn = atomicAdd(ctr, 1u);
-        }
-    };
+    ItemDraw items_of(xcd_ctr, *A.total_items);
+    if (items_of.empty()) return;
     // ---- per-lane constants: rotation bytes (lane (g, i) = vector 16 g + i reaches sub-quantiser (i + s) & 15 at step s, copy g & 1
     // of the code's 16 entries), for the two row halves (+128) and the two planes (plane 1: three rotation bytes + the plane byte)
     uint32_t R00[4], R01[4], R10[6], R11[6];
@@ -844,18 +871,11 @@ __global__ __launch_bounds__(1024) void k_pq_scan_rot16(PQScan8Args A, const PQR
     uint32_t lcur[G];
 #pragma unroll
     for (int gq = 0; gq < G; gq++) lcur[gq] = 0u;
-    const auto load_records = [&](int it_) -> uint4 {       // lanes 0 .. 11 G - 1: the item's G records, 16 bytes per lane
-        uint4 r0 = make_uint4(0xffffffffu, 0, 0, 0);        // l = -1: end marker
-        if (lane < 11 * G && it_ != 0x7fffffff) r0 = reinterpret_cast<const uint4*>(&items[(size_t)it_ * G])[lane];
-        return r0;
-    };
     int item = 0;
     if (w == 0) {
-        if (lane == 0) drawn = atomicAdd(ctr, 1u);
-        item = resolve_draw();
-        const uint4 r0 = load_records(item);
-        if (lane < 11 * G) reinterpret_cast<uint4*>(&islot[0])[lane] = r0;
-        if (lane == 0) islot[0].pad0 = item;
+        items_of.draw(lane);
+        item = items_of.resolve(lane);
+        publish_records<G>(&islot[0], load_records<G>(items, item, lane), item, lane);
     }
     int buf = 0;
 #pragma unroll 1
@@ -865,8 +885,7 @@ __global__ __launch_bounds__(1024) void k_pq_scan_rot16(PQScan8Args A, const PQR
         const int item_l = __builtin_amdgcn_readfirstlane(it0->l);
         if (item_l == -1) break;
         item = __builtin_amdgcn_readfirstlane(it0->pad0);
-        const int64_t len = ((int64_t)__builtin_amdgcn_readfirstlane((int)(it0->len >> 32)) << 32) | (uint32_t)__builtin_amdgcn_readfirstlane((int)it0->len);
-        const int64_t base_row = ((int64_t)__builtin_amdgcn_readfirstlane((int)(it0->base_row >> 32)) << 32) | (uint32_t)__builtin_amdgcn_readfirstlane((int)it0->base_row);
+        const int64_t len = readfirstlane64(it0->len), base_row = readfirstlane64(it0->base_row);
         const int nblk = (int)((len + 63) >> 6);
         const int tb0 = __builtin_amdgcn_readfirstlane(it0->tile) * (16 * bpw);
         int npg[G];
@@ -884,7 +903,7 @@ __global__ __launch_bounds__(1024) void k_pq_scan_rot16(PQScan8Args A, const PQR
             ca[dd] = __builtin_amdgcn_raw_buffer_load_b128(rs, vo16, dd < nmine ? (tb0 + w + 16 * dd) * BB : so_oob, 0);
             __builtin_amdgcn_sched_barrier(0);
         }
-        if (w == 0 && lane == 0) drawn = atomicAdd(ctr, 1u);      // the next item's index: resolved after the staging
+        if (w == 0) items_of.draw(lane);      // the next item's index: resolved after the staging
         // ---- stage the tables, a plane (two groups) at a time: thread e -> (code e >> 4 + 64 pass, half (e >> 3) & 1, copy (e >> 2) & 1,
         // four sub-quantisers e & 3): 16 consecutive lanes write the 16 different 16-byte bank slots of ONE row — no bank conflict
         // (the 4-query form wrote 4 slots of every row: SQ_LDS_BANK_CONFLICT 4.5 % of the kernel's LDS cycles)
@@ -917,9 +936,9 @@ __global__ __launch_bounds__(1024) void k_pq_scan_rot16(PQScan8Args A, const PQR
             }
         }
         // ---- the next item's records: requested now (the draw has returned), parked after the scan
-        uint4 pre = make_uint4(0xffffffffu, 0, 0, 0);
-        int i1 = 0x7fffffff;
-        if (w == 0) { i1 = resolve_draw(); pre = load_records(i1); }
+        uint4 pre = end_marker();
+        int i1 = ITEM_NONE;
+        if (w == 0) { i1 = items_of.resolve(lane); pre = load_records<G>(items, i1, lane); }
         int cin[G];
         uint32_t qstart[G];
 #pragma unroll
@@ -965,19 +984,8 @@ __global__ __launch_bounds__(1024) void k_pq_scan_rot16(PQScan8Args A, const PQR
                         for (int r = 0; r < 4; r++) {
                             const bool cnd = C[r] >= 0;
                             if (__builtin_amdgcn_ballot_w64(cnd)) {
-                                const float p_dis0 = itg->dis0[nq4], p_scale = itg->scale[nq4], p_bias = itg->bias[nq4];
-                                const int64_t p_off = itg->off[nq4];
-                                const uint64_t p_tau = itg->tau[nq4];
                                 const int64_t pos = ((int64_t)b << 6) + 16 * (n >> 2) + 4 * g + r;
-                                const float sc = p_dis0 + __fmaf_rn(p_scale, (float)(C[r] - cinit + 128 * M), p_bias);
-                                const uint64_t key = (cnd && pos < len) ? make_key(sc, (uint32_t)p_off + (uint32_t)pos) : 0ull;
-                                const bool pass = key > p_tau;
-                                const uint64_t mq = __builtin_amdgcn_ballot_w64(pass) & QM;      // this step's survivors of MY query
-                                if (pass) {
-                                    const uint32_t slot = lcur[gq] + __builtin_amdgcn_mbcnt_hi((uint32_t)(mq >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mq, 0u));
-                                    if (slot < (uint32_t)log_cap) log_keys[(mylog_0 + 4 * gq) * (size_t)log_cap + slot] = key;   // beyond: counted, dropped -> exact re-run
-                                }
-                                lcur[gq] += (uint32_t)__builtin_popcountll(mq);
+                                append_survivors<M>(itg, nq4, C[r] - cinit, cnd, pos, len, QM, log_keys + (mylog_0 + 4 * gq) * (size_t)log_cap, lcur[gq], log_cap);
                             }
                         }
                     }
@@ -991,14 +999,9 @@ __global__ __launch_bounds__(1024) void k_pq_scan_rot16(PQScan8Args A, const PQR
             uint32_t l1 = lcur[0], l0 = qstart[0];
 #pragma unroll
             for (int x = 1; x < G; x++) if (gq == x) { l1 = lcur[x]; l0 = qstart[x]; }
-            const uint32_t c0 = l0 < (uint32_t)log_cap ? l0 : (uint32_t)log_cap, c1 = l1 < (uint32_t)log_cap ? l1 : (uint32_t)log_cap;
-            seg_desc[(((size_t)item * G + gq) * 16 + w) * 4 + (lane & 3)] =
-                make_uint2((uint32_t)((mylog_0 - nq4 + lane) * (size_t)log_cap) + c0, (c1 - c0) | ((l1 > (uint32_t)log_cap && l1 > l0) ? 0x80000000u : 0u));
+            seg_desc[(((size_t)item * G + gq) * 16 + w) * 4 + (lane & 3)] = run_descriptor(mylog_0 - nq4 + lane, l0, l1, log_cap);
         }
-        if (w == 0) {
-            if (lane < 11 * G) reinterpret_cast<uint4*>(&islot[(buf ^ 1) * G])[lane] = pre;
-            if (lane == 0) islot[(buf ^ 1) * G].pad0 = i1;
-        }
+        if (w == 0) publish_records<G>(&islot[(buf ^ 1) * G], pre, i1, lane);
     }
 }
 
@@ -1029,29 +1032,8 @@ __global__ __launch_bounds__(1024) void k_pq_scan_sl4(PQScan8Args A, const PQRot
     const int tid = threadIdx.x, lane = tid & 63;
     const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int g = lane >> 4, i = lane & 15, n = lane & 15, nq4 = n & 3;
-    const int ti = *A.total_items;
-    const int per_xcd = (ti + 7) >> 3;
-    const int xcd = blockIdx.x & 7;
-    int xlo = xcd * per_xcd;
-    int xhi = xlo + per_xcd; if (xhi > ti) xhi = ti;
-    if (xlo >= xhi) return;
-    uint32_t* ctr = xcd_ctr + xcd * 32;
-    int cx = xcd, hops = 0;
-    unsigned drawn = 0;
-    auto resolve_draw = [&]() -> int {
-        for (;;) {
-            const int i2 = xlo + (int)__builtin_amdgcn_readfirstlane(drawn);
-            if (i2 < xhi) return i2;
-            if (hops >= 7) return 0x7fffffff;
-            hops++;
-            cx = (cx + 1) & 7;
-            xlo = cx * per_xcd;
-            xhi = xlo + per_xcd; if (xhi > ti) xhi = ti;
-            ctr = xcd_ctr + cx * 32;
-            if (xlo >= xhi) { drawn = 0u; xlo = 0; xhi = 0; continue; }
-            if (lane == 0) drawn = atomicAdd(ctr, 1u);
-        }
-    };
+    ItemDraw items_of(xcd_ctr, *A.total_items);
+    if (items_of.empty()) return;
     // rotation bytes: dword slot 16 (g & 1) + ((i + s) & 15) of the row half; plane and row half are ORed in per slice
     uint32_t R[6];
 #pragma unroll
@@ -1068,18 +1050,11 @@ __global__ __launch_bounds__(1024) void k_pq_scan_sl4(PQScan8Args A, const PQRot
     const size_t mylog_i = ((size_t)blockIdx.x * 16 + (size_t)w) * 4 + (size_t)nq4;
     uint64_t* const mylog = log_keys + mylog_i * (size_t)log_cap;
     uint32_t lcur = 0;
-    const auto load_record = [&](int it_) -> uint4 {
-        uint4 r0 = make_uint4(0xffffffffu, 0, 0, 0);
-        if (lane < 11 && it_ != 0x7fffffff) r0 = reinterpret_cast<const uint4*>(&items[it_])[lane];
-        return r0;
-    };
     int item = 0;
     if (w == 0) {
-        if (lane == 0) drawn = atomicAdd(ctr, 1u);
-        item = resolve_draw();
-        const uint4 r0 = load_record(item);
-        if (lane < 11) reinterpret_cast<uint4*>(&islot[0])[lane] = r0;
-        if (lane == 0) islot[0].pad0 = item;
+        items_of.draw(lane);
+        item = items_of.resolve(lane);
+        publish_records<1>(&islot[0], load_records<1>(items, item, lane), item, lane);
     }
     int buf = 0;
 #pragma unroll 1
@@ -1090,8 +1065,7 @@ __global__ __launch_bounds__(1024) void k_pq_scan_sl4(PQScan8Args A, const PQRot
         if (item_l == -1) break;
         item = __builtin_amdgcn_readfirstlane(it->pad0);
         const int np = __builtin_amdgcn_readfirstlane(it->np) & 15;
-        const int64_t len = ((int64_t)__builtin_amdgcn_readfirstlane((int)(it->len >> 32)) << 32) | (uint32_t)__builtin_amdgcn_readfirstlane((int)it->len);
-        const int64_t base_row = ((int64_t)__builtin_amdgcn_readfirstlane((int)(it->base_row >> 32)) << 32) | (uint32_t)__builtin_amdgcn_readfirstlane((int)it->base_row);
+        const int64_t len = readfirstlane64(it->len), base_row = readfirstlane64(it->base_row);
         const int nblk = (int)((len + 63) >> 6) << 1;
         const int tb0 = __builtin_amdgcn_readfirstlane(it->tile) * tile_blocks;
         int bend = tb0 + tile_blocks; if (bend > nblk) bend = nblk;
@@ -1110,7 +1084,7 @@ __global__ __launch_bounds__(1024) void k_pq_scan_sl4(PQScan8Args A, const PQRot
             for (int sl = 0; sl < NS; sl++) ca[dd][sl] = __builtin_amdgcn_raw_buffer_load_b128(rs, vo16, so == so_oob ? so_oob : so + sl * (PQ_SLICED_GB * 1024), 0);
             __builtin_amdgcn_sched_barrier(0);
         }
-        if (w == 0 && lane == 0) drawn = atomicAdd(ctr, 1u);      // the next item's index: resolved after the staging
+        if (w == 0) items_of.draw(lane);      // the next item's index: resolved after the staging
         // ---- stage the four queries' table: unit = (code, 4 consecutive m) -> 4 dwords (byte k = query k as int8); lut8 is [q][slice][code][32]
         {
             int qq[4];
@@ -1142,9 +1116,9 @@ __global__ __launch_bounds__(1024) void k_pq_scan_sl4(PQScan8Args A, const PQRot
                 *reinterpret_cast<uint4*>(sb + (m >> 6) * 65536 + c * 256 + (m & 63) * 4) = o;       // slice (m >> 5) & 1 = the row half
             }
         }
-        uint4 pre = make_uint4(0xffffffffu, 0, 0, 0);
-        int i1 = 0x7fffffff;
-        if (w == 0) { i1 = resolve_draw(); pre = load_record(i1); }
+        uint4 pre = end_marker();
+        int i1 = ITEM_NONE;
+        if (w == 0) { i1 = items_of.resolve(lane); pre = load_records<1>(items, i1, lane); }
         const int cinit = n < 8 ? it->cinit[nq4] : -(1 << 30);
         const uint32_t qstart = lcur;
         __syncthreads();    // #2: tables staged
@@ -1190,33 +1164,15 @@ __global__ __launch_bounds__(1024) void k_pq_scan_sl4(PQScan8Args A, const PQRot
                         const int Cr = r == 0 ? C[0] : r == 1 ? C[1] : r == 2 ? C[2] : C[3];
                         const bool cnd = Cr >= 0;
                         if (__builtin_amdgcn_ballot_w64(cnd)) {
-                            const float p_dis0 = it->dis0[nq4], p_scale = it->scale[nq4], p_bias = it->bias[nq4];
-                            const int64_t p_off = it->off[nq4];
-                            const uint64_t p_tau = it->tau[nq4];
                             const uint32_t pos = ((uint32_t)b << 5) + (uint32_t)(16 * ((n >> 2) & 1) + 4 * g + r);
-                            const float sc = p_dis0 + __fmaf_rn(p_scale, (float)(Cr - cinit + 128 * M), p_bias);
-                            const uint64_t key = (cnd && pos < (uint32_t)len) ? make_key(sc, (uint32_t)p_off + pos) : 0ull;
-                            const bool pass_ = key > p_tau;
-                            const uint64_t mq = __builtin_amdgcn_ballot_w64(pass_) & QM;
-                            if (pass_) {
-                                const uint32_t slot_k = lcur + __builtin_amdgcn_mbcnt_hi((uint32_t)(mq >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mq, 0u));
-                                if (slot_k < (uint32_t)log_cap) mylog[slot_k] = key;
-                            }
-                            lcur += (uint32_t)__builtin_popcountll(mq);
+                            append_survivors<M>(it, nq4, Cr - cinit, cnd, pos, (uint32_t)len, QM, mylog, lcur, log_cap);
                         }
                     }
                 }
             }
         }
-        if (lane < 4) {
-            const uint32_t c0 = qstart < (uint32_t)log_cap ? qstart : (uint32_t)log_cap, c1 = lcur < (uint32_t)log_cap ? lcur : (uint32_t)log_cap;
-            seg_desc[((size_t)item * 16 + w) * 4 + lane] =
-                make_uint2((uint32_t)(mylog_i * (size_t)log_cap) + c0, (c1 - c0) | ((lcur > (uint32_t)log_cap && lcur > qstart) ? 0x80000000u : 0u));
-        }
-        if (w == 0) {
-            if (lane < 11) reinterpret_cast<uint4*>(&islot[buf ^ 1])[lane] = pre;
-            if (lane == 0) islot[buf ^ 1].pad0 = i1;
-        }
+        if (lane < 4) seg_desc[((size_t)item * 16 + w) * 4 + lane] = run_descriptor(mylog_i, qstart, lcur, log_cap);
+        if (w == 0) publish_records<1>(&islot[buf ^ 1], pre, i1, lane);
     }
 }
 
@@ -1262,31 +1218,8 @@ __global__ __launch_bounds__(1024) void k_pq_scan_sl8(PQScan8Args A, const PQRot
     const int tid = threadIdx.x, lane = tid & 63;
     const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int g = lane >> 4, i = lane & 15, n = lane & 15, nq4 = n & 3;
-    // ---- items: XCD b % 8 owns a contiguous range of the list-major item order, its workgroups draw from one counter, an exhausted
-    // range steals from the next XCD's (as k_pq_scan_rot)
-    const int ti = *A.total_items;
-    const int per_xcd = (ti + 7) >> 3;
-    const int xcd = blockIdx.x & 7;
-    int xlo = xcd * per_xcd;
-    int xhi = xlo + per_xcd; if (xhi > ti) xhi = ti;
-    if (xlo >= xhi) return;
-    uint32_t* ctr = xcd_ctr + xcd * 32;
-    int cx = xcd, hops = 0;
-    unsigned drawn = 0;
-    auto resolve_draw = [&]() -> int {
-        for (;;) {
-            const int i2 = xlo + (int)__builtin_amdgcn_readfirstlane(drawn);
-            if (i2 < xhi) return i2;
-            if (hops >= 7) return 0x7fffffff;
-            hops++;
-            cx = (cx + 1) & 7;
-            xlo = cx * per_xcd;
-            xhi = xlo + per_xcd; if (xhi > ti) xhi = ti;
-            ctr = xcd_ctr + cx * 32;
-            if (xlo >= xhi) { drawn = 0u; xlo = 0; xhi = 0; continue; }
-            if (lane == 0) drawn = atomicAdd(ctr, 1u);
-        }
-    };
+    ItemDraw items_of(xcd_ctr, *A.total_items);
+    if (items_of.empty()) return;
     // ---- per-lane constants.  Rotation bytes: lane (g, i) reads, at step s, the 8-byte slot 16 (g & 1) + ((i + s) & 15) of its code's
     // row; three per register, the fourth byte = the table slot of the pass (0 here, 1 in Rb) -> address bit 16
     uint32_t Ra[6], Rb[6];
@@ -1310,18 +1243,11 @@ __global__ __launch_bounds__(1024) void k_pq_scan_sl8(PQScan8Args A, const PQRot
     const size_t mylog_i = ((size_t)blockIdx.x * 16 + (size_t)w) * (4 * G) + (size_t)qn;
     uint64_t* const mylog = log_keys + mylog_i * (size_t)log_cap;
     uint32_t lcur = 0;
-    const auto load_records = [&](int it_) -> uint4 {
-        uint4 r0 = make_uint4(0xffffffffu, 0, 0, 0);        // l = -1: end marker
-        if (lane < 11 * G && it_ != 0x7fffffff) r0 = reinterpret_cast<const uint4*>(&items[(size_t)it_ * G])[lane];
-        return r0;
-    };
     int item = 0;
     if (w == 0) {
-        if (lane == 0) drawn = atomicAdd(ctr, 1u);
-        item = resolve_draw();
-        const uint4 r0 = load_records(item);
-        if (lane < 11 * G) reinterpret_cast<uint4*>(&islot[0])[lane] = r0;
-        if (lane == 0) islot[0].pad0 = item;
+        items_of.draw(lane);
+        item = items_of.resolve(lane);
+        publish_records<G>(&islot[0], load_records<G>(items, item, lane), item, lane);
     }
     int buf = 0;
 #pragma unroll 1
@@ -1332,8 +1258,7 @@ __global__ __launch_bounds__(1024) void k_pq_scan_sl8(PQScan8Args A, const PQRot
         const int item_l = __builtin_amdgcn_readfirstlane(it0->l);
         if (item_l == -1) break;
         item = __builtin_amdgcn_readfirstlane(it0->pad0);
-        const int64_t len = ((int64_t)__builtin_amdgcn_readfirstlane((int)(it0->len >> 32)) << 32) | (uint32_t)__builtin_amdgcn_readfirstlane((int)it0->len);
-        const int64_t base_row = ((int64_t)__builtin_amdgcn_readfirstlane((int)(it0->base_row >> 32)) << 32) | (uint32_t)__builtin_amdgcn_readfirstlane((int)it0->base_row);
+        const int64_t len = readfirstlane64(it0->len), base_row = readfirstlane64(it0->base_row);
         const int nblk = (int)((len + 63) >> 6) << 1;                          // 32-vector blocks of the list, slab padding included
         const int tb0 = __builtin_amdgcn_readfirstlane(it0->tile) * tile_blocks;
         int bend = tb0 + tile_blocks; if (bend > nblk) bend = nblk;
@@ -1408,8 +1333,8 @@ __global__ __launch_bounds__(1024) void k_pq_scan_sl8(PQScan8Args A, const PQRot
         // other, walk the same sub-tiles in the same order at the same pace, and the second finds the code lines in the XCD's L2.  (Drawn
         // one item ahead, siblings started tens of microseconds apart: 14.6 GB fetched for 9.6 GB of codes.)  Wave 0 draws at the start
         // of the item's last pass and requests the records half-way through it.
-        uint4 pre = make_uint4(0xffffffffu, 0, 0, 0);
-        int i1 = 0x7fffffff;
+        uint4 pre = end_marker();
+        int i1 = ITEM_NONE;
         int dstate = 0;                       // wave 0: 0 = not drawn, 1 = draw in flight, 2 = records requested
         if (w == 0 && lane == 0) { lds_wr32(cntA_a, 0u); lds_wr32(cntS_a, 0u); lds_wr32(cntB_a, 0u); }       // the item's pass counters
         const PQRotItem* itq = &islot[buf * G + rq];
@@ -1424,32 +1349,21 @@ __global__ __launch_bounds__(1024) void k_pq_scan_sl8(PQScan8Args A, const PQRot
         // 2 t and 2 t + 1 share the four registers accp[t] (low / high half): a sub-tile of 16 x NB blocks costs 2 NB VGPRs, which is what
         // sets the number of table re-stagings per item (64 KiB each through the fabric).  The threshold joins in the last pass.
         uint32_t accp[NB / 2][4];
-        uint32_t xacc = 0;
         auto pass = [&](auto PC, int st) {
             constexpr int P = decltype(PC)::value;
             // unit 0 of the wave's share is requested behind block JL0 and written behind JW0, unit 1 behind JL1 / JW1
             constexpr int JL0 = 1 < NB ? 1 : 0, JW0 = NB >= 8 ? NB / 2 - 1 : (NB > 2 ? 2 : NB - 1), JL1 = JW0 + 1 < NB ? JW0 + 1 : NB - 1, JW1 = NB - 2 > JL1 ? NB - 2 : NB - 1;
             const int sl = slice_of(st, P);
             const int pn = P + 1 < NS ? P + 1 : 0, stn = P + 1 < NS ? st : st + 1;       // the pass after this one (prefetch across the boundary)
-#if !(SL8_VAR & 16)
             if (P == 1 && st == 0) { while ((int)(lds_rd32_volatile(cntB_a) - 16u) < 0) __builtin_amdgcn_s_sleep(1); }
-#endif
-#if !(SL8_VAR & 17)     // (16 = no waiting on the pass counters — races, timing only)
             if (P == 2) { while ((int)(lds_rd32_volatile(cntS_a) - (uint32_t)(16 * (st + 1))) < 0) __builtin_amdgcn_s_sleep(1); }
-#endif
 #pragma unroll
             for (int j = 0; j < NB; j++) {
                 const int b = tb0 + 16 * (st * NB + j) + w;
-#if SL8_VAR & 32        // (32 / 64 = the sixteen waves meet before every block / every fourth block: do they fetch better in lock-step?  timing experiment)
-                __builtin_amdgcn_s_barrier();
-#elif SL8_VAR & 64
-                if (j % 4 == 0) __builtin_amdgcn_s_barrier();
-#endif
                 if (P == 2 && w == 0 && st == nsub - 1) {
-                    if (j == 0 && dstate == 0) { if (lane == 0) drawn = atomicAdd(ctr, 1u); dstate = 1; }
-                    if (j == NB / 2 && dstate == 1) { i1 = resolve_draw(); pre = load_records(i1); dstate = 2; }
+                    if (j == 0 && dstate == 0) { items_of.draw(lane); dstate = 1; }
+                    if (j == NB / 2 && dstate == 1) { i1 = items_of.resolve(lane); pre = load_records<G>(items, i1, lane); dstate = 2; }
                 }
-#if !(SL8_VAR & 8)      // (8 = no issue-priority rotation)
                 // the four waves of a SIMD (w, w + 4, w + 8, w + 12) take turns at the top issue priority, SL8_PR blocks each: the arbiter
                 // favours the oldest wave otherwise, and here every wave waits for the slowest once per sub-tile
                 if (j % SL8_PR == 0) {
@@ -1460,24 +1374,17 @@ __global__ __launch_bounds__(1024) void k_pq_scan_sl8(PQScan8Args A, const PQRot
                         default: __builtin_amdgcn_s_setprio(0); break;
                     }
                 }
-#endif
                 uint32_t gv[16];
-#if SL8_VAR & 2         // (2 = the code stream and the table re-staging alone: no look-ups, no sums)
-                xacc ^= ca[(P * NB + j) % RD].x ^ ca[(P * NB + j) % RD].y ^ ca[(P * NB + j) % RD].z ^ ca[(P * NB + j) % RD].w;
-#pragma unroll
-                for (int s2 = 0; s2 < 16; s2++) gv[s2] = 0;
-#else
                 {
                     const uint32_t cw[4] = {ca[(P * NB + j) % RD].x, ca[(P * NB + j) % RD].y, ca[(P * NB + j) % RD].z, ca[(P * NB + j) % RD].w};
 #pragma unroll
                     for (int s2 = 0; s2 < 16; s2++)
                         gv[s2] = __builtin_amdgcn_perm(cw[s2 >> 2], P == 1 ? Rb[s2 / 3] : Ra[s2 / 3], 0x0c030000u | ((uint32_t)(4 + (s2 & 3)) << 8) | (uint32_t)(s2 % 3));
                 }
-#endif
                 __builtin_amdgcn_sched_barrier(0);
                 ca[(P * NB + j) % RD] = __builtin_amdgcn_raw_buffer_load_b128(rs, vo16, j + RD < NB ? code_off(st, P, j + RD) : code_off(stn, pn, j + RD - NB), SL8_AUX);
                 __builtin_amdgcn_sched_barrier(0);
-                if (b < bend && !(SL8_VAR & 2)) {          // wave-uniform: inside the tile and the list (the prefetch slot has been refilled either way)
+                if (b < bend) {          // wave-uniform: inside the tile and the list (the prefetch slot has been refilled either way)
                     v4i C = {0, 0, 0, 0};
                     if (P > 0) {
 #pragma unroll
@@ -1525,19 +1432,8 @@ __global__ __launch_bounds__(1024) void k_pq_scan_sl8(PQScan8Args A, const PQRot
                             const int Cr = r == 0 ? C[0] : r == 1 ? C[1] : r == 2 ? C[2] : C[3];
                             const bool cnd = Cr >= 0;
                             if (__builtin_amdgcn_ballot_w64(cnd)) {
-                                const float p_dis0 = itq->dis0[nq4], p_scale = itq->scale[nq4], p_bias = itq->bias[nq4];
-                                const int64_t p_off = itq->off[nq4];
-                                const uint64_t p_tau = itq->tau[nq4];
                                 const uint32_t pos = (uint32_t)b5 + (uint32_t)(16 * (n >> 3) + 4 * g + r);
-                                const float sc = p_dis0 + __fmaf_rn(p_scale, (float)(Cr - cinit + 128 * M), p_bias);
-                                const uint64_t key = (cnd && pos < (uint32_t)len) ? make_key(sc, (uint32_t)p_off + pos) : 0ull;
-                                const bool pass_ = key > p_tau;
-                                const uint64_t mq = __builtin_amdgcn_ballot_w64(pass_) & QM;      // this step's survivors of MY query
-                                if (pass_) {
-                                    const uint32_t slot_k = lcur + __builtin_amdgcn_mbcnt_hi((uint32_t)(mq >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mq, 0u));
-                                    if (slot_k < (uint32_t)log_cap) mylog[slot_k] = key;   // beyond: counted, dropped -> the query is re-run exactly
-                                }
-                                lcur += (uint32_t)__builtin_popcountll(mq);
+                                append_survivors<M>(itq, nq4, Cr - cinit, cnd, pos, (uint32_t)len, QM, mylog, lcur, log_cap);
                             }
                         }
                     }
@@ -1549,19 +1445,15 @@ __global__ __launch_bounds__(1024) void k_pq_scan_sl8(PQScan8Args A, const PQRot
                     if (j == JL1) stage_issue(1, 1);
                     if (j == JW1) stage_write(1, 1);
                 }
-#if !(SL8_VAR & 1)      // (cost-split builds of tools/build_variant.sh: 1 = no re-staging — wrong sums, timing only)
                 if (P == 1) {
                     if (j == JL0) stage_issue(slice_of(st, 2), 0);
                     if (j == JW0) {
-#if !(SL8_VAR & 16)
                         while ((int)(lds_rd32_volatile(cntA_a) - (uint32_t)(16 * (st + 1))) < 0) __builtin_amdgcn_s_sleep(1);
-#endif
                         stage_write(0, 0);
                     }
                     if (j == JL1) stage_issue(slice_of(st, 2), 1);
                     if (j == JW1) stage_write(0, 1);
                 }
-#endif
             }
             if (P == 0 && st == 0) {
                 asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
@@ -1580,19 +1472,13 @@ __global__ __launch_bounds__(1024) void k_pq_scan_sl8(PQScan8Args A, const PQRot
             pass(std::integral_constant<int, 2>{}, st);
         }
         __builtin_amdgcn_s_setprio(0);
-        if ((SL8_VAR & 2) && xacc == 0x12345678u) mylog[0] = xacc;
         // ---- item epilogue: the wave's 4 G run descriptors (lane = 4 record + slot = its own query column, g = 0, vector half 0), then
         // wave 0 parks the next item's records
-        if (lane < 4 * G) {
-            const uint32_t c0 = qstart < (uint32_t)log_cap ? qstart : (uint32_t)log_cap, c1 = lcur < (uint32_t)log_cap ? lcur : (uint32_t)log_cap;
-            seg_desc[(((size_t)item * G + (size_t)(lane >> 2)) * 16 + w) * 4 + (lane & 3)] =
-                make_uint2((uint32_t)(mylog_i * (size_t)log_cap) + c0, (c1 - c0) | ((lcur > (uint32_t)log_cap && lcur > qstart) ? 0x80000000u : 0u));
-        }
+        if (lane < 4 * G) seg_desc[(((size_t)item * G + (size_t)(lane >> 2)) * 16 + w) * 4 + (lane & 3)] = run_descriptor(mylog_i, qstart, lcur, log_cap);
         if (w == 0) {
-            if (dstate == 0) { if (lane == 0) drawn = atomicAdd(ctr, 1u); dstate = 1; }     // empty items
-            if (dstate == 1) { i1 = resolve_draw(); pre = load_records(i1); }
-            if (lane < 11 * G) reinterpret_cast<uint4*>(&islot[(buf ^ 1) * G])[lane] = pre;
-            if (lane == 0) islot[(buf ^ 1) * G].pad0 = i1;
+            if (dstate == 0) { items_of.draw(lane); dstate = 1; }     // empty items
+            if (dstate == 1) { i1 = items_of.resolve(lane); pre = load_records<G>(items, i1, lane); }
+            publish_records<G>(&islot[(buf ^ 1) * G], pre, i1, lane);
         }
     }
 }
@@ -1676,16 +1562,16 @@ int pq_scan_rot_max_wgs(int M) {
     return (ncu + 7) & ~7;
 }
 
-// G = records per work item (2: the 8-query form); A.max_items counts WORK ITEMS, the workspace holds G records each
-template <int NF, int NH, bool FILTER, int NQ = 0, int G = 1>
-static int launch_pq_scan_rot_t(const PQScan8Args& A, int bpw, void* desc_ws, int log_cap, hipStream_t st) {
-    constexpr int M = 64 * NF + 32 * NH + 16 * NQ;
-    // tables | 2 x G item records (176 B each) + pacing words | sibling progress [64]
-    const size_t shm = (size_t)(G == 2 ? 2 : NF + NH + NQ) * 65536 + (size_t)((2 * G * 176 + 8 + 31) & ~31) + 256;
+// The one host launcher of the work-item scans: Kernel = a scan kernel instantiation (the static DevOnce below is therefore one
+// per instantiation), M / FILTER pick its k_pq_rot_items, G = records per work item (A.max_items counts WORK ITEMS, the workspace
+// holds G records each).  shm = the kernel's dynamic LDS; tail = its arguments behind (A, items, log_keys, seg_desc, xcd_ctr
+// [, prog — PROG: the kernel reads the sibling-progress words]).
+template <auto Kernel, int M, int G, bool FILTER, bool PROG = false, typename... Tail>
+static int launch_item_scan(const PQScan8Args& A, size_t shm, void* desc_ws, int log_cap, hipStream_t st, Tail... tail) {
     static DevOnce once;
     static std::atomic<int> failed{0};
     once.once([&] {
-        if (hipFuncSetAttribute((const void*)k_pq_scan_rot<NF, NH, FILTER, NQ, G>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm) != hipSuccess) failed = 1;
+        if (hipFuncSetAttribute((const void*)Kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm) != hipSuccess) failed = 1;
     });
     if (failed) return -1;
     const int nwg = pq_scan_rot_max_wgs(M);
@@ -1696,98 +1582,38 @@ static int launch_pq_scan_rot_t(const PQScan8Args& A, int bpw, void* desc_ws, in
     uint32_t* xcd_ctr = pq_scan_rot_ws_ctr(desc_ws, recs, log_cap, nwg * G);
     uint32_t* prog = xcd_ctr + 256;
     { const int ll_ = A.nlist + 1 <= 12288 ? A.nlist + 1 : 0; hipLaunchKernelGGL((k_pq_rot_items<M, FILTER>), dim3((unsigned)((recs + 255) / 256)), dim3(256), (size_t)ll_ * 4, st, A, items, xcd_ctr, prog, G, ll_); }
-    static const int var = measure_env("RSX_ROT_VARIANT", 0);
     // one persistent workgroup per CU; never more than the work items
     int64_t grid = nwg;
     if (grid > ((A.max_items + 7) & ~7)) grid = (A.max_items + 7) & ~7;
-    hipLaunchKernelGGL((k_pq_scan_rot<NF, NH, FILTER, NQ, G>), dim3((unsigned)grid), dim3(1024), shm, st, A, items, log_keys, seg_desc, xcd_ctr, prog,
-                       log_cap, bpw, A.pace, var);
+    if constexpr (PROG) hipLaunchKernelGGL(Kernel, dim3((unsigned)grid), dim3(1024), shm, st, A, items, log_keys, seg_desc, xcd_ctr, prog, tail...);
+    else hipLaunchKernelGGL(Kernel, dim3((unsigned)grid), dim3(1024), shm, st, A, items, log_keys, seg_desc, xcd_ctr, tail...);
     if (FILTER && !A.qitems)     // with qitems the runs are consumed in place by k_pq_gather_select
         hipLaunchKernelGGL(k_pq_rot_compact, dim3((unsigned)((recs + ROT_CW - 1) / ROT_CW)), dim3(64 * ROT_CW), 0, st, items, A.total_items, G, log_keys, seg_desc,
                            A.cand, A.cand_cnt, A.cand_cap);
     return 0;
 }
 
+// the four families: dynamic LDS and trailing kernel arguments
+template <int NF, int NH, bool FILTER, int NQ = 0, int G = 1>
+static int launch_pq_scan_rot_t(const PQScan8Args& A, int bpw, void* desc_ws, int log_cap, hipStream_t st) {
+    // tables | 2 x G item records (176 B each) + pacing words | sibling progress [64]
+    const size_t shm = (size_t)(G == 2 ? 2 : NF + NH + NQ) * 65536 + (size_t)((2 * G * 176 + 8 + 31) & ~31) + 256;
+    static const int var = measure_env("RSX_ROT_VARIANT", 0);
+    return launch_item_scan<k_pq_scan_rot<NF, NH, FILTER, NQ, G>, 64 * NF + 32 * NH + 16 * NQ, G, FILTER, true>(A, shm, desc_ws, log_cap, st, log_cap, bpw, A.pace, var);
+}
 // 4-query records per work item of the filtered scan: M = 16: sixteen queries (k_pq_scan_rot16); M = 64 with the 8-byte-entry table
 // (q8): eight (k_pq_scan_rot<1, 0, true, 0, 2>)
 int pq_scan_rot_ngq(int M, bool filtered, int q8) { return !filtered ? 1 : M == 16 ? R16_G : (M == 64 && q8) ? 2 : 1; }
 static int launch_pq_scan_rot16(const PQScan8Args& A, int bpw, void* desc_ws, int log_cap, hipStream_t st) {
-    constexpr int G = R16_G;
-    const size_t shm = (size_t)2 * 65536 + (size_t)2 * G * 176 + 64;
-    static DevOnce once;
-    static std::atomic<int> failed{0};
-    once.once([&] {
-        if (hipFuncSetAttribute((const void*)k_pq_scan_rot16, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm) != hipSuccess) failed = 1;
-    });
-    if (failed) return -1;
-    const int nwg = pq_scan_rot_max_wgs(16);
-    const int64_t recs = (int64_t)A.max_items * G;
-    PQRotItem* items = reinterpret_cast<PQRotItem*>(desc_ws);
-    uint2* seg_desc = pq_scan_rot_ws_desc(desc_ws, recs);
-    uint64_t* log_keys = pq_scan_rot_ws_keys(desc_ws, recs);
-    uint32_t* xcd_ctr = pq_scan_rot_ws_ctr(desc_ws, recs, log_cap, nwg * G);
-    uint32_t* prog = xcd_ctr + 256;
-    { const int ll_ = A.nlist + 1 <= 12288 ? A.nlist + 1 : 0; hipLaunchKernelGGL((k_pq_rot_items<16, true>), dim3((unsigned)((recs + 255) / 256)), dim3(256), (size_t)ll_ * 4, st, A, items, xcd_ctr, prog, G, ll_); }
-    int64_t grid = nwg;
-    if (grid > ((A.max_items + 7) & ~7)) grid = (A.max_items + 7) & ~7;
-    hipLaunchKernelGGL(k_pq_scan_rot16, dim3((unsigned)grid), dim3(1024), shm, st, A, items, log_keys, seg_desc, xcd_ctr, log_cap, bpw);
-    if (!A.qitems)
-        hipLaunchKernelGGL(k_pq_rot_compact, dim3((unsigned)((recs + ROT_CW - 1) / ROT_CW)), dim3(64 * ROT_CW), 0, st, items, A.total_items, G, log_keys, seg_desc,
-                           A.cand, A.cand_cnt, A.cand_cap);
-    return 0;
+    return launch_item_scan<k_pq_scan_rot16, 16, R16_G, true>(A, (size_t)2 * 65536 + (size_t)2 * R16_G * 176 + 64, desc_ws, log_cap, st, log_cap, bpw);
 }
-
 template <int NS, int NB, int RD>
 static int launch_pq_scan_sl8_t(const PQScan8Args& A, int vpl, void* desc_ws, int log_cap, hipStream_t st) {
-    constexpr int G = 2, M = 32 * NS;
-    const size_t shm = (size_t)2 * 65536 + (size_t)2 * G * 176 + 64;
-    static DevOnce once;
-    static std::atomic<int> failed{0};
-    once.once([&] {
-        if (hipFuncSetAttribute((const void*)k_pq_scan_sl8<NS, NB, RD>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm) != hipSuccess) failed = 1;
-    });
-    if (failed) return -1;
-    const int nwg = pq_scan_rot_max_wgs(M);
-    const int64_t recs = (int64_t)A.max_items * G;
-    PQRotItem* items = reinterpret_cast<PQRotItem*>(desc_ws);
-    uint2* seg_desc = pq_scan_rot_ws_desc(desc_ws, recs);
-    uint64_t* log_keys = pq_scan_rot_ws_keys(desc_ws, recs);
-    uint32_t* xcd_ctr = pq_scan_rot_ws_ctr(desc_ws, recs, log_cap, nwg * G);
-    uint32_t* prog = xcd_ctr + 256;
-    { const int ll_ = A.nlist + 1 <= 12288 ? A.nlist + 1 : 0; hipLaunchKernelGGL((k_pq_rot_items<M, true>), dim3((unsigned)((recs + 255) / 256)), dim3(256), (size_t)ll_ * 4, st, A, items, xcd_ctr, prog, G, ll_); }
-    int64_t grid = nwg;
-    if (grid > ((A.max_items + 7) & ~7)) grid = (A.max_items + 7) & ~7;
-    hipLaunchKernelGGL((k_pq_scan_sl8<NS, NB, RD>), dim3((unsigned)grid), dim3(1024), shm, st, A, items, log_keys, seg_desc, xcd_ctr, log_cap, 32 * vpl);
-    if (!A.qitems)
-        hipLaunchKernelGGL(k_pq_rot_compact, dim3((unsigned)((recs + ROT_CW - 1) / ROT_CW)), dim3(64 * ROT_CW), 0, st, items, A.total_items, G, log_keys, seg_desc,
-                           A.cand, A.cand_cnt, A.cand_cap);
-    return 0;
+    return launch_item_scan<k_pq_scan_sl8<NS, NB, RD>, 32 * NS, 2, true>(A, (size_t)2 * 65536 + (size_t)2 * 2 * 176 + 64, desc_ws, log_cap, st, log_cap, 32 * vpl);
 }
-
 template <int NS>
 static int launch_pq_scan_sl4_t(const PQScan8Args& A, int vpl, void* desc_ws, int log_cap, hipStream_t st) {
-    constexpr int M = 32 * NS;
-    const size_t shm = (size_t)((NS + 1) / 2) * 65536 + (size_t)2 * 176 + 64;
-    static DevOnce once;
-    static std::atomic<int> failed{0};
-    once.once([&] {
-        if (hipFuncSetAttribute((const void*)k_pq_scan_sl4<NS>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm) != hipSuccess) failed = 1;
-    });
-    if (failed) return -1;
-    const int nwg = pq_scan_rot_max_wgs(M);
-    PQRotItem* items = reinterpret_cast<PQRotItem*>(desc_ws);
-    uint2* seg_desc = pq_scan_rot_ws_desc(desc_ws, A.max_items);
-    uint64_t* log_keys = pq_scan_rot_ws_keys(desc_ws, A.max_items);
-    uint32_t* xcd_ctr = pq_scan_rot_ws_ctr(desc_ws, A.max_items, log_cap, nwg);
-    uint32_t* prog = xcd_ctr + 256;
-    { const int ll_ = A.nlist + 1 <= 12288 ? A.nlist + 1 : 0; hipLaunchKernelGGL((k_pq_rot_items<M, true>), dim3((unsigned)((A.max_items + 255) / 256)), dim3(256), (size_t)ll_ * 4, st, A, items, xcd_ctr, prog, 1, ll_); }
-    int64_t grid = nwg;
-    if (grid > ((A.max_items + 7) & ~7)) grid = (A.max_items + 7) & ~7;
-    hipLaunchKernelGGL((k_pq_scan_sl4<NS>), dim3((unsigned)grid), dim3(1024), shm, st, A, items, log_keys, seg_desc, xcd_ctr, log_cap, 32 * vpl);
-    if (!A.qitems)
-        hipLaunchKernelGGL(k_pq_rot_compact, dim3((unsigned)((A.max_items + ROT_CW - 1) / ROT_CW)), dim3(64 * ROT_CW), 0, st, items, A.total_items, 1, log_keys, seg_desc,
-                           A.cand, A.cand_cnt, A.cand_cap);
-    return 0;
+    return launch_item_scan<k_pq_scan_sl4<NS>, 32 * NS, 1, true>(A, (size_t)((NS + 1) / 2) * 65536 + (size_t)2 * 176 + 64, desc_ws, log_cap, st, log_cap, 32 * vpl);
 }
 
 // returns 0 on launch, -1 if this M has no rotated kernel.  tau_key == null: unfiltered (every score to a.temp).

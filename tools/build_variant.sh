@@ -7,7 +7,8 @@ tag=$1; src=$2; shift 2
 make -s -j8
 hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -Wno-unused-value -Wno-pass-failed "$@" -c "$src" -o "/tmp/${src%.hip}.$tag.o"
 objs=""
-for o in k_select.o k_misc.o k_gemm.o k_pq.o k_pq_rot.o api_build.o api_search.o api_sharded.o rsx_api.o; do
+# the objects of the regular library, from the Makefile's own list
+for o in $(make -s print-objs); do
   if [ "$o" = "${src%.hip}.o" ]; then objs="$objs /tmp/${src%.hip}.$tag.o"; else objs="$objs $o"; fi
 done
 hipcc --offload-arch=gfx950 -shared -fPIC -o "librsx_$tag.so" $objs
