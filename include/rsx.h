@@ -46,7 +46,7 @@ enum rsx_status {
 
 enum rsx_metric { RSX_METRIC_INNER_PRODUCT = 0, RSX_METRIC_L2 = 1 }; /* = faiss.METRIC_* */
 enum rsx_dtype { RSX_F32 = 0, RSX_F16 = 1 };
-enum rsx_kind { RSX_KIND_FLAT = 0, RSX_KIND_IVFFLAT = 1, RSX_KIND_IVFPQ = 2 };
+enum rsx_kind { RSX_KIND_FLAT = 0, RSX_KIND_IVFFLAT = 1, RSX_KIND_IVFPQ = 2, RSX_KIND_PQ = 3 };
 
 /* Thread-local message of the last error raised on the calling thread ("" if none). */
 const char* rsx_last_error(void);
@@ -73,6 +73,22 @@ int rsx_ivfflat_create(int d, int nlist, int metric, int device, rsx_index_t** o
  * RSX_METRIC_L2 (round 6) ranks by the squared distance to the decoded vector c_l + r^ — a table per (query, list) pair, so it
  * is served by the exact scan (k_pq_scan_l2), every code layout, any k <= 4096 (tests/test_gpu_ivf.py::test_ivfpq_l2_metric_vs_oracle). */
 int rsx_ivfpq_create(int d, int nlist, int M, int nbits, int metric, int device, rsx_index_t** out);
+
+/* faiss.IndexPQ(d, M, nbits, METRIC_INNER_PRODUCT) — contriever/src/index.py:19,28-30,42,53,62 (the vendored Indexer behind
+ * passage_retrieval.py --n_subquantizers; ric/conf/a100.yaml:67 index_type: PQ).  FAISS 1.8.0 IndexPQ: a flat product quantiser, no
+ * coarse stage.  nbits must be 8, d % M == 0, d / M <= 160.  train = ProductQuantizer::train on the vectors themselves (the
+ * library's subsample and seed); add = per-subspace nearest codeword, sequential ids (ids must be NULL: IndexFlatCodes has no
+ * add_with_ids); search scores EVERY stored code with the query's table — inner product: the fp32 sum of the M table entries in
+ * sub-quantiser order, best first; L2: squared distance to the decoded vector, ascending; equal scores by id ascending.
+ * Inner product takes the staged filtered scan: every query scans every code against its 8-bit table in
+ * stages over disjoint tile sets, the per-query threshold rising between stages, then the exact re-score and certificate of the
+ * IVF-PQ fast scan; device memory beside the codes does not grow with ntotal.  L2 and the layouts without a work-item scan take
+ * the exact scans; past 2 GiB of codes in the one list only the staged scan and the exact scans of the rotated / sliced layouts (and L2)
+ * are served, any other routing of a search is refused (RSX_ERR_UNSUPPORTED).  rsx_get "kind" = RSX_KIND_PQ; list calls see ONE list (number 0) in insertion order.  Refused with a message:
+ * selectors (RSX_ERR_UNSUPPORTED, as FAISS 1.8.0's IndexPQ::search refuses search parameters), rsx_remove_ids and sharded
+ * handles of this kind (RSX_ERR_UNSUPPORTED), "add_list_mod", rsx_set_nprobe, rsx_assign, rsx_reserve_lists,
+ * rsx_set_centroids / rsx_get_centroids (RSX_ERR_INVALID). */
+int rsx_pq_create(int d, int M, int nbits, int metric, int device, rsx_index_t** out);
 
 /* ONE handle over several GPUs of the node, single process — SURVEY.md 8(b)/(e).  The reference's offline driver makes one
  * index.search(all_queries, k) call (src/search.py:296) and its serving tier fans a query out to shard workers over HTTP and
@@ -208,7 +224,8 @@ int rsx_get(rsx_index_t* h, const char* key, int64_t* out);
  * the score rows of the batch would exceed ~2 GB [default], 2 = always, 0 = never = full score rows), "pq_prepass_fused" (filtered fast scan: 1 = threshold pre-pass in one launch [default], 0 = grouping +
  * scan + selection launches), "lut_tiled" (IVFPQ fast scan, dsub = 8: 1 = 8-bit tables built by
  * codebook-slice tiles shared by 32 queries [default], 0 = one workgroup per query), "flat_filter" (Flat: 1 = one filtered GEMM launch after the first chunk [default], 0 = score buffer
- * per chunk), "profile" (1 = record stage timings with HIP
+ * per chunk), "pq_flat_first" / "pq_flat_growth" / "pq_flat_max_stages" (IndexPQ staged scan: rows of the first stage, 0 =
+ * default; percent by which each stage outgrows the one before, 0 = default 300; most stages, 0 = default 12), "profile" (1 = record stage timings with HIP
  * events on the library's stream; 2 = additionally count the vectors each search scanned). */
 /* Build-time knob (IVF indexes, before the first add): "add_list_mod" = N, "add_list_rem" = r make this handle a LIST
  * shard of an N-way multi-GPU index: rsx_add assigns every vector of the stream (sequential ids keep counting all
@@ -219,8 +236,8 @@ int rsx_set_param(rsx_index_t* h, const char* key, double value);
 
 /* HIP-event timings (ms) of the stages of the last rsx_search on this handle when
  * "profile"=1: "coarse", "select_probe", "lut", "scan", "select", "finalize", "total",
- * "scan_launches", "fast_queries", "fallback_queries" (certificate failures re-run exactly) and (profile 2)
- * "scanned_vectors".  Used by bench.py for the roofline object. */
+ * "scan_launches", "fast_queries", "fallback_queries" (certificate failures re-run exactly), "pq_flat_stages" (IndexPQ: stages
+ * of the staged filtered scan, summed over the internal batches) and (profile 2) "scanned_vectors", "cand_keys", "cand_keys_max".  Used by bench.py for the roofline object. */
 int rsx_get_timing(rsx_index_t* h, const char* key, double* ms);
 
 /* ---- filtered search (FAISS SearchParameters with an IDSelector) ------------------- */

@@ -22,7 +22,7 @@ int64_t workspace_bytes(const rsx_index* h) {
     const DevBuf* bufs[] = {&h->w_q32, &h->w_q16, &h->w_coarse, &h->w_keys1, &h->w_probekeys, &h->w_probelist, &h->w_dis0, &h->w_segstart,
                             &h->w_temp, &h->w_lut, &h->w_lutws, &h->w_state, &h->w_D, &h->w_I, &h->w_qin, &h->w_pairs, &h->w_flag, &h->w_x,
                             &h->w_partial, &h->w_assign, &h->w_dest, &h->w_idsin, &h->w_misc, &h->w_lut8, &h->w_qparam, &h->w_uncertain,
-                            &h->w_fbq, &h->w_fbD, &h->w_fbI, &h->w_cand, &h->w_candcnt, &h->w_itemdesc, &h->w_tau, &h->w_excl, &h->w_state2, &h->w_addcnt, &h->w_addstart, &h->w_qitems, &h->w_tiews, &h->sh_D, &h->sh_I, &h->sh_q,
+                            &h->w_fbq, &h->w_fbD, &h->w_fbI, &h->w_cand, &h->w_candcnt, &h->w_itemdesc, &h->w_tau, &h->w_excl, &h->w_state2, &h->w_addcnt, &h->w_addstart, &h->w_qitems, &h->w_tiews, &h->w_stagedir, &h->sh_D, &h->sh_I, &h->sh_q,
                             &h->sh_oD, &h->sh_oI, &h->sel_mask, &h->sel_dev, &h->codes_plain /* derived from the payload on demand, dropped by the next add */};
     int64_t t = 0;
     for (const DevBuf* b : bufs) t += (int64_t)b->bytes;
@@ -195,6 +195,16 @@ rsx_index* create_common(int kind, int d, int nlist, int M, int nbits, int metri
     h->h_base.assign((size_t)h->nlist, 0);
     h->h_len.assign((size_t)h->nlist, 0);
     h->h_cap.assign((size_t)h->nlist, 0);
+    update_trained(h.get());
+    return h.release();
+}
+
+// faiss.IndexPQ: one list, zero centroid (rsx_index::flat_pq); trained once the codebooks are there
+rsx_index* create_flat_pq(int d, int M, int nbits, int metric, int device) {
+    std::unique_ptr<rsx_index> h(create_common(KIND_IVFPQ, d, 1, M, nbits, metric, device));
+    h->flat_pq = true;
+    const std::vector<float> zero((size_t)d, 0.0f);
+    set_centroids(h.get(), zero.data());
     update_trained(h.get());
     return h.release();
 }
@@ -429,7 +439,11 @@ void train_impl(rsx_index* h, int64_t n, const void* x, int dtype) {
     std::vector<float> cen((size_t)h->nlist * d), cb;
     DevBuf dcen;                                  // the new centroids on the device, for the PQ stage
     // ---- coarse quantiser: k-means, IP assignment, spherical centroids, niter 10, <=256 pts/centroid
-    {
+    if (h->flat_pq) {      // IndexPQ: no coarse stage — the zero centroid stays, the codebooks are trained on the vectors themselves (x - 0 = x)
+        std::fill(cen.begin(), cen.end(), 0.0f);
+        dcen.ensure((size_t)d * 4);
+        HIPCHECK(hipMemsetAsync(dcen.p, 0, (size_t)d * 4, h->st));
+    } else {
         const int k = h->nlist;
         int64_t keep = (int64_t)k * 256;
         std::vector<float> xs;
@@ -619,7 +633,7 @@ void save_impl(rsx_index* h, const char* path) {
     try {
         FileHeader hd{};
         memcpy(hd.magic, "RSX1", 4);
-        hd.version = 2; hd.kind = h->kind; hd.d = h->d; hd.metric = h->metric; hd.nlist = h->nlist; hd.M = h->M;
+        hd.version = 2; hd.kind = public_kind(h); hd.d = h->d; hd.metric = h->metric; hd.nlist = h->nlist; hd.M = h->M;
         hd.nbits = h->nbits; hd.trained = h->trained; hd.storage_f16 = h->storage_f16; hd.custom_ids = h->custom_ids;
         hd.nprobe = h->nprobe; hd.ntotal = h->ntotal;
         wr(f, &hd, sizeof(hd));
@@ -673,7 +687,7 @@ rsx_index* load_impl(const char* path, int device) {
         FileHeader hd{};
         rd(f, &hd, sizeof(hd));
         if (memcmp(hd.magic, "RSX1", 4) != 0) RSX_THROW(RSX_ERR_IO, "%s is not an RSX1 index file", path);
-        h = create_common(hd.kind, hd.d, hd.nlist, hd.M, hd.nbits, hd.metric, device);
+        h = hd.kind == 3 ? create_flat_pq(hd.d, hd.M, hd.nbits, hd.metric, device) : create_common(hd.kind, hd.d, hd.nlist, hd.M, hd.nbits, hd.metric, device);
         h->nprobe = hd.nprobe;
         FileHeaderV2 h2{0, 1, 0};
         if (hd.version >= 2) rd(f, &h2, sizeof(h2));

@@ -155,6 +155,7 @@ struct BatchPlan {
     int nprobe, pad_to;        // IVF: probed lists per query; list padding of the score rows
     int64_t tmax, maxlen;      // IVF: a query's score row (the nprobe longest padded lists, at least 256) and the longest of those lists
     bool needs_score_rows;     // the IVF-PQ fast scan with in-kernel filtering and the one-launch threshold pre-pass never writes a score row
+    bool staged;               // IndexPQ (rsx_index::flat_pq): the staged filtered scan over the one list (pq_staged_scan)
 };
 static BatchPlan plan_batch(rsx_index* h, int64_t nq, const void* dq, int dtype, int k, bool allow_fast) {
     BatchPlan P{};
@@ -167,7 +168,10 @@ static BatchPlan plan_batch(rsx_index* h, int64_t nq, const void* dq, int dtype,
     // filtered scan behind the one-launch pre-pass (every other setting takes the exact scan)
     P.fast = allow_fast && pq && h->metric == RSX_METRIC_INNER_PRODUCT && h->pq_fast != 0 && h->scan_kernel == 0 && (h->CB == 16 || pq_rot_family(h->CB)) && h->M * 255 < 65536;
     if (P.fast) { kp_for(h, k, true, P.KP, P.BUF); if (P.KP > 4096) P.fast = false; }
-    if (P.fast && P.sliced && !(P.nprobe > 1 && P.pq_filter != 0 && h->pq_prepass_fused != 0)) P.fast = false;
+    // IndexPQ: one list scanned by every query — the work-item scans of the block layouts, in stages (no score rows).  Every
+    // other layout and setting of such a handle takes the one-list IVF-PQ routes (score rows cut by the temp budget) and is as correct
+    P.staged = P.fast && h->flat_pq && P.rot && P.pq_filter != 0 && h->pq_prepass_fused != 0 && h->M == h->Mpad && pq_rot_applies(h->M);
+    if (P.fast && P.sliced && !((P.nprobe > 1 || P.staged) && P.pq_filter != 0 && h->pq_prepass_fused != 0)) P.fast = false;
     kp_for(h, k, P.fast, P.KP, P.BUF);
     P.certify = h->kind != KIND_IVFPQ && allow_fast && h->flat_cert != 0;
     // fast coarse quantiser (round 6): fp16 MFMA scores of all lists + exact chains of the candidates; needs the re-run machinery behind it
@@ -183,7 +187,7 @@ static BatchPlan plan_batch(rsx_index* h, int64_t nq, const void* dq, int dtype,
     // the finalize-from-the-row kernel (k_pq_final_tab) will serve this batch: let the table builder store the fp32 tables for it
     // (M KiB per query, 100 MB at M = 96 / batch 1024) instead of every query's workgroup re-deriving its table from the 786 KB codebook
     P.tab_expected = P.pq_fused_lut && P.rot && h->pq_final_tab != 0 && (h->pq_final_tab == 2 || P.KP >= 512 || h->dsub > 8) &&
-                     P.nprobe > 1 && P.pq_filter != 0 && h->pq_prepass_fused != 0 && pq_final_tab_capacity(h->M, h->CB, k) > 0;
+                     (P.nprobe > 1 || P.staged) && P.pq_filter != 0 && h->pq_prepass_fused != 0 && pq_final_tab_capacity(h->M, h->CB, k) > 0;
     // the matrix-core table build will serve this batch and the fast coarse quantiser runs: its first pass rides in the probe-pick launch
     P.lut_pass0_early = P.coarse_fast && P.pq_fused_lut && !P.side_lut && h->dsub == 8 && h->lut_tiled >= 2 && h->metric == RSX_METRIC_INNER_PRODUCT &&
                         h->pq_lut_early != 0;
@@ -200,7 +204,7 @@ static BatchPlan plan_batch(rsx_index* h, int64_t nq, const void* dq, int dtype,
     // score rows [nq, tmax]: every path but the filtered IVF-PQ fast scan with the one-launch pre-pass fills (part of) them.  At the
     // reference's nprobe 512 a row is 35 MB: allocating it unconditionally used to cut a 1024-query batch into four internal
     // batches (round 4: 4x the fixed stages, a quarter of the queries per list group)
-    P.needs_score_rows = !(P.fast && P.nprobe > 1 && P.pq_filter != 0 && h->pq_prepass_fused != 0);
+    P.needs_score_rows = !(P.fast && (P.nprobe > 1 || P.staged) && P.pq_filter != 0 && h->pq_prepass_fused != 0);
     return P;
 }
 // Keys a query's candidate row can hold (filtered IVF-PQ fast scan, filtered IVF-Flat list scan).  The IVF-PQ threshold is valid by
@@ -355,6 +359,11 @@ static void check_supported(rsx_index* h, const BatchPlan& P) {
     if (h->kind == KIND_FLAT) return;
     if (P.nprobe > 4096) RSX_THROW(RSX_ERR_UNSUPPORTED, "search: %d probed lists per query exceed this build's maximum of 4096", P.nprobe);
     if (P.tmax >= ((int64_t)1 << 32)) RSX_THROW(RSX_ERR_UNSUPPORTED, "probed lists exceed 2^32 vectors per query");
+    // IndexPQ: ONE list.  The list-wide scans address a list's codes with 32-bit byte offsets (an inverted list never comes near 2 GiB); past
+    // that only the routes that do not are served: the staged scan (a tile per item), k_pq_scan_rot_exact and k_pq_scan_l2 (64-bit row addresses)
+    if (h->flat_pq && h->h_len[0] * (int64_t)h->Mpad >= ((int64_t)1 << 31) && !(P.staged || (!P.fast && (P.rot || h->metric == RSX_METRIC_L2))))
+        RSX_THROW(RSX_ERR_UNSUPPORTED, "IndexPQ: %lld x %d bytes of codes are served by the staged scan and the exact scans of the rotated / sliced layouts only "
+                  "(this search was routed elsewhere: M = %d, pq_layout, pq_fast / pq_filter / scan_kernel)", (long long)h->h_len[0], h->Mpad, h->M);
 }
 // Round 4 (overlap = 1, no longer the default): the 8-bit tables depend on the queries only — their build starts here on the side
 // stream and runs beside the coarse quantiser and the probe selection; the per-query parameters (k_pq_qparam: they need the coarse
@@ -671,6 +680,7 @@ static PqGeometry pq_geometry(const rsx_index* h, const BatchPlan& P, bool filte
 }
 // the one-launch threshold pre-pass behind the table build (and the pair grouping where it rides along); the two-call search parks
 // behind it.  Returns whether the pairs are grouped already
+// (staged flat scan: no pairs to group, no emission — its stages scan every tile — and no parking: the thresholds keep moving)
 static bool pq_prepass(rsx_index* h, const BatchPlan& P, BatchResult& R, const PairArea& pr, const PqGeometry& g, void* lut_ws, StageTimer& tm) {
     const int64_t nq = P.nq; const int nlist = h->nlist;
     R.cand_cap = alloc_cand_rows(h, P, h->M);
@@ -681,11 +691,11 @@ static bool pq_prepass(rsx_index* h, const BatchPlan& P, BatchResult& R, const P
     pa.nprobe = P.nprobe; pa.Mpad = h->Mpad; pa.pre_rows = g.pre_rows; pa.KP = P.KP; pa.CB = h->CB; pa.k = P.k;
     pa.state = h->w_state.as<uint64_t>(); pa.cand_cnt = h->w_candcnt.as<unsigned long long>();
     h->w_tau.ensure((size_t)nq * 8); pa.tau = h->w_tau.as<uint64_t>();
-    if (P.rot) {       // the sample's own candidates leave from the pre-pass; the scan drops that (query, list, tile 0)
+    if (P.rot && !P.staged) {       // the sample's own candidates leave from the pre-pass; the scan drops that (query, list, tile 0)
         h->w_excl.ensure((size_t)nq * 2);
         pa.cand = h->w_cand.as<uint64_t>(); pa.cand_cap = R.cand_cap; pa.tile_rows = g.tile_rows; pa.excl = h->w_excl.as<uint16_t>();
     }
-    const bool group_in_tables = lut_ws && !P.side_lut && h->lut_tiled >= 2 && h->pq_group_fused != 0 && pr.npairs <= PG_MAX_PAIRS &&
+    const bool group_in_tables = !P.staged && lut_ws && !P.side_lut && h->lut_tiled >= 2 && h->pq_group_fused != 0 && pr.npairs <= PG_MAX_PAIRS &&
                                  nlist <= PG_BLOCKS * PG_MAX_LPB;
     PairGroupArgs pg{};
     bool grouped = false;
@@ -700,7 +710,7 @@ static bool pq_prepass(rsx_index* h, const BatchPlan& P, BatchResult& R, const P
         grouped = true;
     }
     build_pq_tables(h, P, lut_ws, group_in_tables ? &pg : nullptr, tm);
-    if (P.side_lut) {       // the (list, tile, group) work items of the scan: built beside the pre-pass (they need the probes only)
+    if (P.side_lut && !P.staged) {       // the (list, tile, group) work items of the scan: built beside the pre-pass (they need the probes only)
         HIPCHECK(hipStreamWaitEvent(h->st2, h->ev_probe, 0));
         pr.group(h, 4 * P.ngq, g.tile_rows, P.nprobe, 0, h->st2);
         HIPCHECK(hipEventRecord(h->ev_group, h->st2));
@@ -711,7 +721,7 @@ static bool pq_prepass(rsx_index* h, const BatchPlan& P, BatchResult& R, const P
     if (!(g.pre4 && launch_pq_prepass4(pa, nq, h->st) == 0) && !(pre4big && launch_pq_prepass4_big(pa, nq, h->st) == 0))
         launch_pq_prepass(pa, nq, h->st);
     R.fused_pre_used = true;
-    if (h->tc && h->tc->active && P.allow_fast && std::this_thread::get_id() == h->tc->worker) {
+    if (!P.staged && h->tc && h->tc->active && P.allow_fast && std::this_thread::get_id() == h->tc->worker) {
         // two-call search: the thresholds are final on the device; hand them to the caller and wait for rsx_search_scan
         HIPCHECK(hipStreamSynchronize(h->st));
         rsx_index::TwoCall& t = *h->tc; std::unique_lock<std::mutex> lk(t.mu);
@@ -774,6 +784,93 @@ static bool pq_filtered_scan(rsx_index* h, const BatchPlan& P, BatchResult& R, P
                                            pr.total_groups, pr.item_off, pr.total_items, nlist, mi, g.vpl, tau_ptr, tau_stride,
                                            h->w_cand.as<uint64_t>(), h->w_candcnt.as<unsigned long long>(), R.cand_cap, h->st)) == 0;
 }
+// IndexPQ (faiss.IndexPQ: one list, every query scans every code): the staged filtered scan.  The filtered IVF-PQ scan takes ONE threshold
+// from a sample of its closest list; over N rows in exchangeable order a threshold from R0 rows lets ~N k / R0 rows through — 49 000 per
+// query at N = 10M, k = 10, R0 = 2048, three candidate rows' worth.  Here the threshold tightens while the scan runs, as the staged Flat
+// GEMM's does (flat_staged): stage s scans a SET of the list's tiles with tau_s (work items of that set only: k_pq_rot_items' tile-set
+// form, the work-item scans unchanged), k_pq_stage_gather moves the survivors into the candidate rows, derives tau_(s+1) = max(tau_s,
+// a_k - 2 eps) from the row's k-th best approximate key and compacts the row to it.  Stage sizes grow geometrically (each stage
+// `growth` times the rows scanned before it: ~k growth new rows per query and stage beside the 2 eps band), and the tiles of a stage
+// are spread over the whole list (tile number j -> (j mul) mod T, mul ~ 0.618 T coprime to T), so a corpus added source by source or in
+// sorted order meets every stage with a sample of all of it.  After the last stage the row holds every vector whose approximate score
+// reaches the final tau — the invariant k_pq_final_tab / k_finalize and the second chance rely on; an overflowed row or log flags its
+// query alone for the exact re-run.  Beside the codes nothing grows with N: candidate rows (cand_row_cap), survivor logs, one stage's items.
+static void pq_staged_scan(rsx_index* h, const BatchPlan& P, BatchResult& R, PQScanArgs& a, PqGeometry g, void* lut_ws, StageTimer& tm) {
+    const int64_t nq = P.nq, N = h->h_len[0];
+    // tiles: at least 64 of them where the index allows it (the stages need something to grow over), never more rows than the work-item scans' largest tile
+    int vpl = h->scan_chunk > 0 ? g.vpl : 32;
+    if (h->scan_chunk <= 0) while (vpl > 1 && (N + 1024 * vpl - 1) / (1024 * vpl) < 64) vpl /= 2;
+    g.vpl = vpl; g.tile_rows = 1024 * vpl;
+    const int T = (int)std::max<int64_t>(1, (N + g.tile_rows - 1) / g.tile_rows);
+    const PairArea none(h, 0, 1, 1);
+    pq_prepass(h, P, R, none, g, lut_ws, tm);
+    tm.mark("scan0");
+    // the stage boundaries, in tiles
+    const double growth = (h->pq_flat_growth > 0 ? h->pq_flat_growth : 300) / 100.0;
+    const int max_stages = h->pq_flat_max_stages > 0 ? h->pq_flat_max_stages : 12;
+    const int64_t first_rows = h->pq_flat_first > 0 ? h->pq_flat_first : std::max<int64_t>(65536, (int64_t)4 * g.pre_rows);
+    const int c0 = (int)std::min<int64_t>(T, std::max<int64_t>(1, (first_rows + g.tile_rows - 1) / g.tile_rows));
+    double ratio = 1.0 + growth;
+    if (T > c0 && max_stages > 1 && std::log((double)T / c0) / std::log(ratio) > max_stages - 1) ratio = std::pow((double)T / c0, 1.0 / (max_stages - 1));
+    std::vector<int> ends;      // ends[s]: tiles scanned once stage s is done; a stage never holds more tiles than the gather's LDS describes
+    {
+        double c = c0;
+        for (int prev = 0; prev < T;) {
+            const int want = max_stages == 1 ? T : (int)std::min<double>(T, std::ceil(c));
+            const int e = std::min(std::max(want, prev + 1), prev + PQ_STAGE_MAX_TILES);
+            ends.push_back(e); prev = e;
+            if (e >= want) c *= ratio;
+        }
+    }
+    const int S = (int)ends.size();
+    int tmax = 0;
+    for (int s_ = 0; s_ < S; s_++) tmax = std::max(tmax, ends[(size_t)s_] - (s_ ? ends[(size_t)s_ - 1] : 0));
+    int mul = (int)std::llround(0.6180339887 * T);
+    if (mul < 1) mul = 1;
+    auto gcd = [](int x, int y) { while (y) { const int t = x % y; x = y; y = t; } return x; };
+    while (gcd(mul, T) != 1) mul++;
+    // the work items of a stage: every group of G queries x the stage's tiles.  One list, so the pair grouping is known on the host: the pairs
+    // in query order, one entry of pair_off / group_off, and per stage item_off = {0, groups x tiles}
+    const int G = 4 * P.ngq, ng = (int)((nq + G - 1) / G);
+    std::vector<int32_t>& hd = h->stage_host;
+    hd.assign((size_t)nq + 8 + (size_t)4 * S, 0);
+    for (int64_t i = 0; i < nq; i++) hd[(size_t)i] = (int32_t)i;
+    hd[(size_t)nq + 1] = (int32_t)nq; hd[(size_t)nq + 3] = ng; hd[(size_t)nq + 4] = ng;
+    for (int s_ = 0; s_ < S; s_++) {
+        const int nt = ends[(size_t)s_] - (s_ ? ends[(size_t)s_ - 1] : 0);
+        hd[(size_t)nq + 8 + (size_t)4 * s_ + 1] = ng * nt; hd[(size_t)nq + 8 + (size_t)4 * s_ + 2] = ng * nt;
+    }
+    h->w_stagedir.ensure(hd.size() * 4);
+    HIPCHECK(hipMemcpyAsync(h->w_stagedir.p, hd.data(), hd.size() * 4, hipMemcpyHostToDevice, h->st));
+    const int32_t* sd = h->w_stagedir.as<int32_t>();
+    const int32_t *pairs_sorted = sd, *pair_off = sd + nq, *group_off = sd + nq + 2, *total_groups = sd + nq + 4;
+    const int64_t mi = (int64_t)ng * tmax + 8;
+    int log_cap = 64;
+    void* rws = rot_scan_ws(h, P.k, mi, P.ngq, log_cap);
+    h->w_qitems.ensure((size_t)nq * tmax * 4);
+    PQStageArgs ga{};
+    ga.qitems = h->w_qitems.as<int32_t>(); ga.tmax = tmax;
+    ga.seg_desc = pq_scan_rot_ws_desc(rws, mi * P.ngq); ga.log_keys = pq_scan_rot_ws_keys(rws, mi * P.ngq);
+    ga.cand = h->w_cand.as<uint64_t>(); ga.cand_cnt = h->w_candcnt.as<unsigned long long>(); ga.cand_cap = R.cand_cap;
+    ga.qparam = h->w_qparam.as<float>(); ga.k = P.k; ga.tau = h->w_tau.as<uint64_t>();
+    for (int s_ = 0; s_ < S; s_++) {
+        const int j0 = s_ ? ends[(size_t)s_ - 1] : 0, nt = ends[(size_t)s_] - j0;
+        const int32_t* item_off = sd + nq + 8 + 4 * s_;
+        if (s_ == S - 1) tm.pre_scan();
+        PQTileSet ts; ts.j0 = j0; ts.mul = mul; ts.mod = T;
+        if (launch_pq_scan_rot(a, h->w_lut8.as<uint8_t>(), h->w_qparam.p, pairs_sorted, pair_off, group_off, total_groups, item_off, item_off + 2,
+                               1, mi, g.vpl, h->w_tau.as<uint64_t>(), 1, h->w_cand.as<uint64_t>(), h->w_candcnt.as<unsigned long long>(), R.cand_cap,
+                               rws, log_cap, 0, (h->pq_pace & 0xffff), nullptr, h->w_qitems.as<int32_t>(), tmax, h->st,
+                               P.sliced ? (P.sl_eight ? 1 : 0) : h->pq_q8, ts) != 0)
+            RSX_THROW(RSX_ERR_UNSUPPORTED, "IndexPQ staged scan: no kernel for M=%d", h->M);
+        tm.mark("scan");
+        ga.ntiles = nt; ga.nrecs = (int64_t)ng * nt * P.ngq; ga.last = s_ == S - 1;
+        launch_pq_stage_gather(ga, nq, h->st);
+        tm.mark("select");
+    }
+    h->timing["pq_flat_stages"] += (double)S;
+    R.filtered = true;
+}
 // 8-bit tables, 4 queries per LDS read; approximate scores, certified in k_finalize
 static void pq_fast_scan(rsx_index* h, const BatchPlan& P, BatchResult& R, PQScanArgs& a, StageTimer& tm) {
     const int64_t nq = P.nq; const int nlist = h->nlist, nprobe = P.nprobe;
@@ -789,10 +886,14 @@ static void pq_fast_scan(rsx_index* h, const BatchPlan& P, BatchResult& R, PQSca
     //           appending to a small per-query candidate buffer only the keys that beat the bound
     //           (wave-aggregated atomics); a final select merges them with state0.
     // A full candidate buffer marks the query uncertain (-> exact fallback), so this is always exact.
-    R.filtered = nprobe > 1 && P.pq_filter != 0;
+    R.filtered = (nprobe > 1 || P.staged) && P.pq_filter != 0;
     const PqGeometry g = pq_geometry(h, P, R.filtered);
     bool done = true, grouped = false;
-    if (g.fused_pre) grouped = pq_prepass(h, P, R, pr, g, lut_ws, tm);
+    if (P.staged) {
+        if (!g.fused_pre) RSX_THROW(RSX_ERR_UNSUPPORTED, "IndexPQ staged scan: the threshold pre-pass does not fit (M=%d)", h->M);
+        pq_staged_scan(h, P, R, a, g, lut_ws, tm);
+    }
+    else if (g.fused_pre) grouped = pq_prepass(h, P, R, pr, g, lut_ws, tm);
     else {
         build_pq_tables(h, P, lut_ws, nullptr, tm);
         h->w_temp.ensure((size_t)nq * P.tmax * 4);       // this form scores a prefix / everything into the score rows
@@ -809,7 +910,7 @@ static void pq_fast_scan(rsx_index* h, const BatchPlan& P, BatchResult& R, PQSca
                       : launch_pq_scan8(a, h->w_lut8.as<uint8_t>(), h->w_qparam.p, pr.pairs_sorted, pr.pair_off, pr.group_off,
                                         pr.total_groups, pr.item_off, pr.total_items, nlist, mi, vpl, h->st)) == 0;
     }
-    if (done && R.filtered) done = pq_filtered_scan(h, P, R, a, pr, g, grouped, tm);
+    if (done && R.filtered && !P.staged) done = pq_filtered_scan(h, P, R, a, pr, g, grouped, tm);
     if (!done) RSX_THROW(RSX_ERR_UNSUPPORTED, "IVFPQ fast scan: no kernel for M=%d", h->M);
     // rotated layout, threshold by construction: finalize straight from the complete candidate row (k_pq_final_tab) when K'
     // is large or a table entry is a long chain (M = 16: dsub 48) — the K' cut, its certificate and the second chance disappear

@@ -247,26 +247,32 @@ __global__ __launch_bounds__(256) void k_pq_rot_items(PQScan8Args A, PQRotItem* 
     while (hi - lo > 1) { const int mid = (lo + hi) >> 1; if (ioff[mid] <= item) lo = mid; else hi = mid; }
     const int ng = A.group_off[lo + 1] - A.group_off[lo];
     const int r = item - ioff[lo];
-    const int tile = r / ng, gi = r - tile * ng;
+    const int tile_n = r / ng, gi = r - tile_n * ng;     // the tile's number in the item order ...
+    // ... and the list tile it stands for (staged flat scan: a set of tiles spread over the list, PQScan8Args::tile_mod)
+    const int tile = A.tile_mod > 0 ? (int)(((int64_t)(A.tile_j0 + tile_n) * A.tile_mul) % A.tile_mod) : tile_n;
     const int cnt = A.pair_off[lo + 1] - A.pair_off[lo];
     const int first = 4 * (gi * ngq + h);                 // this record's first pair within the list's sorted pairs
     int npr = cnt - first; if (npr > 4) npr = 4; if (npr < 0) npr = 0;
     const int pair0 = A.pair_off[lo] + (npr > 0 ? first : 0);
     PQRotItem d;
-    d.l = lo; d.tile = tile; d.np = npr; d.pad0 = 0;
+    // (tile-set form: the item's record describes the TILE as a list of its own — base row, length, candidate offset — so the scans' 32-bit
+    //  byte offsets into "the list" stay inside one tile however long the one list of an IndexPQ is: 100M x 96 bytes is 9.6 GB)
+    const int64_t trow = A.tile_mod > 0 ? (int64_t)tile * A.tile_rows : 0;
+    d.l = lo; d.tile = A.tile_mod > 0 ? 0 : tile; d.np = npr; d.pad0 = 0;
     // the item's FAMILY = the ng query groups of one list tile, adjacent in the item order: [item - gi, item - gi + ng)
     const int fam = ((gi < 0x3fff ? gi : 0x3fff) << 4) | ((ng < 0x3fff ? ng : 0x3fff) << 18);
     if (h == 0) prog[item] = 0u;
-    d.len = a.list_len[lo]; d.base_row = a.list_base[lo];
+    d.len = a.list_len[lo] - trow; d.base_row = a.list_base[lo] + trow;
+    if (A.tile_mod > 0 && d.len > A.tile_rows) d.len = A.tile_rows;
 #pragma unroll
     for (int k = 0; k < 4; k++) {
         const int pi = A.pairs_sorted[pair0 + (k < npr ? k : 0)];
         const int64_t q = pi / a.nprobe;
         const PQQParam p = A.qp[q];
-        const int64_t col = a.seg_start[q * (a.nprobe + 1) + (pi - (int)q * a.nprobe)];
+        const int64_t col = a.seg_start[q * (a.nprobe + 1) + (pi - (int)q * a.nprobe)] + trow;
         const float dis0 = a.probe_dis0[pi];
         d.q[k] = (int32_t)q; d.dis0[k] = dis0; d.scale[k] = p.scale; d.bias[k] = p.bias;
-        if (FILTER && A.qitems && k < npr && tile < A.qitems_tmax) A.qitems[(int64_t)pi * A.qitems_tmax + tile] = rec * 4 + k;
+        if (FILTER && A.qitems && k < npr && tile_n < A.qitems_tmax) A.qitems[(int64_t)pi * A.qitems_tmax + tile_n] = rec * 4 + k;
         d.off[k] = FILTER ? col : q * a.tstride + col;
         const uint64_t tau = FILTER ? A.tau_key[q * A.tau_stride] : 0ull;
         d.tau[k] = tau;
@@ -1622,7 +1628,7 @@ int launch_pq_scan_rot(const PQScanArgs& a, const uint8_t* lut8t, const void* qp
                        const int32_t* item_off, const int32_t* total_items, int nlist, int64_t max_items, int vpl,
                        const uint64_t* tau_key, int64_t tau_stride, uint64_t* cand, unsigned long long* cand_cnt,
                        int cand_cap, void* item_ws, int log_cap, int prune, int pace, const uint16_t* excl, int32_t* qitems,
-                       int qitems_tmax, hipStream_t st, int q8) {
+                       int qitems_tmax, hipStream_t st, int q8, PQTileSet tiles) {
     if (!pq_rot_family(a.CB) || !item_ws || log_cap <= 0 || !pq_rot_applies(a.M) || a.M != a.Mpad || max_items <= 0 || max_items > 0x7fffff00) return -1;
     if (a.CB == PQ_SLICED && (!tau_key || !pq_sliced_applies(a.M))) return -1;      // the sliced layout has the filtered 8-query scan only
     PQScan8Args A;
@@ -1632,6 +1638,7 @@ int launch_pq_scan_rot(const PQScanArgs& a, const uint8_t* lut8t, const void* qp
     A.nlist = nlist; A.max_items = (int)max_items;
     A.tau_key = tau_key; A.tau_stride = tau_stride; A.cand = cand; A.cand_cnt = cand_cnt; A.cand_cap = cand_cap;
     A.prune = prune; A.pace = pace; A.excl = excl; A.qitems = qitems; A.qitems_tmax = qitems_tmax;
+    A.tile_j0 = tiles.j0; A.tile_mul = tiles.mul; A.tile_mod = tiles.mod; A.tile_rows = 1024 * vpl;
     const int bpw = 4 * vpl;   // tile = 16 waves x bpw blocks x 16 vectors = 1024 vpl vectors, as k_pq_scan8's
     const bool f = tau_key != nullptr;
     if (a.CB == PQ_SLICED) return q8 ? launch_pq_scan_sl8_t<3, SL8_NB, SL8_RD>(A, vpl, item_ws, log_cap, st) : launch_pq_scan_sl4_t<3>(A, vpl, item_ws, log_cap, st);

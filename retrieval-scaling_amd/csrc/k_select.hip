@@ -468,6 +468,148 @@ void launch_pq_gather_select(const PQGatherArgs& a, int64_t nq, hipStream_t st) 
 }
 
 // ---------------------------------------------------------------------------------------
+// Staged flat scan (IndexPQ), the step between two stages (PQStageArgs, rsx_internal.h).  One workgroup per query, no atomics outside
+// its LDS, no host round trip:
+//   1. the 16 run descriptors of each of the stage's tiles (k_pq_rot_items left the item + slot of every (query, tile) in qitems),
+//   2. their exclusive prefix, 3. the runs' keys copied behind what the candidate row holds — as k_pq_gather_select does —
+//   4. the k-th best approximate key a_k of the row (a radix walk, threshold only).  The row holds every scanned vector whose approximate
+//      score reaches tau, so for k or more keys a_k is the k-th best approximate score of ALL rows scanned so far: the pre-pass's
+//      argument on a larger sample gives tau' = max(tau, a_k - 2 eps), valid for the rows still to come and for the row itself,
+//   5. the row compacted in place to the keys above tau' (chunks of 1024 keys: a chunk is read, a barrier, then written at or below
+//      where it was read), so the row's length follows the 2 eps band and the stage's own yield, not the number of stages.
+// A run that lost keys to a full log, or a row that was full, leaves the count past the capacity whatever is compacted later:
+// k_finalize / k_pq_final_tab flag that query and it alone is re-run exactly.
+// ---------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void k_pq_stage_gather(PQStageArgs a) {
+    extern __shared__ __attribute__((aligned(16))) uint64_t sg_smem[];
+    const int NS = a.ntiles * 16;
+    uint64_t* obuf = sg_smem;                                      // [2]: threshold key of the selection; the new tau
+    int32_t* hist = reinterpret_cast<int32_t*>(sg_smem + 2);       // [256]
+    int32_t* ctl = hist + 256;                                     // [8]
+    int32_t* misc = ctl + 8;                                       // [8]: 0 overflow flag, 1..4 wave totals
+    uint32_t* sfirst = reinterpret_cast<uint32_t*>(misc + 8);      // [NS]: first key of the run in the log pool
+    uint32_t* spre = sfirst + NS;                                  // [NS]: the run's length, then the keys in the runs before it
+    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+    const int64_t q = blockIdx.x;
+    if (tid < 8) misc[tid] = 0;
+    __syncthreads();
+    {
+        bool over = false;
+        for (int s0 = tid; s0 < NS; s0 += 256 * 4) {
+            uint2 dsc[4];
+#pragma unroll
+            for (int u = 0; u < 4; u++) {
+                const int s2 = s0 + u * 256;
+                dsc[u] = make_uint2(0u, 0u);
+                if (s2 < NS) {
+                    const int32_t slot = a.qitems[q * a.tmax + (s2 >> 4)];
+                    if (slot >= 0 && (int64_t)(slot >> 2) < a.nrecs) dsc[u] = a.seg_desc[(size_t)(slot >> 2) * 64 + (size_t)(s2 & 15) * 4 + (slot & 3)];
+                }
+            }
+#pragma unroll
+            for (int u = 0; u < 4; u++) {
+                const int s2 = s0 + u * 256;
+                if (s2 >= NS) break;
+                if (dsc[u].y >> 31) over = true;                     // the wave's log was full: keys were dropped
+                sfirst[s2] = dsc[u].x; spre[s2] = dsc[u].y & 0x7fffffffu;
+            }
+        }
+        if (over) misc[0] = 1;
+    }
+    const unsigned long long e0 = a.cand_cnt[q * CCS];             // what the row holds (past the capacity: flagged earlier)
+    __syncthreads();
+    const int spt = (NS + 255) >> 8;
+    int mine = 0;
+    for (int u = 0; u < spt; u++) { const int s2 = tid * spt + u; if (s2 < NS) mine += (int)spre[s2]; }
+    int incl = mine;
+#pragma unroll
+    for (int off = 1; off < 64; off <<= 1) { const int y = __shfl_up(incl, off); if (lane >= off) incl += y; }
+    if (lane == 63) misc[1 + w] = incl;
+    __syncthreads();
+    int wbase = 0, total = 0;
+#pragma unroll
+    for (int ww = 0; ww < 4; ww++) { const int v = misc[1 + ww]; if (ww < w) wbase += v; total += v; }
+    {
+        uint32_t run = (uint32_t)(wbase + incl - mine);
+        for (int u = 0; u < spt; u++) { const int s2 = tid * spt + u; if (s2 < NS) { const uint32_t c = spre[s2]; spre[s2] = run; run += c; } }
+    }
+    const unsigned long long cap = (unsigned long long)a.cand_cap;
+    const unsigned long long e0c = e0 < cap ? e0 : cap;
+    const bool flagged = misc[0] != 0 || e0 > cap || e0c + (unsigned long long)total > cap;
+    const int nrow = (int)(e0c + (unsigned long long)total < cap ? e0c + (unsigned long long)total : cap);      // keys that fit the row
+    __syncthreads();        // spre is complete
+    uint64_t* row = a.cand + q * a.cand_cap;
+    for (int p0 = tid; p0 < total; p0 += 256 * 4) {
+        uint64_t kk[4]; int pp[4];
+#pragma unroll
+        for (int u = 0; u < 4; u++) {
+            const int pk = p0 + u * 256;
+            pp[u] = -1; kk[u] = 0ull;
+            if (pk >= total) continue;
+            int lo = 0, hi = NS;         // largest run index with spre <= pk: spre is non-decreasing, the last such run is the non-empty one
+            while (hi - lo > 1) { const int mid = (lo + hi) >> 1; if (spre[mid] <= (uint32_t)pk) lo = mid; else hi = mid; }
+            pp[u] = (int)e0c + pk;
+            if (pp[u] < a.cand_cap) kk[u] = a.log_keys[(size_t)sfirst[lo] + (size_t)((uint32_t)pk - spre[lo])];
+        }
+#pragma unroll
+        for (int u = 0; u < 4; u++) if (pp[u] >= 0 && pp[u] < a.cand_cap) row[pp[u]] = kk[u];
+    }
+    if (a.last) {
+        if (tid == 0) a.cand_cnt[q * CCS] = (unsigned long long)nrow + (flagged ? cap + 1ull : 0ull);
+        return;
+    }
+    __syncthreads();        // workgroup-scope release / acquire: the row written above is visible to every thread
+    auto key_at = [&](int i2) -> uint64_t { return row[i2]; };
+    radix_topk_wg<256, true>(key_at, nrow, a.k, obuf, hist, ctl);
+    if (tid == 0) {
+        uint64_t tau = a.tau[q];
+        const uint64_t kth = obuf[0];                                 // a lower bound of the row's k-th largest key; 0: no more than k keys
+        if (kth > 1ull) {
+            const float eps = a.qparam[q * 4 + 2];
+            float t = __fmaf_rn(-2.0002f, eps, key_score(kth));
+            t -= fabsf(t) * 4.8e-7f + 1e-30f;                         // two ulps down: the subtraction's own rounding (as k_pq_prepass)
+            const uint64_t tn = make_key(t, 0xFFFFFFFFu);             // low word 0: every key with score >= t compares greater
+            if (tn > tau) tau = tn;
+        }
+        a.tau[q] = tau;
+        obuf[1] = tau;
+    }
+    __syncthreads();
+    const uint64_t tau = obuf[1];
+    int outp = 0;
+    for (int base = 0; base < nrow; base += 1024) {
+        uint64_t kk[4]; int c = 0;
+#pragma unroll
+        for (int u = 0; u < 4; u++) {
+            const int i2 = base + tid * 4 + u;
+            kk[u] = i2 < nrow ? row[i2] : 0ull;
+            if (kk[u] > tau) c++; else kk[u] = 0ull;
+        }
+        int inc2 = c;
+#pragma unroll
+        for (int off = 1; off < 64; off <<= 1) { const int y = __shfl_up(inc2, off); if (lane >= off) inc2 += y; }
+        if (lane == 63) misc[1 + w] = inc2;
+        __syncthreads();    // the chunk has been read by every thread; the wave totals are there
+        int wb = 0, tot = 0;
+#pragma unroll
+        for (int ww = 0; ww < 4; ww++) { const int v = misc[1 + ww]; if (ww < w) wb += v; tot += v; }
+        int o = outp + wb + inc2 - c;
+#pragma unroll
+        for (int u = 0; u < 4; u++) if (kk[u] != 0ull) row[o++] = kk[u];
+        outp += tot;
+        __syncthreads();    // misc is free again; the writes sit at or below the chunk just read
+    }
+    if (tid == 0) a.cand_cnt[q * CCS] = (unsigned long long)outp + (flagged ? cap + 1ull : 0ull);
+}
+void launch_pq_stage_gather(const PQStageArgs& a, int64_t nq, hipStream_t st) {
+    if (nq <= 0) return;
+    const size_t shm = 16 + (256 + 8 + 8) * 4 + (size_t)a.ntiles * 16 * 8 + 64;
+    static DevSize attr;
+    attr.grow(shm, [&] { (void)hipFuncSetAttribute((const void*)k_pq_stage_gather, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm); });
+    hipLaunchKernelGGL(k_pq_stage_gather, dim3((unsigned)nq), dim3(256), shm, st, a);
+}
+
+// ---------------------------------------------------------------------------------------
 // IVF-PQ threshold pre-pass in ONE launch: a workgroup per query scores the first pre_rows vectors of the
 // query's closest NON-EMPTY probed list with the query's 8-bit table (24 KiB in LDS, byte gathers; the SAME integer sums and
 // the same fp32 expression as k_pq_scan8, hence the same keys), selects their K'-th largest key in LDS and

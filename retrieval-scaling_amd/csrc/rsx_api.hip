@@ -22,6 +22,11 @@ struct SelScope {
     }
 };
 
+// faiss.IndexPQ handles (rsx_index::flat_pq) have no coarse quantiser, no selectors and no removal
+static void refuse_flat_pq(const rsx_index* h, int code, const char* what) {
+    if (h && h->flat_pq) RSX_THROW(code, "%s: not available on an IndexPQ handle (a flat product quantiser: one list, no coarse quantiser)", what);
+}
+
 extern "C" {
 static int search_prepass_common(rsx_index_t* h, int64_t nq, const void* q, int dtype, int k, const rsx_selector* sel, int nprobe_override,
                                  float* D, int64_t* I, uint64_t** tau_dev, int64_t* ntau) {
@@ -29,6 +34,7 @@ static int search_prepass_common(rsx_index_t* h, int64_t nq, const void* q, int 
         if (!h || !tau_dev || !ntau) RSX_THROW(RSX_ERR_INVALID, "null pointer");
         if (dtype != RSX_F32 && dtype != RSX_F16) RSX_THROW(RSX_ERR_INVALID, "bad dtype %d", dtype);
         if (nprobe_override < 0) RSX_THROW(RSX_ERR_INVALID, "nprobe override must be positive or 0 (got %d)", nprobe_override);
+        if (sel) refuse_flat_pq(h, RSX_ERR_UNSUPPORTED, "search with a selector (FAISS 1.8.0 IndexPQ::search takes no search parameters)");
         if (is_sharded(h)) RSX_THROW(RSX_ERR_UNSUPPORTED, "search_prepass: not available on a sharded handle (its shards share one process)");
         if (nq > h->query_batch) RSX_THROW(RSX_ERR_UNSUPPORTED, "search_prepass: nq = %lld exceeds query_batch = %d (one internal batch per two-call search)", (long long)nq, h->query_batch);
         if (!h->tc) h->tc.reset(new rsx_index::TwoCall());
@@ -60,7 +66,7 @@ static int search_prepass_common(rsx_index_t* h, int64_t nq, const void* q, int 
 extern "C" {
 
 const char* rsx_last_error(void) { return g_err.c_str(); }
-int rsx_version(void) { return 1002; }     // 1001: filtered search (rsx_selector_*, rsx_search_sel, rsx_search_prepass_sel); 1002: rsx_remove_ids
+int rsx_version(void) { return 1003; }     // 1001: filtered search (rsx_selector_*, rsx_search_sel, rsx_search_prepass_sel); 1002: rsx_remove_ids; 1003: rsx_pq_create
 
 int rsx_device_count(int* n) {
     return guarded([&] {
@@ -81,9 +87,13 @@ int rsx_ivfflat_create(int d, int nlist, int metric, int device, rsx_index_t** o
 int rsx_ivfpq_create(int d, int nlist, int M, int nbits, int metric, int device, rsx_index_t** out) {
     return guarded([&] { if (!out) RSX_THROW(RSX_ERR_INVALID, "null out"); *out = create_common(KIND_IVFPQ, d, nlist, M, nbits, metric, device); });
 }
+int rsx_pq_create(int d, int M, int nbits, int metric, int device, rsx_index_t** out) {
+    return guarded([&] { if (!out) RSX_THROW(RSX_ERR_INVALID, "null out"); *out = create_flat_pq(d, M, nbits, metric, device); });
+}
 int rsx_sharded_create(int kind, int d, int nlist, int M, int nbits, int metric, int ndev, const int* devices, rsx_index_t** out) {
     return guarded([&] {
         if (!out) RSX_THROW(RSX_ERR_INVALID, "null out");
+        if (kind == RSX_KIND_PQ) RSX_THROW(RSX_ERR_UNSUPPORTED, "sharded_create: IndexPQ (kind 3) has no sharded form in this build");
         if (kind != KIND_FLAT && kind != KIND_IVFFLAT && kind != KIND_IVFPQ) RSX_THROW(RSX_ERR_INVALID, "unknown index kind %d", kind);
         *out = sharded_create(kind, d, nlist, M, nbits, metric, ndev, devices);
     });
@@ -133,6 +143,7 @@ int rsx_set_centroids(rsx_index_t* h, const float* c) {
     return guarded([&] {
         if (!h || !c) RSX_THROW(RSX_ERR_INVALID, "null pointer");
         refuse_while_two_call(h, "set_centroids");
+        refuse_flat_pq(h, RSX_ERR_INVALID, "set_centroids");
         if (h->kind == KIND_FLAT) RSX_THROW(RSX_ERR_INVALID, "Flat has no centroids");
         if (h->ntotal) RSX_THROW(RSX_ERR_INVALID, "cannot replace centroids of a populated index");
         if (is_sharded(h)) {
@@ -160,6 +171,7 @@ int rsx_set_codebooks(rsx_index_t* h, const float* c) {
 int rsx_get_centroids(rsx_index_t* h, float* out) {
     return guarded([&] {
         if (!h || !out) RSX_THROW(RSX_ERR_INVALID, "null pointer");
+        refuse_flat_pq(h, RSX_ERR_INVALID, "get_centroids");
         if (is_sharded(h)) h = h->shards[0];
         if (h->h_centroids.empty()) RSX_THROW(RSX_ERR_NOT_TRAINED, "no centroids");
         memcpy(out, h->h_centroids.data(), h->h_centroids.size() * 4);
@@ -180,6 +192,7 @@ int rsx_add(rsx_index_t* h, int64_t n, const void* x, int dtype, const int64_t* 
         refuse_while_two_call(h, "add");
         if (dtype != RSX_F32 && dtype != RSX_F16) RSX_THROW(RSX_ERR_INVALID, "bad dtype %d", dtype);
         if (!h->trained) RSX_THROW(RSX_ERR_NOT_TRAINED, "add before train");
+        if (ids) refuse_flat_pq(h, RSX_ERR_UNSUPPORTED, "add with ids (FAISS's IndexFlatCodes has no add_with_ids)");
         if (n <= 0) return;
         if (is_sharded(h)) { sharded_add(h, n, x, dtype, ids); return; }
         use_device(h);
@@ -192,6 +205,7 @@ int rsx_assign(rsx_index_t* h, int64_t n, const void* x, int dtype, int64_t* lab
         if (dtype != RSX_F32 && dtype != RSX_F16) RSX_THROW(RSX_ERR_INVALID, "bad dtype %d", dtype);
         if (h->kind == KIND_FLAT) RSX_THROW(RSX_ERR_INVALID, "Flat has no coarse quantiser");
         refuse_while_two_call(h, "assign");
+        refuse_flat_pq(h, RSX_ERR_INVALID, "assign");
         if (is_sharded(h)) h = h->shards[0];
         if (h->h_centroids.empty()) RSX_THROW(RSX_ERR_NOT_TRAINED, "assign before train");
         use_device(h);
@@ -241,6 +255,7 @@ int rsx_reserve_lists(rsx_index_t* h, const int64_t* counts) {
     return guarded([&] {
         if (!h || !counts) RSX_THROW(RSX_ERR_INVALID, "null pointer");
         refuse_while_two_call(h, "reserve_lists");
+        refuse_flat_pq(h, RSX_ERR_INVALID, "reserve_lists");
         if (is_sharded(h)) { sharded_reserve(h, counts); return; }
         use_device(h);
         std::vector<int64_t> need(counts, counts + h->nlist);
@@ -286,6 +301,7 @@ int rsx_set_nprobe(rsx_index_t* h, int nprobe) {
     return guarded([&] {
         if (!h) RSX_THROW(RSX_ERR_INVALID, "null pointer");
         refuse_while_two_call(h, "set_nprobe");
+        refuse_flat_pq(h, RSX_ERR_INVALID, "set_nprobe");
         if (nprobe <= 0) RSX_THROW(RSX_ERR_INVALID, "nprobe must be positive (got %d)", nprobe);
         // FAISS accepts any nprobe and probes min(nprobe, nlist) lists; the effective value is bounded at search time
         h->nprobe = nprobe;
@@ -314,7 +330,8 @@ int rsx_search_sel(rsx_index_t* h, int64_t nq, const void* q, int dtype, int k, 
         refuse_while_two_call(h, "search");
         if (dtype != RSX_F32 && dtype != RSX_F16) RSX_THROW(RSX_ERR_INVALID, "bad dtype %d", dtype);
         if (nprobe_override < 0) RSX_THROW(RSX_ERR_INVALID, "nprobe override must be positive or 0 (got %d)", nprobe_override);
-        SelScope sc(h, sel, nprobe_override);
+        if (sel) refuse_flat_pq(h, RSX_ERR_UNSUPPORTED, "search with a selector (FAISS 1.8.0 IndexPQ::search takes no search parameters)");
+        SelScope sc(h, sel, h->flat_pq ? 0 : nprobe_override);
         if (is_sharded(h)) {
             if (!h->trained) RSX_THROW(RSX_ERR_NOT_TRAINED, "search before train");
             sharded_search(h, nq, q, dtype, k, D, I);
@@ -329,6 +346,7 @@ int rsx_remove_ids(rsx_index_t* h, const rsx_selector_t* sel, int64_t* nremoved)
     return guarded([&] {
         if (!h || !sel || !nremoved) RSX_THROW(RSX_ERR_INVALID, "null pointer");
         refuse_while_two_call(h, "remove_ids");
+        refuse_flat_pq(h, RSX_ERR_UNSUPPORTED, "remove_ids");
         *nremoved = 0;
         if (is_sharded(h)) { *nremoved = sharded_remove(h, sel); return; }
         use_device(h);
@@ -474,7 +492,7 @@ int rsx_get(rsx_index_t* h, const char* key, int64_t* out) {
         else if (s == "nprobe") *out = h->nprobe;
         else if (s == "M") *out = h->M;
         else if (s == "nbits") *out = h->nbits;
-        else if (s == "kind") *out = h->kind;
+        else if (s == "kind") *out = public_kind(h);
         else if (s == "metric") *out = h->metric;
         else if (s == "storage_dtype") *out = (h->kind == KIND_IVFPQ) ? -1 : (h->storage_f16 ? RSX_F16 : RSX_F32);
         else if (s == "code_size") *out = (h->kind == KIND_IVFPQ) ? h->M : (int64_t)h->d * (h->storage_f16 ? 2 : 4);
@@ -507,6 +525,7 @@ int rsx_set_param(rsx_index_t* h, const char* key, double value) {
         else if (s == "pq_pace") h->pq_pace = std::max(0, (int)value);
         else if (s == "add_list_mod" || s == "add_list_rem") {
             if (h->kind == KIND_FLAT) RSX_THROW(RSX_ERR_UNSUPPORTED, "%s: IVF indexes only", key);
+            refuse_flat_pq(h, RSX_ERR_INVALID, key);
             if (h->ntotal + h->ndropped > 0) RSX_THROW(RSX_ERR_INVALID, "%s must be set before the first add", key);
             if (s == "add_list_mod") { if (value < 1) RSX_THROW(RSX_ERR_INVALID, "add_list_mod >= 1"); h->add_list_mod = (int)value; h->add_list_rem = 0; }
             else { if (value < 0 || value >= h->add_list_mod) RSX_THROW(RSX_ERR_INVALID, "0 <= add_list_rem < add_list_mod"); h->add_list_rem = (int)value; }
@@ -522,6 +541,9 @@ int rsx_set_param(rsx_index_t* h, const char* key, double value) {
         else if (s == "ivf_pre_lists") h->ivf_pre_lists = std::max(0, (int)value);
         else if (s == "ivf_pre_mult") h->ivf_pre_mult = std::max(1, (int)value);
         else if (s == "pq_pre_rows") h->pq_pre_rows = (int)value;
+        else if (s == "pq_flat_first") h->pq_flat_first = std::max(0, (int)value);
+        else if (s == "pq_flat_growth") h->pq_flat_growth = std::max(0, (int)value);
+        else if (s == "pq_flat_max_stages") h->pq_flat_max_stages = std::min(64, std::max(0, (int)value));
         else if (s == "pq_log_cap") h->pq_log_cap = std::max(0, (int)value);
         else if (s == "pq_pre_mult") h->pq_pre_mult = std::max(1, (int)value);
         else if (s == "pq_pre_max") h->pq_pre_max = std::min(32768, std::max(64, (int)value));

@@ -178,6 +178,10 @@ struct rsx_index {
 #define PQ_LAYOUT_DEFAULT 2      // RSX_PQ_LAYOUT unset: 1 = rotated wherever it applies, 2 = additionally the sliced layout for M = 96
 #endif
     int nprobe = 1;
+    // RSX_KIND_PQ (faiss.IndexPQ, rsx_pq_create): stored as an IVF-PQ index of ONE list with a zero centroid (kind stays KIND_IVFPQ: code
+    // layouts, encoder, table builders, finalize and the RSX1 writer are shared; residual = x - 0 = x, dis0 = <q, 0> = +0) that reports
+    // kind 3, refuses what a flat index has not, and searches through the staged filtered scan (api_search.hip: pq_staged_scan)
+    bool flat_pq = false;
     bool trained = false;
     int64_t ntotal = 0;
     hipStream_t st = nullptr;
@@ -243,6 +247,9 @@ struct rsx_index {
     int pq_final_tab = 1;    // rotated fast scan: finalize from the complete candidate row with the fp32 table in LDS (1 = when K' >= 512 or dsub > 8 and as the second chance, 2 = always, 0 = never)
     int pq_log_cap = 0;      // rotated fast scan: keys per survivor log (0 = from the pool budget); tests shrink it to force the overflow path
     int pq_pre_mult = 80, pq_pre_max = 16384;    // ... and for larger k: pq_pre_mult x k rows, at most pq_pre_max (<= 32768: 64 KiB of 16-bit sums in LDS; 16384 measured best overall on the headline index at k = 100 / 1000 / 2000, profiles/r04u_pre_sweep.jsonl; round 6, after the four-query histogram pre-pass: 80 x k — k = 100 2.95 -> 2.88 ms per batch, k = 50 / 200 / 1000 unchanged, profiles/r06_fixed_cost.md 5)
+    int pq_flat_first = 0;       // IndexPQ staged scan: rows of the first stage (0 = 4 scan tiles, at least 64 k rows)
+    int pq_flat_growth = 0;      // ... percent by which a stage outgrows the one before it (0 = 300: each stage three times the rows scanned so far)
+    int pq_flat_max_stages = 0;  // ... most stages (0 = 12; the last stage takes whatever is left)
     int pq_pre_rows = 4096;  // filtered fast scan: vectors of each query's closest list the threshold pre-pass scores (0 = one scan tile)
     int add_list_mod = 1, add_list_rem = 0;   // IVF add keeps only lists l with l % mod == rem (list-sharded multi-GPU index)
     int64_t ndropped = 0;                     // vectors seen by add but owned by other shards
@@ -259,7 +266,8 @@ struct rsx_index {
 
     // workspace
     DevBuf w_q32, w_q16, w_coarse, w_keys1, w_probekeys, w_probelist, w_dis0, w_segstart, w_temp, w_lut, w_lutws, w_pgflags, w_state,
-        w_D, w_I, w_qin, w_pairs, w_flag, w_x, w_partial, w_assign, w_dest, w_idsin, w_misc, w_lut8, w_qparam, w_uncertain, w_fbq, w_fbD, w_fbI, w_cand, w_candcnt, w_itemdesc, w_tau, w_excl, w_state2, w_addcnt, w_addstart, w_qitems, w_tiews;
+        w_D, w_I, w_qin, w_pairs, w_flag, w_x, w_partial, w_assign, w_dest, w_idsin, w_misc, w_lut8, w_qparam, w_uncertain, w_fbq, w_fbD, w_fbI, w_cand, w_candcnt, w_itemdesc, w_tau, w_excl, w_state2, w_addcnt, w_addstart, w_qitems, w_tiews, w_stagedir;
+    std::vector<int32_t> stage_host;      // IndexPQ staged scan: host image of w_stagedir (the stages' item tables), alive while the copy runs
     std::map<std::string, double> timing;
 
     // filtered search (rsx_search_sel): the selector of the call in flight (null = unfiltered) and its slot mask — bit s of
@@ -338,6 +346,7 @@ void set_centroids(rsx_index* h, const float* c);
 void set_codebooks(rsx_index* h, const float* c);
 void update_trained(rsx_index* h);
 rsx_index* create_common(int kind, int d, int nlist, int M, int nbits, int metric, int device);
+rsx_index* create_flat_pq(int d, int M, int nbits, int metric, int device);
 void add_all(rsx_index* h, int64_t n, const void* x, int dtype, const int64_t* ids);
 void train_impl(rsx_index* h, int64_t n, const void* x, int dtype);
 void search_impl(rsx_index* h, int64_t nq, const void* q, int dtype, int k, float* D, int64_t* I);
@@ -376,6 +385,7 @@ void launch_rm_flat_chunk(const uint32_t* mask, const int32_t* word_pre, const i
 }  // namespace rsx
 
 static inline bool is_sharded(const rsx_index* h) { return !h->shards.empty(); }
+static inline int public_kind(const rsx_index* h) { return h->flat_pq ? 3 : h->kind; }      // rsx_kind as callers and files see it
 
 template <typename F>
 static inline void for_each_shard_parallel(rsx_index* h, F&& f) {

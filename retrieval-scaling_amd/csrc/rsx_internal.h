@@ -325,7 +325,14 @@ struct PQScan8Args {
     // k_pq_rot_items (optional): qitems[(q * nprobe + probe rank) * qitems_tmax + tile] = item * 4 + slot of that (query, list tile) —
     // the inverse of the item order, which lets k_pq_gather_select find a query's survivor segments without atomics
     int32_t* qitems; int qitems_tmax;
+    // k_pq_rot_items, staged flat scan (IndexPQ; tile_mod > 0): the launch covers a SET of the list's tiles — the item order's tile number t
+    // (0 .. tiles of the stage - 1, what qitems is indexed by) stands for list tile ((tile_j0 + t) * tile_mul) % tile_mod.  tile_mod = the
+    // list's tile count, tile_mul coprime to it: consecutive numbers are spread over the whole list and the stages' sets are disjoint.
+    // The item then describes its tile as a list of its own (base row, length <= tile_rows, tile 0, candidate offset): the scans' 32-bit byte
+    // offsets stay inside the tile.
+    int tile_j0 = 0, tile_mul = 0, tile_mod = 0, tile_rows = 0;
 };
+struct PQTileSet { int j0 = 0, mul = 0, mod = 0; };
 
 // Work-item decode shared by the list-major scans.  Items are ordered (list, tile, group) so that the
 // query groups of one list-tile (same codes) are adjacent; XCD c takes the contiguous item range
@@ -356,7 +363,8 @@ int launch_pq_scan_rot(const PQScanArgs& a, const uint8_t* lut8t, const void* qp
                        const uint64_t* tau_key, int64_t tau_stride, uint64_t* cand, unsigned long long* cand_cnt,
                        int cand_cap, void* item_ws /* pq_scan_rot_ws(max_items, log_cap, pq_scan_rot_max_wgs(M)) bytes */, int log_cap, int prune, int pace,
                        const uint16_t* excl, int32_t* qitems /* non-null: fill it and leave the runs for k_pq_gather_select */,
-                       int qitems_tmax, hipStream_t st, int q8 = 0 /* filtered M = 64: eight queries per work item (pq_scan_rot_ngq) */);
+                       int qitems_tmax, hipStream_t st, int q8 = 0 /* filtered M = 64: eight queries per work item (pq_scan_rot_ngq) */,
+                       PQTileSet tiles = PQTileSet() /* mod > 0: the launch covers that set of tiles (PQScan8Args::tile_mod) */);
 // Survivors of the filtered scan (round 4): every (persistent workgroup, wave, query slot) appends to its own LOG of log_cap keys;
 // an 8-byte descriptor per (item, wave, slot) = {index of the run's first key in the log pool, keys stored | bit 31: keys were
 // dropped because the log was full} lets the gather / compaction kernels find an item's runs.
@@ -382,6 +390,20 @@ struct PQGatherArgs {
     uint64_t* state; int KP;
 };
 bool pq_gather_select_applies(int nprobe, int tmax, int KP);
+// Staged flat scan (IndexPQ), between two stages, one workgroup per query: the stage's survivor runs (every wave's runs of the
+// stage's `ntiles` tiles, found through qitems [nq][tmax]) go behind what the query's candidate row holds; the k-th best approximate key of
+// the row gives tau' = max(tau, a_k - 2 eps) (the pre-pass's rule on a larger sample), the row is compacted to the keys above tau' and
+// tau[q] = tau' serves the next stage.  The row's count goes past the capacity for good once a log dropped keys or the row was full.
+// last: gather only (the finalize cuts the row itself).
+struct PQStageArgs {
+    const int32_t* qitems; int tmax; int ntiles;
+    int64_t nrecs;                                  // item records of the stage's launch (a slot beyond them is not followed)
+    const uint2* seg_desc; const uint64_t* log_keys;
+    uint64_t* cand; unsigned long long* cand_cnt; int cand_cap;
+    const float* qparam; int k; uint64_t* tau; int last;
+};
+constexpr int PQ_STAGE_MAX_TILES = 1024;      // 16 runs per tile, 8 bytes of LDS per run
+void launch_pq_stage_gather(const PQStageArgs& a, int64_t nq, hipStream_t st);
 void launch_pq_gather_select(const PQGatherArgs& a, int64_t nq, hipStream_t st);
 // exact per-(query, list) scan of the rotated layout (fp32 table, sequential sums = oracle bits): fallback / A-B path
 int launch_pq_scan_rot_exact(const PQScanArgs& a, hipStream_t st);

@@ -9,6 +9,7 @@ written against `faiss`:
     faiss.IndexFlatIP(d)            flat.py:42         rsx.IndexFlatIP(d)
     faiss.IndexIVFFlat(q,d,nlist,METRIC_INNER_PRODUCT) ivf_flat.py:144   rsx.IndexIVFFlat(...)
     faiss.IndexIVFPQ(q,d,nlist,M,nbits,METRIC_IP)      ivf_pq.py:147     rsx.IndexIVFPQ(...)
+    faiss.IndexPQ(d,M,nbits,METRIC_IP)    contriever/src/index.py:19     rsx.IndexPQ(...)
     index.train / add / search / nprobe / ntotal / is_trained            same
     faiss.read_index / write_index                                        rsx.read_index / write_index
     StandardGpuResources / GpuClonerOptions / index_cpu_to_gpu / index_gpu_to_cpu
@@ -37,7 +38,7 @@ _lib = None
 #: every symbol include/rsx.h declares (checked by tests/test_abi.py against the header)
 ABI_SYMBOLS = [
     "rsx_last_error", "rsx_version", "rsx_device_count", "rsx_flat_create", "rsx_ivfflat_create",
-    "rsx_ivfpq_create", "rsx_sharded_create", "rsx_load_sharded", "rsx_destroy", "rsx_train", "rsx_set_centroids", "rsx_set_codebooks",
+    "rsx_ivfpq_create", "rsx_pq_create", "rsx_sharded_create", "rsx_load_sharded", "rsx_destroy", "rsx_train", "rsx_set_centroids", "rsx_set_codebooks",
     "rsx_get_centroids", "rsx_get_codebooks", "rsx_add", "rsx_assign", "rsx_reset", "rsx_reserve_lists", "rsx_add_list",
     "rsx_get_list", "rsx_get_list_sizes", "rsx_set_nprobe", "rsx_search", "rsx_search_prepass", "rsx_search_scan", "rsx_merge_topk", "rsx_pack_topk", "rsx_merge_packed", "rsx_get",
     "rsx_set_param",
@@ -143,6 +144,8 @@ def _create(kind, d, nlist, M, nbits, metric, device, devices):
         _check(lib().rsx_flat_create(int(d), int(metric), dev, ctypes.byref(h)))
     elif kind == 1:
         _check(lib().rsx_ivfflat_create(int(d), int(nlist), int(metric), dev, ctypes.byref(h)))
+    elif kind == 3:
+        _check(lib().rsx_pq_create(int(d), int(M), int(nbits), int(metric), dev, ctypes.byref(h)))
     else:
         _check(lib().rsx_ivfpq_create(int(d), int(nlist), int(M), int(nbits), int(metric), dev, ctypes.byref(h)))
     return h
@@ -531,7 +534,7 @@ class Index:
         n = ctypes.c_int64(0)
         _check(lib().rsx_get_list(self._h, ctypes.c_int64(list_no), ctypes.byref(n), None, None))
         n = n.value
-        if self._get("kind") == 2:
+        if self._get("kind") in (2, 3):
             payload = np.empty((n, self._get("M")), dtype=np.uint8)
         else:
             payload = np.empty((n, self.d), dtype=np.float32)
@@ -548,7 +551,7 @@ class Index:
         return out
 
     def reconstruct_n(self, i0, n):
-        assert self._get("kind") == 0, "reconstruct_n is implemented for Flat indexes"
+        assert self._get("kind") == 0, "reconstruct_n is implemented for Flat and PQ indexes"
         payload, _ = self.get_list(0)
         return payload[i0:i0 + n]
 
@@ -652,6 +655,42 @@ class IndexIVFPQ(_IndexIVF):
         return cb
 
 
+class IndexPQ(Index):
+    """faiss.IndexPQ(d, M, nbits=8, metric=METRIC_L2): a flat product quantiser — no coarse stage, every query scans every code
+    (contriever/src/index.py:19, built by passage_retrieval.py --n_subquantizers; rsx_pq_create).  nbits must be 8.  `pq_layout`
+    (set_param, before the first add) picks the code layout as for IndexIVFPQ; inner product takes the staged filtered scan.
+    No add_with_ids (FAISS's IndexFlatCodes has none), no remove_ids, no search parameters (as FAISS 1.8.0's IndexPQ::search)."""
+
+    def __init__(self, d, M, nbits=8, metric=METRIC_L2, device=None):
+        super().__init__(_create(3, d, 1, M, nbits, metric, device, None), int(d), int(metric))
+        self.M = int(M)
+        self.nbits = int(nbits)
+
+    set_codebooks = IndexIVFPQ.set_codebooks
+    get_codebooks = IndexIVFPQ.get_codebooks
+
+    def add_codes(self, codes):
+        """Bulk import of already encoded vectors (uint8 [n, M]) behind the stored ones, sequential ids (the FAISS reader's path)."""
+        codes = np.ascontiguousarray(codes, dtype=np.uint8)
+        assert codes.ndim == 2 and codes.shape[1] == self.M
+        n0 = self.ntotal
+        ids = np.arange(n0, n0 + len(codes), dtype=np.int64)
+        if len(codes):
+            _check(lib().rsx_add_list(self._h, ctypes.c_int64(0), ctypes.c_int64(len(codes)), codes.ctypes.data_as(ctypes.c_void_p), _F32,
+                                      ids.ctypes.data_as(ctypes.c_void_p)))
+
+    def reconstruct_n(self, i0=0, n=None):
+        """Decoded vectors float32 [n, d] of the stored codes i0 .. i0 + n - 1 (host arithmetic on the exported codes)."""
+        codes, _ = self.get_list(0)
+        codes = codes[i0:] if n is None else codes[i0:i0 + n]
+        cb = self.get_codebooks()
+        dsub = self.d // self.M
+        out = np.empty((len(codes), self.d), dtype=np.float32)
+        for m in range(self.M):
+            out[:, m * dsub:(m + 1) * dsub] = cb[m][codes[:, m]]
+        return out
+
+
 # ------------------------------------------------------------------------------------------
 # persistence
 # ------------------------------------------------------------------------------------------
@@ -663,12 +702,12 @@ def _wrap_handle(h):
         return v.value
 
     kind, d, metric = g("kind"), g("d"), g("metric")
-    cls = {0: IndexFlat, 1: IndexIVFFlat, 2: IndexIVFPQ}[kind]
+    cls = {0: IndexFlat, 1: IndexIVFFlat, 2: IndexIVFPQ, 3: IndexPQ}[kind]
     obj = cls.__new__(cls)
     Index.__init__(obj, h, d, metric)
-    if kind == 2:
+    if kind in (2, 3):
         obj.M, obj.nbits = g("M"), g("nbits")
-    if kind != 0:
+    if kind in (1, 2):
         obj.quantizer = None
     return obj
 

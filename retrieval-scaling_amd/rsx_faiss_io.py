@@ -1,4 +1,4 @@
-"""FAISS on-disk index format (.faiss) reader / writer for the three index types of the path.
+"""FAISS on-disk index format (.faiss) reader / writer for the index types of the path (Flat, IVF-Flat, IVF-PQ) and IndexPQ.
 
 Reference call sites: faiss.read_index / faiss.write_index in src/indicies/flat.py:39,63,69,
 ivf_flat.py:71,167,170,185, ivf_pq.py:75,171,174,190 — and the released MassiveDS artefacts
@@ -14,6 +14,10 @@ FAISS-produced file is available offline, so byte-compatibility with real FAISS 
   IndexIVFFlat: "IwFl" | ivf header | inverted lists
   IndexIVFPQ  : "IwPQ" | ivf header | by_residual u8 | code_size u64 | PQ (d u64, M u64, nbits u64,
                 centroids: u64 n + f32[n], laid out [M][256][dsub]) | inverted lists
+  IndexPQ     : "IxPq" | header | PQ (as above) | codes (u64 n + u8[n], n = ntotal * M) | search_type i32 (0 = ST_PQ)
+                | encode_signs u8 | polysemous_ht i32      (contriever/src/index.py:19 builds this class; like the other
+                containers restated from upstream knowledge of index_write.cpp and UNVERIFIED against a FAISS-produced file;
+                the legacy "IxPQ" / "IxPo" magics are not read)
   inv. lists  : "ilar" | nlist u64 | code_size u64 | "full" + sizes (u64 n + u64[n])
                                                    | "sprs" + (list, size) pairs (u64 n + u64[n])
                 then per non-empty list: codes (size*code_size bytes) followed by ids (i64[size])
@@ -137,7 +141,15 @@ def _read_index(r):
         h.update(kind="IVFPQ", fourcc=cc, M=M, nbits=nbits,
                  codebooks=cen.reshape(M, 1 << nbits, pq_d // M), invlists=_read_invlists(r))
         return h
-    raise RuntimeError(f"unsupported FAISS index type '{cc}' (supported: IxFI, IxF2, IwFl, IwPQ)")
+    if cc == "IxPq":
+        h = _read_header(r)
+        pq_d, M, nbits = r.u64(), r.u64(), r.u64()
+        cen = r.vector(np.float32)
+        codes = r.vector(np.uint8)
+        h.update(kind="PQ", fourcc=cc, M=M, nbits=nbits, codebooks=cen.reshape(M, 1 << nbits, pq_d // M),
+                 codes=codes.reshape(-1, M), search_type=r.i32(), encode_signs=bool(r.u8()), polysemous_ht=r.i32())
+        return h
+    raise RuntimeError(f"unsupported FAISS index type '{cc}' (supported: IxFI, IxF2, IwFl, IwPQ, IxPq)")
 
 
 def parse_faiss(path_or_bytes):
@@ -184,12 +196,28 @@ def _w_invlists(out, code_size, codes, ids):
             out.write(np.ascontiguousarray(i, dtype=np.int64).tobytes())
 
 
+def _w_pq(out, d, ntotal, is_trained, metric, M, codebooks, code_blocks, search_type=0, encode_signs=False, polysemous_ht=0):
+    """The IxPq container; code_blocks: uint8 arrays that together hold the ntotal * M code bytes."""
+    out.write(b"IxPq")
+    _w_header(out, d, ntotal, is_trained, metric)
+    out.write(struct.pack("<QQQ", d, M, 8))
+    _w_vector(out, codebooks, np.float32)
+    out.write(struct.pack("<Q", int(ntotal) * int(M)))
+    for c in code_blocks:
+        out.write(np.ascontiguousarray(c, dtype=np.uint8).tobytes())
+    out.write(struct.pack("<iBi", int(search_type), 1 if encode_signs else 0, int(polysemous_ht)))
+
+
 def serialize_faiss(p):
     """Inverse of parse_faiss for the dict layout it returns (only the fields it needs)."""
     out = io.BytesIO()
     kind = p["kind"]
     if kind == "Flat":
         _w_flat(out, p["d"], p["metric"], p["vectors"])
+        return out.getvalue()
+    if kind == "PQ":
+        _w_pq(out, p["d"], p["ntotal"], p["is_trained"], p["metric"], p["M"], p["codebooks"], [p["codes"]],
+              p.get("search_type", 0), p.get("encode_signs", False), p.get("polysemous_ht", 0))
         return out.getvalue()
     out.write(b"IwFl" if kind == "IVFFlat" else b"IwPQ")
     _w_header(out, p["d"], p["ntotal"], p["is_trained"], p["metric"])
@@ -213,9 +241,13 @@ def serialize_faiss(p):
 # ------------------------------------------------------------------------------------------ rsx bridge
 def index_to_parsed(index):
     """rsx index -> the dict layout above (vectors / codes pulled out of HBM list by list)."""
-    kind = {0: "Flat", 1: "IVFFlat", 2: "IVFPQ"}[index._get("kind")]
+    kind = {0: "Flat", 1: "IVFFlat", 2: "IVFPQ", 3: "PQ"}[index._get("kind")]
     p = {"kind": kind, "d": index.d, "metric": index.metric_type, "ntotal": index.ntotal,
          "is_trained": index.is_trained}
+    if kind == "PQ":
+        p.update(M=index.M, nbits=8, codes=index.get_list(0)[0], search_type=0, encode_signs=False, polysemous_ht=0,
+                 codebooks=index.get_codebooks() if index.is_trained else np.zeros((index.M, 256, index.d // index.M), np.float32))
+        return p
     if kind == "Flat":
         p["vectors"], ids = index.get_list(0)
         if len(ids) and not np.array_equal(ids, np.arange(len(ids))):
@@ -237,8 +269,8 @@ def write_faiss_index(index, path):
     """rsx index -> .faiss file, STREAMED: the header blocks first, then one inverted list at a time out of HBM (a 100M x 96-byte
     IVF-PQ index is 10.4 GB; nothing here holds more than one list on the host).  Byte-identical to
     serialize_faiss(index_to_parsed(index))."""
-    kind = {0: "Flat", 1: "IVFFlat", 2: "IVFPQ"}[index._get("kind")]
-    if kind == "Flat":
+    kind = {0: "Flat", 1: "IVFFlat", 2: "IVFPQ", 3: "PQ"}[index._get("kind")]
+    if kind in ("Flat", "PQ"):      # (an IndexPQ of 100M x 96 bytes is 9.6 GB of codes: one list, exported in one piece)
         data = serialize_faiss(index_to_parsed(index))
         with open(path, "wb") as f:
             f.write(data)
@@ -284,6 +316,18 @@ def index_from_parsed(p, device=None, devices=None):
         ix = rsx.IndexFlat(d, metric, device=device, devices=devices)
         if len(p["vectors"]):
             ix.add(p["vectors"])
+        return ix
+    if kind == "PQ":
+        if devices is not None and len(devices) > 1:
+            raise RuntimeError("an IndexPQ file cannot be loaded onto several devices (no sharded form)")
+        if p["nbits"] != 8:
+            raise RuntimeError("only nbits = 8 IndexPQ files are supported")
+        if p.get("search_type", 0) != 0:
+            raise RuntimeError("only IndexPQ files with search_type ST_PQ are supported (no polysemous search)")
+        ix = rsx.IndexPQ(d, p["M"], 8, metric, device=device)
+        if p["is_trained"]:
+            ix.set_codebooks(p["codebooks"])
+            ix.add_codes(p["codes"])
         return ix
     q = p["quantizer"]
     if q["kind"] != "Flat" or q["metric"] != METRIC_INNER_PRODUCT:
