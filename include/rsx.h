@@ -80,10 +80,12 @@ int rsx_ivfpq_create(int d, int nlist, int M, int nbits, int metric, int device,
  * library's subsample and seed); add = per-subspace nearest codeword, sequential ids (ids must be NULL: IndexFlatCodes has no
  * add_with_ids); search scores EVERY stored code with the query's table — inner product: the fp32 sum of the M table entries in
  * sub-quantiser order, best first; L2: squared distance to the decoded vector, ascending; equal scores by id ascending.
- * Inner product takes the staged filtered scan: every query scans every code against its 8-bit table in
+ * Both metrics take the staged filtered scan: every query scans every code against its 8-bit table in
  * stages over disjoint tile sets, the per-query threshold rising between stages, then the exact re-score and certificate of the
- * IVF-PQ fast scan; device memory beside the codes does not grow with ntotal.  L2 and the layouts without a work-item scan take
- * the exact scans; past 2 GiB of codes in the one list only the staged scan and the exact scans of the rotated / sliced layouts (and L2)
+ * IVF-PQ fast scan; device memory beside the codes does not grow with ntotal.  Under L2 the table holds the NEGATED squared
+ * sub-vector distances (the one list's centroid is zero, so the table is per query; the sum of its entries is bit for bit
+ * -distance) and the fp32 tables of a batch are kept for the re-score (M KiB per query).  The layouts without a work-item scan
+ * (granule; M not in {16, 32, 64, 96, 128}) take the exact scans; past 2 GiB of codes in the one list only the staged scan and the exact scans of the rotated / sliced layouts (and L2)
  * are served, any other routing of a search is refused (RSX_ERR_UNSUPPORTED).  rsx_get "kind" = RSX_KIND_PQ; list calls see ONE list (number 0) in insertion order.  Refused with a message:
  * selectors (RSX_ERR_UNSUPPORTED, as FAISS 1.8.0's IndexPQ::search refuses search parameters), rsx_remove_ids and sharded
  * handles of this kind (RSX_ERR_UNSUPPORTED), "add_list_mod", rsx_set_nprobe, rsx_assign, rsx_reserve_lists,
@@ -217,7 +219,8 @@ int rsx_get(rsx_index_t* h, const char* key, int64_t* out);
 /* Tuning knobs that do not change results: "query_batch" (max queries per internal pass),
  * "scan_chunk" (vectors per scan work item, 0 = auto), "scan_kernel" (IVFPQ: 0 = auto, 1 = per-pair
  * v1 kernel, 2 = exact list-major kernel; non-zero disables the fast scan), "pq_fast" (IVFPQ: 1 = 8-bit-table
- * fast scan with certified exact re-rank [default], 0 = exact scan only), "pq_fast_kp" (candidates kept by the
+ * fast scan with certified exact re-rank [default], 0 = exact scan only; IndexPQ: 1 = the staged scan for inner product and L2,
+ * 0 = the exact scan of its metric), "pq_fast_kp" (candidates kept by the
  * fast scan, 0 = auto), "pq_filter" (fast scan: 1 = candidates filtered inside the scan kernel [default], 0 = full
  * score buffer), "pq_pre_rows" (filtered fast scan: vectors of each query's closest list scored by the threshold
  * pre-pass, default 2048, 0 = one scan tile), "ivf_filter" (IVF-Flat: candidates filtered inside the list scan: 1 = when

@@ -166,11 +166,16 @@ static BatchPlan plan_batch(rsx_index* h, int64_t nq, const void* dq, int dtype,
     P.nprobe = std::min(h->nprobe, h->nlist);
     // IVFPQ fast path: needs the 16-byte-granule layout, 16-bit integer sums, and K' <= 4096.  The sliced layout has ONE fast kernel: the
     // filtered scan behind the one-launch pre-pass (every other setting takes the exact scan)
-    P.fast = allow_fast && pq && h->metric == RSX_METRIC_INNER_PRODUCT && h->pq_fast != 0 && h->scan_kernel == 0 && (h->CB == 16 || pq_rot_family(h->CB)) && h->M * 255 < 65536;
+    // METRIC_L2: the table depends on the (query, list) pair, so IVF-PQ keeps the exact scan (k_pq_scan_l2) — but an IndexPQ is one list with a
+    // ZERO centroid: a per-query table again, built negated (k_pq_lut8f<_, true>), and served by the staged scan below or not at all
+    const bool l2 = h->metric == RSX_METRIC_L2;
+    P.fast = allow_fast && pq && (!l2 || h->flat_pq) && h->pq_fast != 0 && h->scan_kernel == 0 && (h->CB == 16 || pq_rot_family(h->CB)) && h->M * 255 < 65536;
     if (P.fast) { kp_for(h, k, true, P.KP, P.BUF); if (P.KP > 4096) P.fast = false; }
     // IndexPQ: one list scanned by every query — the work-item scans of the block layouts, in stages (no score rows).  Every
     // other layout and setting of such a handle takes the one-list IVF-PQ routes (score rows cut by the temp budget) and is as correct
     P.staged = P.fast && h->flat_pq && P.rot && P.pq_filter != 0 && h->pq_prepass_fused != 0 && h->M == h->Mpad && pq_rot_applies(h->M);
+    // (L2: the negated table comes from the VALU builders, and the per-query one must be available — every M the staged route admits fits its LDS up to dsub 60)
+    if (l2 && !(P.staged && pq_lut8_fused_lds(h->M, h->Mpad, h->dsub) <= 160 * 1024 - 64)) P.fast = P.staged = false;
     if (P.fast && P.sliced && !((P.nprobe > 1 || P.staged) && P.pq_filter != 0 && h->pq_prepass_fused != 0)) P.fast = false;
     kp_for(h, k, P.fast, P.KP, P.BUF);
     P.certify = h->kind != KIND_IVFPQ && allow_fast && h->flat_cert != 0;
@@ -183,11 +188,14 @@ static BatchPlan plan_batch(rsx_index* h, int64_t nq, const void* dq, int dtype,
     // (not with the side-stream table build: it reads the fp32 copy before the GEMM has run)
     P.q16_direct = pq && P.coarse_fast && h->overlap == 0 && dtype == RSX_F16 && h->d == h->ld && nq % 128 == 0 && ((uintptr_t)dq & 15) == 0;
     P.pq_fused_lut = pq && P.fast && pq_lut8_fused_lds(h->M, h->Mpad, h->dsub) <= 160 * 1024 - 64;
-    P.side_lut = P.pq_fused_lut && h->overlap != 0 && h->dsub == 8 && h->lut_tiled != 0 && nq >= 64;
+    P.side_lut = P.pq_fused_lut && !l2 && h->overlap != 0 && h->dsub == 8 && h->lut_tiled != 0 && nq >= 64;      // (the side-stream split is a tiled-builder form)
     // the finalize-from-the-row kernel (k_pq_final_tab) will serve this batch: let the table builder store the fp32 tables for it
     // (M KiB per query, 100 MB at M = 96 / batch 1024) instead of every query's workgroup re-deriving its table from the 786 KB codebook
     P.tab_expected = P.pq_fused_lut && P.rot && h->pq_final_tab != 0 && (h->pq_final_tab == 2 || P.KP >= 512 || h->dsub > 8) &&
                      (P.nprobe > 1 || P.staged) && P.pq_filter != 0 && h->pq_prepass_fused != 0 && pq_final_tab_capacity(h->M, h->CB, k) > 0;
+    // L2 always stores them: every exact re-score (k_finalize, k_pq_rescore_all, k_pq_final_tab) then READS its entries, and the code that
+    // re-derives inner-product entries from the codebook needs no second metric
+    P.tab_expected = P.tab_expected || (P.fast && l2);
     // the matrix-core table build will serve this batch and the fast coarse quantiser runs: its first pass rides in the probe-pick launch
     P.lut_pass0_early = P.coarse_fast && P.pq_fused_lut && !P.side_lut && h->dsub == 8 && h->lut_tiled >= 2 && h->metric == RSX_METRIC_INNER_PRODUCT &&
                         h->pq_lut_early != 0;
@@ -375,7 +383,7 @@ static void fork_side_tables(rsx_index* h, const BatchPlan& P) {
     HIPCHECK(hipEventRecord(h->ev_fork, h->st));
     HIPCHECK(hipStreamWaitEvent(h->st2, h->ev_fork, 0));
     launch_pq_lut8(nullptr, h->w_q32.as<float>(), h->ld, h->d_codebooks.as<float>(), h->dsub, P.nq, h->M, h->Mpad, nullptr, 0,
-                   h->w_lut8.as<uint8_t>(), h->w_qparam.p, h->w_lutws.p, P.sliced ? 2 : P.rot ? 1 : 0, h->st2, 1, lut32_out(h, P));
+                   h->w_lut8.as<uint8_t>(), h->w_qparam.p, h->w_lutws.p, P.sliced ? 2 : P.rot ? 1 : 0, h->st2, h->metric, 1, lut32_out(h, P));
     HIPCHECK(hipEventRecord(h->ev_lut, h->st2));
 }
 static FinalizeArgs finalize_args(rsx_index* h, const BatchPlan& P, float* dD, int64_t* dI) {
@@ -622,7 +630,7 @@ static void build_pq_tables(rsx_index* h, const BatchPlan& P, void* lut_ws, cons
     if (P.side_lut) HIPCHECK(hipStreamWaitEvent(h->st, h->ev_lut, 0));     // the tables were built beside the probe selection
     launch_pq_lut8(P.pq_fused_lut ? nullptr : h->w_lut.as<float>(), h->w_q32.as<float>(), h->ld, h->d_codebooks.as<float>(), h->dsub, P.nq, h->M,
                    h->Mpad, h->w_dis0.as<float>(), P.nprobe, h->w_lut8.as<uint8_t>(), h->w_qparam.p, lut_ws, P.sliced ? 2 : P.rot ? 1 : 0, h->st,
-                   P.side_lut ? 2 : 0, lut32_out(h, P), (lut_ws && !P.side_lut && h->lut_tiled >= 2) ? (P.lut_pass0_early ? 2 : 1) : 0, pg);
+                   h->metric, P.side_lut ? 2 : 0, lut32_out(h, P), (lut_ws && !P.side_lut && h->lut_tiled >= 2) ? (P.lut_pass0_early ? 2 : 1) : 0, pg);
     tm.mark("lut8");
 }
 // the fast scan's tiles and its threshold pre-pass: vectors per lane (vpl, tile_rows = 1024 vpl), the pre-pass sample and its form
@@ -1172,7 +1180,9 @@ static void finalize_stage(rsx_index* h, const BatchPlan& P, const BatchResult& 
     if (P.fast) {
         fa.pq_rescore = 1; fa.codes = h->data.as<uint8_t>(); fa.M = h->M; fa.Mpad = h->Mpad; fa.CB = h->CB;
         plain_codes(h, P, fa);
-        fa.lut32 = P.pq_fused_lut ? nullptr : h->w_lut.as<float>(); fa.codebooks = h->d_codebooks.as<float>(); fa.dsub = h->dsub;
+        fa.lut32 = P.pq_fused_lut ? nullptr : h->w_lut.as<float>();
+        if (h->metric == RSX_METRIC_L2) fa.lut32 = lut32_out(h, P);       // the negated tables the builder stored (plan: tab_expected)
+        fa.codebooks = h->d_codebooks.as<float>(); fa.dsub = h->dsub;
         fa.probe_dis0 = h->w_dis0.as<float>(); fa.qparam = h->w_qparam.p;
         fa.uncertain = h->w_uncertain.as<int32_t>();
         if (R.filtered) { fa.cand_cnt = h->w_candcnt.as<unsigned long long>(); fa.cand_cap = R.cand_cap; }

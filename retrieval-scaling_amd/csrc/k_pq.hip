@@ -363,7 +363,9 @@ __global__ __launch_bounds__(256) void k_pq_lut8(const float* lut32, int M, int 
 // hence the same bits) straight into LDS, derives the affine 8-bit quantisation from it and writes only
 // the u8 table + parameters.  The fp32 table (98 KB/query) never touches HBM; k_finalize recomputes the
 // few entries the exact re-score needs.  LDS: Mpad*1 KiB table + the query + 3*Mpad floats.
-template <int DSUB>   // 8: two float4 loads per codeword; 0: generic dsub
+// L2 (IndexPQ, METRIC_L2: one list with a zero centroid, so the residual query is the query): T[m][c] = -|q_m - cb[m][c]|^2, the negated
+// pq_l2_entry — 0 + sum_m T[m][code_m] is bit for bit -distance, and the quantisation below, the scans and the certificate see a table like any other.
+template <int DSUB, bool L2 = false>   // 8: two float4 loads per codeword; 0: generic dsub
 __global__ __launch_bounds__(256) void k_pq_lut8f(const float* Q32, int ldq, const float* codebooks, int dsub, int M,
                                                   int Mpad, const float* probe_dis0, int nprobe, uint8_t* lut8,
                                                   PQQParam* qp, int transposed, float* lut32_out) {
@@ -385,12 +387,18 @@ __global__ __launch_bounds__(256) void k_pq_lut8f(const float* Q32, int ldq, con
             const float4* cw = (const float4*)(codebooks + ((int64_t)m * 256 + c) * 8);
             float4 x = cw[0], y = cw[1];
             const float* qs = s_q + m * 8;
+            if (L2) {
+                const float cw8[8] = {x.x, x.y, x.z, x.w, y.x, y.y, y.z, y.w};
+                s = -pq_l2_entry(qs, cw8, 8);
+            } else {
             s = __fmaf_rn(qs[0], x.x, s); s = __fmaf_rn(qs[1], x.y, s); s = __fmaf_rn(qs[2], x.z, s); s = __fmaf_rn(qs[3], x.w, s);
             s = __fmaf_rn(qs[4], y.x, s); s = __fmaf_rn(qs[5], y.y, s); s = __fmaf_rn(qs[6], y.z, s); s = __fmaf_rn(qs[7], y.w, s);
+            }
         } else {
             const float* cw = codebooks + ((int64_t)m * 256 + c) * dsub;
             const float* qs = s_q + m * dsub;
-            for (int t = 0; t < dsub; t++) s = __fmaf_rn(qs[t], cw[t], s);
+            if (L2) s = -pq_l2_entry(qs, cw, dsub);
+            else for (int t = 0; t < dsub; t++) s = __fmaf_rn(qs[t], cw[t], s);
         }
         T[m * 256 + c] = s;
         if (lut32_out) lut32_out[(q * Mpad + m) * 256 + c] = s;      // the fp32 table for k_pq_final_tab (round 4): M KiB per query
@@ -471,7 +479,7 @@ __device__ __forceinline__ float lut_coarsen(float u) {
 #ifndef LT_QC
 #define LT_QC 8      // queries per tile: 32 -> 8 quadruples the workgroups (1536 at batch 1024), measured 0.135 -> 0.100 ms for the build
 #endif
-template <int PASS>
+template <int PASS, bool L2 = false>      // L2: the negated squared-distance entries of an L2 IndexPQ (see k_pq_lut8f)
 __global__ __launch_bounds__(256) void k_pq_lut_tiled(const float* Q32, int ldq, const float* codebooks, int M, int Mpad,
                                                       int64_t nq, float* mnmx, float* errb, uint8_t* lut8, int transposed, float* lut32_out) {
     __shared__ float s_q[LT_QC * LT_MB * 8];     // the tile's query slices
@@ -530,8 +538,13 @@ __global__ __launch_bounds__(256) void k_pq_lut_tiled(const float* Q32, int ldq,
 #pragma unroll
             for (int j = 0; j < 4; j++) {
                 float t = 0.0f;
+                if (L2) {
+                    const float q8[8] = {q0_, q1_, q2_, q3_, q4_, q5_, q6_, q7_}, cw8[8] = {cx[j].x, cx[j].y, cx[j].z, cx[j].w, cy[j].x, cy[j].y, cy[j].z, cy[j].w};
+                    t = -pq_l2_entry(q8, cw8, 8);
+                } else {
                 t = __fmaf_rn(q0_, cx[j].x, t); t = __fmaf_rn(q1_, cx[j].y, t); t = __fmaf_rn(q2_, cx[j].z, t); t = __fmaf_rn(q3_, cx[j].w, t);
                 t = __fmaf_rn(q4_, cy[j].x, t); t = __fmaf_rn(q5_, cy[j].y, t); t = __fmaf_rn(q6_, cy[j].z, t); t = __fmaf_rn(q7_, cy[j].w, t);
+                }
                 v[j] = t;
             }
             if (PASS == 0) {
@@ -780,8 +793,30 @@ size_t pq_lut8_fused_lds(int M, int Mpad, int dsub) { return ((size_t)Mpad * 256
 
 void launch_pq_lut8(const float* lut32, const float* Q32, int ldq, const float* codebooks, int dsub, int64_t nq, int M,
                     int Mpad, const float* probe_dis0, int nprobe, uint8_t* lut8, void* qparam, void* ws, int transposed,
-                    hipStream_t st, int phase, float* lut32_out, int mfma, const PairGroupArgs* pg) {
+                    hipStream_t st, int metric, int phase, float* lut32_out, int mfma, const PairGroupArgs* pg) {
     if (nq <= 0) return;
+    if (metric != 0) {      // L2 (rsx_metric, as FinalizeArgs::metric): a squared difference is no contraction, so never the matrix-core builder
+        if (ws && dsub == 8) {      // the VALU tiles (measured at M = 96, batch 1024: the per-query builder below takes 0.30 ms): two passes + the parameters
+            float* mnmx = reinterpret_cast<float*>(ws);
+            float* errb = mnmx + (size_t)nq * Mpad * 2;
+            const int64_t nmb = (Mpad + LT_MB - 1) / LT_MB, nqt8 = (((nq + LT_QC - 1) / LT_QC) + 7) / 8;
+            const dim3 grid((unsigned)(nmb * nqt8 * 8));
+            const size_t osm = transposed ? (size_t)LT_QC * 256 * LT_MB : 0;
+            static DevOnce once_t;
+            if (osm) once_t.once([&] { hipFuncSetAttribute((const void*)k_pq_lut_tiled<1, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)osm); });
+            hipLaunchKernelGGL((k_pq_lut_tiled<0, true>), grid, dim3(256), 0, st, Q32, ldq, codebooks, M, Mpad, nq, mnmx, errb, lut8, transposed, (float*)nullptr);
+            hipLaunchKernelGGL((k_pq_lut_tiled<1, true>), grid, dim3(256), osm, st, Q32, ldq, codebooks, M, Mpad, nq, mnmx, errb, lut8, transposed, lut32_out);
+            hipLaunchKernelGGL(k_pq_qparam, dim3((unsigned)nq), dim3(64), 0, st, nq, M, Mpad, mnmx, errb, probe_dis0, nprobe, (PQQParam*)qparam);
+            return;
+        }
+        const size_t lds = pq_lut8_fused_lds(M, Mpad, dsub);
+        auto kern = dsub == 8 ? k_pq_lut8f<8, true> : k_pq_lut8f<0, true>;
+        static DevOnce once8, once0;
+        (dsub == 8 ? once8 : once0).once([&] { hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); });
+        hipLaunchKernelGGL(kern, dim3((unsigned)nq), dim3(256), lds, st, Q32, ldq, codebooks, dsub, M, Mpad, probe_dis0, nprobe,
+                           lut8, (PQQParam*)qparam, transposed, lut32_out);
+        return;
+    }
     if (phase != 0 && !(ws && dsub == 8 && !lut32)) return;     // only the tiled build splits into tables (1) + per-query parameters (2)
     if (lut32) {
         hipLaunchKernelGGL(k_pq_lut8, dim3((unsigned)nq), dim3(256), 0, st, lut32, M, Mpad, probe_dis0, nprobe, lut8,

@@ -2107,7 +2107,8 @@ __global__ __launch_bounds__(1024) void k_pq_scan_rot_exact(PQScanArgs a) {
 // builds the pair's fp32 table in LDS (M x 256 fmaf chains of dsub terms: the arithmetic the CPU restatement under oracle/ fixes for this metric) and scans
 // its chunk with one thread per vector, sums in m order.  Scores leave NEGATED (every selection downstream keeps the largest keys;
 // k_finalize hands back the distance).  Any code layout (byte loads through pq_code_addr): correct first, not tuned — 2 x 256 x M x dsub
-// flops of table build per (query, list, chunk) bound it, not the scan.
+// flops of table build per (query, list, chunk) bound it, not the scan.  (An L2 IndexPQ — one list, zero centroid: a per-query table — takes the
+// staged 8-bit scan instead and comes here for pq_fast = 0, the layouts without a work-item scan and the exact re-run of flagged queries.)
 // ---------------------------------------------------------------------------------------
 __global__ __launch_bounds__(1024) void k_pq_scan_l2(PQScanArgs a, const float* __restrict__ Q32, int ldq, const float* __restrict__ centroids,
                                                      const float* __restrict__ codebooks, int d, int dsub) {
@@ -2130,12 +2131,7 @@ __global__ __launch_bounds__(1024) void k_pq_scan_l2(PQScanArgs a, const float* 
     __syncthreads();
     for (int e = tid; e < a.Mpad * 256; e += 1024) {
         const int m = e >> 8, c = e & 255;
-        float acc = 0.0f;
-        if (m < a.M) {
-            const float* cw = codebooks + ((int64_t)m * 256 + c) * dsub;
-            for (int t = 0; t < dsub; t++) { const float df = __fsub_rn(qr[m * dsub + t], cw[t]); acc = __fmaf_rn(df, df, acc); }
-        }
-        l2_tab[e] = acc;
+        l2_tab[e] = m < a.M ? pq_l2_entry(qr + m * dsub, codebooks + ((int64_t)m * 256 + c) * dsub, dsub) : 0.0f;
     }
     __syncthreads();
     const int64_t row0 = a.list_base[l];

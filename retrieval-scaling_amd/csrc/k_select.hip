@@ -1998,7 +1998,10 @@ __device__ __forceinline__ void ft_for_keys(const uint64_t* row, int n, int tid,
         for (int u = 0; u < 8; u++) { const int c = c0 + u * 1024; if (c < n) f(c, kk[u]); }
     }
 }
-template <int NRUN>      // M / 16: the 16-sub-quantiser runs of a code vector (1, 2, 4, 6, 8)
+// L2 (an L2 IndexPQ: FinalizeArgs::metric != 0): the table is the builder's negated one (always stored: lut32) and the scores travel negated;
+// only the emission differs — the distance 0 - s, +inf padding, as k_finalize's.  A template parameter, so that the inner-product kernels
+// are the code they were.
+template <int NRUN, bool L2 = false>      // NRUN = M / 16: the 16-sub-quantiser runs of a code vector (1, 2, 4, 6, 8)
 __global__ __launch_bounds__(1024) void k_pq_final_tab(FinalizeArgs a, uint64_t* cand, int cand_cap, int P, uint64_t* tie_ws, int stage_probes, int bm_off, int wq_off, int wq_cap) {
     extern __shared__ __attribute__((aligned(16))) float ft_T[];
     const int M = a.M, dsub = a.dsub;
@@ -2363,7 +2366,9 @@ __global__ __launch_bounds__(1024) void k_pq_final_tab(FinalizeArgs a, uint64_t*
     FT_MARK(5);
     for (int j = tid; j < a.k; j += 1024) {
         const bool valid = j < ns && sord[j] != 0u && sid[j] != INT64_MAX;
-        a.D[q * a.k + j] = valid ? ord2f(sord[j]) : -__builtin_inff();
+        float s = valid ? ord2f(sord[j]) : -__builtin_inff();
+        if (L2) s = valid ? (0.0f - s) : __builtin_inff();
+        a.D[q * a.k + j] = s;
         a.I[q * a.k + j] = valid ? sid[j] : -1;
     }
     if (tid == 0) a.uncertain[q] = 0;
@@ -2429,12 +2434,18 @@ void launch_pq_final_tab(const FinalizeArgs& a, uint64_t* cand, int cand_cap, ui
     }
     static DevSize attr;
     auto kern = a.M == 16 ? k_pq_final_tab<1> : a.M == 32 ? k_pq_final_tab<2> : a.M == 64 ? k_pq_final_tab<4> : a.M == 96 ? k_pq_final_tab<6> : k_pq_final_tab<8>;
+    if (a.metric != 0) kern = a.M == 16 ? k_pq_final_tab<1, true> : a.M == 32 ? k_pq_final_tab<2, true> : a.M == 64 ? k_pq_final_tab<4, true> : a.M == 96 ? k_pq_final_tab<6, true> : k_pq_final_tab<8, true>;
     attr.grow(shm, [&] {
         (void)hipFuncSetAttribute((const void*)k_pq_final_tab<1>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
         (void)hipFuncSetAttribute((const void*)k_pq_final_tab<2>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
         (void)hipFuncSetAttribute((const void*)k_pq_final_tab<4>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
         (void)hipFuncSetAttribute((const void*)k_pq_final_tab<6>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
         (void)hipFuncSetAttribute((const void*)k_pq_final_tab<8>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+        (void)hipFuncSetAttribute((const void*)k_pq_final_tab<1, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+        (void)hipFuncSetAttribute((const void*)k_pq_final_tab<2, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+        (void)hipFuncSetAttribute((const void*)k_pq_final_tab<4, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+        (void)hipFuncSetAttribute((const void*)k_pq_final_tab<6, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+        (void)hipFuncSetAttribute((const void*)k_pq_final_tab<8, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
     });
     hipLaunchKernelGGL(kern, dim3((unsigned)a.nq), dim3(1024), shm, st, a, cand, cand_cap, P, tie_ws, stage_probes, bm_off, wq_off, wq_cap);
 }

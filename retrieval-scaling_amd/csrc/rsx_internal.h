@@ -142,6 +142,15 @@ __host__ __device__ inline bool pq_rot_family(int CB) { return CB == 0 || CB == 
 __host__ __device__ inline int64_t pq_lut8_index(int64_t q, int c, int m, int Mpad, int mode) {
     return mode == 0 ? (q * Mpad + m) * 256 + c : mode == 1 ? (q * 256 + c) * Mpad + m : ((q * (Mpad >> 5) + (m >> 5)) * 256 + c) * 32 + (m & 31);
 }     // block layouts: transposed tables, work-item scans
+// METRIC_L2 table entry, THE definition: squared distance of a query's (residual) sub-vector qs[0..dsub) to one codeword, the oracle's
+// chain (the CPU restatement under oracle/: df = qr - cb, acc = fmaf(df, df, acc) from +0).  k_pq_scan_l2 sums the entries; the 8-bit table builder of an
+// L2 IndexPQ (k_pq_lut8f<_, true>) stores them NEGATED, so that 0 + sum_m T'[m][code_m] is bit for bit -distance (negation is exact,
+// rounding symmetric) and everything downstream keeps "largest score wins".
+__device__ __forceinline__ float pq_l2_entry(const float* qs, const float* cw, int dsub) {
+    float acc = 0.0f;
+    for (int t = 0; t < dsub; t++) { const float df = __fsub_rn(qs[t], cw[t]); acc = __fmaf_rn(df, df, acc); }
+    return acc;
+}
 // The two 8-byte halves of the piece that holds sub-quantisers 16 run .. 16 run + 15 of vector `row` (M >= 32, rotated or sliced layout);
 // rotated left by row & 15 bytes (rot16_bytes, k_select.hip) the 16 bytes are the codes in m order.
 __device__ inline void pq_piece_ptrs(const uint8_t* codes, int64_t row, int M, int CB, int run, const uint8_t*& p0, const uint8_t*& p1) {
@@ -292,6 +301,8 @@ void launch_pq_lut8(const float* lut32, const float* Q32, int ldq, const float* 
                     void* qparam /* [nq] {scale, bias, eps, pad} */,
                     void* ws /* pq_lut8_tiled_ws(nq, Mpad) bytes -> tiled build (dsub 8), or null */,
                     int transposed /* pq_lut8_index: 0: lut8 [nq][Mpad][256]; 1: [nq][256][Mpad] (rotated-layout scans); 2: [nq][Mpad/32][256][32] (sliced) */, hipStream_t st,
+                    int metric /* rsx_metric; 1 = L2 (IndexPQ only: Q32 is the residual to a zero centroid): negated squared-distance tables by the
+                                  VALU builders only (tiled when ws is given and dsub = 8, else per query), whatever phase / mfma say */,
                     int phase = 0 /* tiled build only: 1 = the tables (independent of the probe selection), 2 = the per-query parameters */,
                     float* lut32_out = nullptr /* fused forms only: also store the fp32 tables [nq][Mpad][256] (k_pq_final_tab reads them) */,
                     int mfma = 0 /* tiled build, phase 0: the matrix-core form (k_pq_lut_mfma: tables and per-query parameters in two launches; 2: its

@@ -658,7 +658,8 @@ class IndexIVFPQ(_IndexIVF):
 class IndexPQ(Index):
     """faiss.IndexPQ(d, M, nbits=8, metric=METRIC_L2): a flat product quantiser — no coarse stage, every query scans every code
     (contriever/src/index.py:19, built by passage_retrieval.py --n_subquantizers; rsx_pq_create).  nbits must be 8.  `pq_layout`
-    (set_param, before the first add) picks the code layout as for IndexIVFPQ; inner product takes the staged filtered scan.
+    (set_param, before the first add) picks the code layout as for IndexIVFPQ; both metrics take the staged filtered scan in the rotated / sliced layouts (L2 through
+    negated per-query tables: the one list's centroid is zero), set_param("pq_fast", 0) switches back to the exact scan.
     No add_with_ids (FAISS's IndexFlatCodes has none), no remove_ids, no search parameters (as FAISS 1.8.0's IndexPQ::search)."""
 
     def __init__(self, d, M, nbits=8, metric=METRIC_L2, device=None):

@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
 """IndexPQ measurement (profiles/indexpq_speed.md): the staged filtered scan of a flat product quantiser on the bench
-generator's data (768 dimensions, NC 4096, seeds as bench.py), inner product, one JSON line per measurement on stdout.
+generator's data (768 dimensions, NC 4096, seeds as bench.py), inner product or (--metric l2, profiles/indexpq_l2_speed.md) L2, one JSON
+line per measurement on stdout.
 
   headline   per (n, M[, layout]) and k: ms per batch of distinct queries (synchronised wall time: median, min, max over --steps
              batches after a warm-up of the shape), then one profiled pass for the stage breakdown ("lut8", "scan0", "scan", "select",
@@ -10,9 +11,10 @@ generator's data (768 dimensions, NC 4096, seeds as bench.py), inner product, on
              codes and codebooks, alternated with IndexPQ in one process, --repeats repeats of --steps batches each; the pass
              condition of profiles/indexpq_speed.md is IndexPQ's slowest repeat against the emulation's fastest
 
-  check      --check Q: the first Q queries' staged result against the exact scan (pq_fast = 0) of the same index
+  check      --check Q: the first Q queries' staged result against the exact scan (pq_fast = 0) of the same index, either metric
+  exact      --pq-fast 0: time the exact scan itself (under L2 the route every L2 IndexPQ took before the staged scan served both metrics)
 
-  python tools/bench_pq.py [--n 10000000] [--ms 64,96] [--ks 10,100,1000] [--layouts 96:2,96:1] [--emulation] [--check 32] [--steps 20]
+  python tools/bench_pq.py [--n 10000000] [--ms 64,96] [--ks 10,100,1000] [--layouts 96:2,96:1] [--emulation] [--check 32] [--steps 20] [--metric ip|l2]
 """
 import argparse, json, os, sys, time
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -23,9 +25,9 @@ D, NC, SC, SX, SQ = 768, 4096, 1234, 10000, 999
 CH = 1_000_000
 
 
-def build(rsx, torch, n, M, layout, cb=None):
+def build(rsx, torch, n, M, layout, cb=None, metric=0):
     dev = torch.device("cuda", 0)
-    ix = rsx.IndexPQ(D, M, 8, rsx.METRIC_INNER_PRODUCT, device=0)
+    ix = rsx.IndexPQ(D, M, 8, metric, device=0)
     if layout is not None:
         ix.set_param("pq_layout", float(layout))
     if cb is None:
@@ -85,9 +87,13 @@ def main():
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--emulation", action="store_true")
     ap.add_argument("--repeats", type=int, default=5)
+    ap.add_argument("--metric", choices=("ip", "l2"), default="ip")
+    ap.add_argument("--pq-fast", type=int, default=1, help="0: time the exact scan (no --check then)")
     ap.add_argument("--check", type=int, default=0, help="queries of the first batch whose staged result is compared with the exact scan (pq_fast = 0)")
     args = ap.parse_args()
     import torch, rsx
+    metric = rsx.METRIC_L2 if args.metric == "l2" else rsx.METRIC_INNER_PRODUCT
+    tag = {} if (args.metric == "ip" and args.pq_fast == 1) else {"metric": args.metric, "pq_fast": args.pq_fast}      # (the default run's lines are unchanged)
     ks = [int(v) for v in args.ks.split(",") if v]
     shapes = [(int(m), None) for m in args.ms.split(",") if m]
     if args.layouts:
@@ -96,25 +102,27 @@ def main():
         Q = queries(rsx, torch, n, args.warmup + args.steps, args.batch)
         for M, layout in shapes:
             t0 = time.time()
-            ix = build(rsx, torch, n, M, layout)
+            ix = build(rsx, torch, n, M, layout, metric=metric)
             print(f"[bench_pq] IndexPQ {n} x {D} M={M} layout={ix._get('pq_layout')} build {time.time() - t0:.1f}s", file=sys.stderr, flush=True)
-            if args.check > 0:      # the exact scan addresses rows with 64-bit offsets and shares nothing with the staged route but the codes
+            if args.check > 0 and args.pq_fast == 1:      # the exact scan addresses rows with 64-bit offsets and shares nothing with the staged route but the codes
                 Df, If = ix.search(Q[:args.batch], ks[0])
                 ix.set_param("pq_fast", 0)
                 De, Ie = ix.search(Q[:args.check], ks[0])
                 ix.set_param("pq_fast", 1)
-                print(json.dumps({"check": "staged scan vs exact scan", "n": n, "M": M, "k": ks[0], "queries": args.check,
+                print(json.dumps({"check": "staged scan vs exact scan", **tag, "n": n, "M": M, "k": ks[0], "queries": args.check,
                                   "same_result": bool(torch.equal(Df[:args.check], De) and torch.equal(If[:args.check], Ie))}), flush=True)
+            if args.pq_fast != 1:
+                ix.set_param("pq_fast", float(args.pq_fast))
             for k in ks:
                 timed(torch, ix, Q, args.batch, k, 0, args.warmup)
                 ms = timed(torch, ix, Q, args.batch, k, args.warmup, args.steps)
-                rec = {"index": "IndexPQ", "n": n, "M": M, "pq_layout": ix._get("pq_layout"), "k": k, "batch": args.batch, "steps": args.steps,
+                rec = {"index": "IndexPQ", **tag, "n": n, "M": M, "pq_layout": ix._get("pq_layout"), "k": k, "batch": args.batch, "steps": args.steps,
                        "ms_median": round(float(np.median(ms)), 3), "ms_min": round(min(ms), 3), "ms_max": round(max(ms), 3)}
                 rec.update(profile_pass(torch, ix, Q, args.batch, k, n))
                 print(json.dumps(rec), flush=True)
             if args.emulation and M == 64:
                 k = ks[0]
-                em = rsx.IndexIVFPQ(rsx.IndexFlatIP(D), D, 1, M, 8, rsx.METRIC_INNER_PRODUCT, device=0)
+                em = rsx.IndexIVFPQ(rsx.IndexFlatIP(D), D, 1, M, 8, metric, device=0)
                 em.set_centroids(np.zeros((1, D), np.float32)); em.set_codebooks(ix.get_codebooks())
                 codes, ids = ix.get_list(0)
                 em.add_list(0, codes, ids); em.nprobe = 1
