@@ -870,7 +870,7 @@ static void pq_staged_scan(rsx_index* h, const BatchPlan& P, BatchResult& R, PQS
                                1, mi, g.vpl, h->w_tau.as<uint64_t>(), 1, h->w_cand.as<uint64_t>(), h->w_candcnt.as<unsigned long long>(), R.cand_cap,
                                rws, log_cap, 0, (h->pq_pace & 0xffff), nullptr, h->w_qitems.as<int32_t>(), tmax, h->st,
                                P.sliced ? (P.sl_eight ? 1 : 0) : h->pq_q8, ts) != 0)
-            RSX_THROW(RSX_ERR_UNSUPPORTED, "IndexPQ staged scan: no kernel for M=%d", h->M);
+            RSX_THROW(RSX_ERR_UNSUPPORTED, "IndexPQ staged scan: no kernel for M=%d at a batch of %lld queries (the sliced 8-query scan takes at most 4 GiB of 8-bit tables per batch)", h->M, (long long)P.nq);
         tm.mark("scan");
         ga.ntiles = nt; ga.nrecs = (int64_t)ng * nt * P.ngq; ga.last = s_ == S - 1;
         launch_pq_stage_gather(ga, nq, h->st);
@@ -919,7 +919,7 @@ static void pq_fast_scan(rsx_index* h, const BatchPlan& P, BatchResult& R, PQSca
                                         pr.total_groups, pr.item_off, pr.total_items, nlist, mi, vpl, h->st)) == 0;
     }
     if (done && R.filtered && !P.staged) done = pq_filtered_scan(h, P, R, a, pr, g, grouped, tm);
-    if (!done) RSX_THROW(RSX_ERR_UNSUPPORTED, "IVFPQ fast scan: no kernel for M=%d", h->M);
+    if (!done) RSX_THROW(RSX_ERR_UNSUPPORTED, "IVFPQ fast scan: no kernel for M=%d at a batch of %lld queries (the sliced 8-query scan takes at most 4 GiB of 8-bit tables per batch)", h->M, (long long)P.nq);
     // rotated layout, threshold by construction: finalize straight from the complete candidate row (k_pq_final_tab) when K'
     // is large or a table entry is a long chain (M = 16: dsub 48) — the K' cut, its certificate and the second chance disappear
     R.tab_fits = R.filtered && R.fused_pre_used && P.rot && h->pq_final_tab != 0 && pq_final_tab_capacity(h->M, h->CB, P.k) > 0;

@@ -97,6 +97,14 @@ typedef unsigned int rot_v2u __attribute__((ext_vector_type(2)));
 __device__ __forceinline__ rot_v2u lds_rd64(uint32_t addr) {      // ds_read_b64: 2 LDS cycles per wave, bank = (addr / 4) % 64
     return *reinterpret_cast<const __attribute__((address_space(3))) rot_v2u*>((uintptr_t)addr);
 }
+// s_setprio takes an immediate, so a priority that depends on a run-time phase needs branches.  Written out by hand: the compiler's
+// form of this four-way choice is a tree of about twelve scalar instructions with flag registers; this one executes five to seven
+// (phase 0 .. 3 -> priority P0 .. P3; a second s_setprio simply overrides the first).
+#define SL8_SETPRIO_ROT(phase, P0, P1, P2, P3)                                                                               \
+    asm volatile("s_bitcmp1_b32 %0, 1\n\ts_cbranch_scc1 1f\n\t"                                                              \
+                 "s_bitcmp1_b32 %0, 0\n\ts_setprio " #P0 "\n\ts_cbranch_scc0 2f\n\ts_setprio " #P1 "\n\ts_branch 2f\n"         \
+                 "1:\n\ts_bitcmp1_b32 %0, 0\n\ts_setprio " #P2 "\n\ts_cbranch_scc0 2f\n\ts_setprio " #P3 "\n"                  \
+                 "2:" : : "s"(phase) : "scc")
 
 // registers of rotation bytes a phase needs: plane 0 packs 4 per dword, planes >= 1 pack 3 + the plane byte
 __host__ __device__ constexpr int rot_nreg(int plane, int steps) { return plane == 0 ? steps / 4 : (steps + 2) / 3; }
@@ -1203,6 +1211,14 @@ __global__ __launch_bounds__(1024) void k_pq_scan_sl4(PQScan8Args A, const PQRot
 // instructions of the 4-query form (k_pq_scan_rot), and a list probed by 5 .. 8 queries is passed over once instead of twice.
 // Work items, thresholds (accumulators start at -threshold: C >= 0 <=> survivor), survivor logs and run descriptors are those of
 // k_pq_scan_rot<.., G = 2>: two 4-query records per item, everything downstream is shared.
+// The block loop (profiles/sl8_block_loop.md; tests/test_scan_codegen.py checks the compiler's output): at 128 VGPRs with four
+// waves per SIMD a wave's per-block dependency chain sets the CU-side floor, so a block body holds the look-ups and little else —
+// code offsets are running sums, "the block exists" is one compare against the wave's count of blocks left, the table loads go
+// through one descriptor with a scalar offset per query slot, the priority choice is five to seven scalar instructions.  Whatever
+// the compiler can hoist out of the 48 unrolled bodies it hoists and then spills (lane masks of comparisons to VGPR lanes, 64-bit
+// lane addresses to scratch): the loop's scalars are therefore made opaque per block, and the item epilogue finds its addresses again.
+// The zero-spill state rests on those empty asm statements at exactly 128 VGPRs; the counts of the write-up were obtained with ROCm
+// 7.2.0 (AMD clang 22.0.0git, roc-7.2.0), and the test is what notices when another compiler undoes it.
 // ---------------------------------------------------------------------------------------
 template <int NS, int NB, int RD>
 __global__ __launch_bounds__(1024) void k_pq_scan_sl8(PQScan8Args A, const PQRotItem* __restrict__ items, uint64_t* __restrict__ log_keys,
@@ -1210,6 +1226,7 @@ __global__ __launch_bounds__(1024) void k_pq_scan_sl8(PQScan8Args A, const PQRot
     static_assert(NS == 3, "zig-zag schedule written for three slices (M = 96)");
     static_assert((NS * NB) % RD == 0 && RD <= NB, "the prefetch slot of a step is a compile-time function of (pass, block)");
     static_assert(NB % 2 == 0, "two blocks' partial sums share a register");
+    static_assert(16 % PQ_SLICED_GB == 0, "a wave's next block (16 blocks on) is the same block of a later slice-major group");
     constexpr int M = 32 * NS, G = 2;
     constexpr int BB = 32 * M;                 // bytes per 32-vector block
     constexpr int TAB = 2 * 65536;             // two table slots
@@ -1227,14 +1244,15 @@ __global__ __launch_bounds__(1024) void k_pq_scan_sl8(PQScan8Args A, const PQRot
     ItemDraw items_of(xcd_ctr, *A.total_items);
     if (items_of.empty()) return;
     // ---- per-lane constants.  Rotation bytes: lane (g, i) reads, at step s, the 8-byte slot 16 (g & 1) + ((i + s) & 15) of its code's
-    // row; three per register, the fourth byte = the table slot of the pass (0 here, 1 in Rb) -> address bit 16
-    uint32_t Ra[6], Rb[6];
+    // row; three per register, the fourth byte = 1: a pass over table slot 1 selects it into address bit 16, a pass over slot 0
+    // selects a zero byte there (the selectors are scalar constants, so one set of registers serves both)
+    uint32_t Ra[6];
 #pragma unroll
     for (int r = 0; r < 6; r++) {
-        uint32_t v = 0;
+        uint32_t v = 0x01000000u;
 #pragma unroll
         for (int bb = 0; bb < 3; bb++) { const int s2 = r * 3 + bb; if (s2 < 16) v |= (uint32_t)(128 * (g & 1) + 8 * ((i + s2) & 15)) << (8 * bb); }
-        Ra[r] = v; Rb[r] = v | 0x01000000u;
+        Ra[r] = v;
     }
     // B one-hot: an A operand = two 8-byte gathers (dwords 0, 2: queries 0-3; 1, 3: queries 4-7) of vector i (K groups 0, 1) or 16 + i
     // (K groups 2, 3): column n = 8 (vector half) + query takes byte query & 3 of the dwords with j & 1 == query >> 2 of its half's K groups
@@ -1255,6 +1273,10 @@ __global__ __launch_bounds__(1024) void k_pq_scan_sl8(PQScan8Args A, const PQRot
         item = items_of.resolve(lane);
         publish_records<G>(&islot[0], load_records<G>(items, item, lane), item, lane);
     }
+    // the batch's tables, [nq][slice][code][32], behind one descriptor bounded by their real size (the launcher refuses a batch whose
+    // tables pass 4 GiB)
+    const uint32_t lut_bytes = (uint32_t)a.nq * (uint32_t)(256 * M);
+    const __amdgpu_buffer_rsrc_t rt = __builtin_amdgcn_make_buffer_rsrc((void*)A.lut8, 0, (int)lut_bytes, 0x00020000);
     int buf = 0;
 #pragma unroll 1
     for (;; buf ^= 1) {
@@ -1273,30 +1295,29 @@ __global__ __launch_bounds__(1024) void k_pq_scan_sl8(PQScan8Args A, const PQRot
         const int so_oob = ((nblk + PQ_SLICED_GB - 1) / PQ_SLICED_GB) * (PQ_SLICED_GB * BB);      // past the descriptor's end: reads zeros
         const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc((void*)(a.codes + (base_row >> 5) * (int64_t)BB), 0, so_oob, 0x00020000);
         const int nsub = bend > tb0 ? (bend - tb0 + 16 * NB - 1) / (16 * NB) : 0;
-        int qq[8];                                                              // the eight queries (SGPRs: they live through the item's re-stagings)
+        // the eight query slots' tables as 32-bit offsets into the table descriptor rt (one SGPR each: they live through the item's
+        // re-stagings).  A slot WITHOUT a query gets the descriptor's end: its loads are out of range — they return zero and fetch
+        // nothing, as so_oob does for the codes
+        uint32_t qo[8];
 #pragma unroll
-        for (int k = 0; k < 8; k++) qq[k] = __builtin_amdgcn_readfirstlane(k < 4 ? it0->q[k] : it1->q[k - 4]);
+        for (int k = 0; k < 8; k++) {
+            const uint32_t q = (uint32_t)__builtin_amdgcn_readfirstlane(k < 4 ? it0->q[k] : it1->q[k - 4]);
+            qo[k] = (k < 4 ? k < np0 : k - 4 < np1) ? q * (uint32_t)(256 * M) : lut_bytes;      // unsigned: the tables may pass 2 GiB
+        }
         // ---- staging of one slice's table into a slot: unit = (code, 4 consecutive m of the slice) -> the eight queries' dwords ->
         // four 8-byte entries (bytes 0-3: record 0's queries, 4-7: record 1's) = 32 contiguous bytes of the code's row.  Two units per
         // thread; issue (16 loads in flight) and write-out are separate so that the loads can travel behind scan blocks.
         // (the tables of query slots WITHOUT a query are not fetched — three slots in ten are empty on the bench batch, and every slice
         //  of table crosses the fabric like a code line does; their accumulators start at -2^30, whatever the slot's table bytes are.
-        //  Scalar base + 32-bit lane offset per load; the offset is made opaque so that the compiler does not keep sixteen 64-bit
-        //  addresses alive — spilled — across the item's passes)
+        //  One descriptor, one lane offset per unit and the slot's scalar offset per load: no 64-bit address, no lane mask and no
+        //  branch per slot)
         // (behind scan blocks the two units travel ONE AT A TIME — eight registers in flight instead of sixteen: they pay for the third code
         //  load in flight per wave)
         uint32_t sin[8];
         auto stage_issue = [&](int sl, int u) {
-            {
-                uint32_t eoff = (uint32_t)((tid + u * 1024) * 4 + sl * 8192);       // lut8 is [q][slice][code][32]: thread e takes dword e of the slice's 8 KiB
-                asm volatile("" : "+v"(eoff));
+            const int eoff = (tid + u * 1024) * 4 + sl * 8192;       // lut8 is [q][slice][code][32]: thread e takes dword e of the slice's 8 KiB
 #pragma unroll
-                for (int k = 0; k < 8; k++) {
-                    sin[k] = 0u;
-                    if (k < 4 ? k < np0 : k - 4 < np1)        // wave-uniform
-                        sin[k] = __builtin_nontemporal_load(reinterpret_cast<const uint32_t*>(A.lut8 + (int64_t)qq[k] * (256 * M) + eoff));
-                }
-            }
+            for (int k = 0; k < 8; k++) sin[k] = __builtin_amdgcn_raw_buffer_load_b32(rt, eoff, (int)qo[k], 2);       // 2 = non-temporal
         };
         auto stage_write = [&](int slot, int u) {
             {
@@ -1320,15 +1341,20 @@ __global__ __launch_bounds__(1024) void k_pq_scan_sl8(PQScan8Args A, const PQRot
         };
         // ---- the code stream: step t = (sub-tile, pass, block j) in scan order; the load of step t + RD is issued when step t's
         // codes have become gather addresses.  Block of (sub-tile st, j): tb0 + 16 (st NB + j) + w; slice of pass p: zig-zag.
+        // A wave's consecutive blocks lie 16 blocks apart — a whole number of slice-major groups, the same block of its group — so
+        // their offsets are RUNNING sums: sbase = slice 0 of the wave's first block of the sub-tile, + CSTEP per block, + the pass's
+        // slice term.  left = the wave's blocks from the sub-tile's first one to the end of the tile (<= 0: none): block j of the
+        // sub-tile exists <=> j < left, block j of the next sub-tile <=> j < left - NB; what does not exist is loaded from so_oob.
+        constexpr int CSTEP = 16 * BB, SLB = PQ_SLICED_GB * 1024;
         auto slice_of = [&](int st, int p) -> int { return (st & 1) ? NS - 1 - p : p; };
-        auto code_off = [&](int st, int p, int j) -> int {
-            const int b = tb0 + 16 * (st * NB + j) + w;
-            return (st < nsub && b < bend) ? (b / PQ_SLICED_GB) * (PQ_SLICED_GB * BB) + slice_of(st, p) * (PQ_SLICED_GB * 1024) + (b % PQ_SLICED_GB) * 1024 : so_oob;
-        };
+        const uint32_t b0 = (uint32_t)(tb0 + w);
+        int bsub = (int)b0;                                                     // the wave's first block of the sub-tile
+        int sbase = (int)((b0 / PQ_SLICED_GB) * (uint32_t)(PQ_SLICED_GB * BB) + (b0 % PQ_SLICED_GB) * 1024u);
+        int left = (bend - (int)b0 + 15) >> 4;
         v4u ca[RD];
 #pragma unroll
         for (int dd = 0; dd < RD; dd++) {
-            ca[dd] = __builtin_amdgcn_raw_buffer_load_b128(rs, vo16, code_off(0, 0, dd), SL8_AUX);
+            ca[dd] = __builtin_amdgcn_raw_buffer_load_b128(rs, vo16, dd < left ? sbase + dd * CSTEP : so_oob, SL8_AUX);
             __builtin_amdgcn_sched_barrier(0);
         }
         // only slice 0 is staged ahead of the scan; slice 1 (slot 1, needed by the second pass) travels behind the first pass of the
@@ -1359,25 +1385,31 @@ __global__ __launch_bounds__(1024) void k_pq_scan_sl8(PQScan8Args A, const PQRot
             constexpr int P = decltype(PC)::value;
             // unit 0 of the wave's share is requested behind block JL0 and written behind JW0, unit 1 behind JL1 / JW1
             constexpr int JL0 = 1 < NB ? 1 : 0, JW0 = NB >= 8 ? NB / 2 - 1 : (NB > 2 ? 2 : NB - 1), JL1 = JW0 + 1 < NB ? JW0 + 1 : NB - 1, JW1 = NB - 2 > JL1 ? NB - 2 : NB - 1;
-            const int sl = slice_of(st, P);
-            const int pn = P + 1 < NS ? P + 1 : 0, stn = P + 1 < NS ? st : st + 1;       // the pass after this one (prefetch across the boundary)
+            // this pass's blocks and the next pass's (prefetch across the boundary): offset of block 0, blocks that exist
+            const int cur = sbase + slice_of(st, P) * SLB;
+            const int nxt = P + 1 < NS ? sbase + slice_of(st, P + 1) * SLB : sbase + NB * CSTEP + slice_of(st + 1, 0) * SLB;
+            // the four waves of a SIMD (w, w + 4, w + 8, w + 12) take turns at the top issue priority, SL8_PR blocks each: the arbiter
+            // favours the oldest wave otherwise, and here every wave waits for the slowest once per sub-tile.  The wave's phase is
+            // found once per pass; a block picks its s_setprio immediate by that phase alone
+            // (left and phase are made opaque per block: known ahead, their sixteen comparisons are hoisted out of the pass as lane
+            //  masks — two SGPRs each, spilled to VGPR lanes and tested with three instructions instead of one)
+            int phase = (P * (NB / SL8_PR) + st + (w >> 2)) & 3;
             if (P == 1 && st == 0) { while ((int)(lds_rd32_volatile(cntB_a) - 16u) < 0) __builtin_amdgcn_s_sleep(1); }
             if (P == 2) { while ((int)(lds_rd32_volatile(cntS_a) - (uint32_t)(16 * (st + 1))) < 0) __builtin_amdgcn_s_sleep(1); }
 #pragma unroll
             for (int j = 0; j < NB; j++) {
-                const int b = tb0 + 16 * (st * NB + j) + w;
                 if (P == 2 && w == 0 && st == nsub - 1) {
                     if (j == 0 && dstate == 0) { items_of.draw(lane); dstate = 1; }
                     if (j == NB / 2 && dstate == 1) { i1 = items_of.resolve(lane); pre = load_records<G>(items, i1, lane); dstate = 2; }
                 }
-                // the four waves of a SIMD (w, w + 4, w + 8, w + 12) take turns at the top issue priority, SL8_PR blocks each: the arbiter
-                // favours the oldest wave otherwise, and here every wave waits for the slowest once per sub-tile
-                if (j % SL8_PR == 0) {
-                    switch ((j / SL8_PR + P * (NB / SL8_PR) + st + (w >> 2)) & 3) {
-                        case 0: __builtin_amdgcn_s_setprio(3); break;
-                        case 1: __builtin_amdgcn_s_setprio(2); break;
-                        case 2: __builtin_amdgcn_s_setprio(1); break;
-                        default: __builtin_amdgcn_s_setprio(0); break;
+                asm volatile("" : "+s"(left), "+s"(phase));
+                if (j % SL8_PR == 0) {       // priority 3 - ((j / SL8_PR + phase) & 3)
+                    const int jr = (j / SL8_PR) & 3;
+                    switch (jr) {
+                        case 0: SL8_SETPRIO_ROT(phase, 3, 2, 1, 0); break;
+                        case 1: SL8_SETPRIO_ROT(phase, 2, 1, 0, 3); break;
+                        case 2: SL8_SETPRIO_ROT(phase, 1, 0, 3, 2); break;
+                        default: SL8_SETPRIO_ROT(phase, 0, 3, 2, 1); break;
                     }
                 }
                 uint32_t gv[16];
@@ -1385,12 +1417,13 @@ __global__ __launch_bounds__(1024) void k_pq_scan_sl8(PQScan8Args A, const PQRot
                     const uint32_t cw[4] = {ca[(P * NB + j) % RD].x, ca[(P * NB + j) % RD].y, ca[(P * NB + j) % RD].z, ca[(P * NB + j) % RD].w};
 #pragma unroll
                     for (int s2 = 0; s2 < 16; s2++)
-                        gv[s2] = __builtin_amdgcn_perm(cw[s2 >> 2], P == 1 ? Rb[s2 / 3] : Ra[s2 / 3], 0x0c030000u | ((uint32_t)(4 + (s2 & 3)) << 8) | (uint32_t)(s2 % 3));
+                        gv[s2] = __builtin_amdgcn_perm(cw[s2 >> 2], Ra[s2 / 3], (P == 1 ? 0x0c030000u : 0x0c0c0000u) | ((uint32_t)(4 + (s2 & 3)) << 8) | (uint32_t)(s2 % 3));
                 }
                 __builtin_amdgcn_sched_barrier(0);
-                ca[(P * NB + j) % RD] = __builtin_amdgcn_raw_buffer_load_b128(rs, vo16, j + RD < NB ? code_off(st, P, j + RD) : code_off(stn, pn, j + RD - NB), SL8_AUX);
+                ca[(P * NB + j) % RD] = __builtin_amdgcn_raw_buffer_load_b128(rs, vo16, j + RD < NB ? (j + RD < left ? cur + (j + RD) * CSTEP : so_oob)
+                                                                                                      : (j + RD - NB < (P + 1 < NS ? left : left - NB) ? nxt + (j + RD - NB) * CSTEP : so_oob), SL8_AUX);
                 __builtin_amdgcn_sched_barrier(0);
-                if (b < bend) {          // wave-uniform: inside the tile and the list (the prefetch slot has been refilled either way)
+                if (j < left) {          // wave-uniform: inside the tile and the list (the prefetch slot has been refilled either way)
                     v4i C = {0, 0, 0, 0};
                     if (P > 0) {
 #pragma unroll
@@ -1429,7 +1462,7 @@ __global__ __launch_bounds__(1024) void k_pq_scan_sl8(PQScan8Args A, const PQRot
                     }
                     else if (__builtin_amdgcn_ballot_w64((C[0] & C[1] & C[2] & C[3]) >= 0)) {
                         // C[r] = cinit + sum over all M sub-quantisers of (u8 - 128) for vector 16 (n >> 3) + 4 g + r of block b and query n & 7
-                        int b5 = b << 5;
+                        int b5 = (bsub + 16 * j) << 5;
                         asm volatile("" : "+s"(b5));      // opaque: the positions of all NB x 4 rows would otherwise be computed ahead of the pass loop and spilled
                         // (rolled: this rare path is instantiated once per unrolled block of the last pass — unrolled four ways it was two
                         //  thirds of the kernel's code, and the scan loop has to stay inside the instruction cache)
@@ -1476,11 +1509,17 @@ __global__ __launch_bounds__(1024) void k_pq_scan_sl8(PQScan8Args A, const PQRot
             pass(std::integral_constant<int, 0>{}, st);
             pass(std::integral_constant<int, 1>{}, st);
             pass(std::integral_constant<int, 2>{}, st);
+            sbase += NB * CSTEP; bsub += 16 * NB; left -= NB;
         }
         __builtin_amdgcn_s_setprio(0);
         // ---- item epilogue: the wave's 4 G run descriptors (lane = 4 record + slot = its own query column, g = 0, vector half 0), then
         // wave 0 parks the next item's records
-        if (lane < 4 * G) seg_desc[(((size_t)item * G + (size_t)(lane >> 2)) * 16 + w) * 4 + (lane & 3)] = run_descriptor(mylog_i, qstart, lcur, log_cap);
+        // (the lane is made opaque: the lane's part of the descriptor's 64-bit address would otherwise be held — spilled — through the scan)
+        int le = lane;
+        asm volatile("" : "+v"(le));
+        if (le < 4 * G)      // (lane < 8: its query column qn is the lane itself, so this is mylog_i — found again, not kept)
+            seg_desc[(((size_t)item * G + (size_t)(le >> 2)) * 16 + w) * 4 + (le & 3)] =
+                run_descriptor(((size_t)blockIdx.x * 16 + (size_t)w) * (4 * G) + (size_t)(le & 7), qstart, lcur, log_cap);
         if (w == 0) {
             if (dstate == 0) { items_of.draw(lane); dstate = 1; }     // empty items
             if (dstate == 1) { i1 = items_of.resolve(lane); pre = load_records<G>(items, i1, lane); }
@@ -1631,6 +1670,9 @@ int launch_pq_scan_rot(const PQScanArgs& a, const uint8_t* lut8t, const void* qp
                        int qitems_tmax, hipStream_t st, int q8, PQTileSet tiles) {
     if (!pq_rot_family(a.CB) || !item_ws || log_cap <= 0 || !pq_rot_applies(a.M) || a.M != a.Mpad || max_items <= 0 || max_items > 0x7fffff00) return -1;
     if (a.CB == PQ_SLICED && (!tau_key || !pq_sliced_applies(a.M))) return -1;      // the sliced layout has the filtered 8-query scan only
+    // k_pq_scan_sl8 reaches the batch's tables through one buffer descriptor: 32-bit offsets, at most 4 GiB = 174 762 queries at M = 96
+    // (DESIGN.md §5); the caller reports a larger batch as unsupported
+    if (a.CB == PQ_SLICED && q8 && (a.nq <= 0 || a.nq * 256 * a.M > 0xffffffffll)) return -1;
     PQScan8Args A;
     A.b = a; A.lut8 = lut8t; A.qp = (const PQQParam*)qparam;
     A.pairs_sorted = pairs_sorted; A.pair_off = pair_off; A.group_off = group_off; A.total_groups = total_groups;
