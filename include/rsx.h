@@ -212,7 +212,8 @@ int rsx_merge_packed(int nshards, int64_t nq, int k, int metric, const int64_t* 
 
 /* Integer properties: "ntotal", "nlist", "d", "is_trained", "nprobe", "M", "nbits", "kind",
  * "metric", "storage_dtype", "code_size", "device", "max_k", "pq_layout" (IVFPQ: 1 = rotated code layout), "nshards"
- * (0 = single-device handle), "hbm_bytes".
+ * (0 = single-device handle), "hbm_bytes", "explicit_ids" (1 = a Flat handle that stores caller ids, or any handle one of whose
+ * rsx_add calls since the last rsx_reset carried ids).
  * (index.ntotal / index.is_trained — ivf_flat.py:171; ivf_pq.py:175) */
 int rsx_get(rsx_index_t* h, const char* key, int64_t* out);
 
@@ -275,6 +276,27 @@ int rsx_search_sel(rsx_index_t* h, int64_t nq, const void* q, int dtype, int k, 
  * threshold pre-pass: *tau_dev = NULL, *ntau = 0 whenever sel is not NULL. */
 int rsx_search_prepass_sel(rsx_index_t* h, int64_t nq, const void* q, int dtype, int k, const rsx_selector_t* sel,
                            int nprobe_override, float* D, int64_t* I, uint64_t** tau_dev, int64_t* ntau);
+
+/* ---- exact re-ranking (FAISS IndexRefineFlat) -------------------------------------- */
+
+/* IndexFlat::compute_distance_subset followed by IndexRefine::search's re-order: re-score the kc candidate labels of every query
+ * exactly against the rows a Flat handle stores and keep the best k.  The reference holds the same idea as dead code
+ * (get_knn_scores re-scores retrieved ids from the raw embeddings, src/indicies/ivf_pq.py:119-123); rsx.IndexRefineFlat puts it
+ * behind a compressed index: search the base for k * k_factor candidates, refine, keep k.
+ *   flat     a Flat handle of sequential ids: a label is the position of a stored row (fp16 or widened fp32 storage alike);
+ *   q        [nq, d] dtype;  labels  int64 [nq, kc];  D float32 [nq, k];  I int64 [nq, k];  1 <= k <= kc <= 4096.
+ * Score: fp64 accumulation of the exact products, rounded once to fp32 (what rsx_search on the Flat handle returns for that row);
+ * inner product: the score, best first; L2: the squared distance, ascending; equal scores by label ascending.  Labels < 0 (the
+ * padding of a base search) are skipped; a label that occurs twice is scored twice and may be returned twice, next to itself (as
+ * FAISS's compute_distance_subset + reorder_2_heaps would); slots that cannot be filled get I = -1 and D = -inf (IP) / +inf (L2).
+ * A label >= ntotal is never dereferenced: it is skipped, the call returns RSX_ERR_INVALID once its work has finished, and D / I are
+ * unspecified.  q, labels and D / I follow rsx_search's host / device rule, each on its own (D and I on the same side).  One
+ * kernel launch per "query_batch" queries (k_refine: one workgroup per query) on the handle's stream; the call may directly follow an
+ * rsx_search on another handle of the same device that produced `labels` (rsx_search returns with its results complete).
+ * Refused with the handle untouched: a handle that is not Flat (RSX_ERR_INVALID), a Flat handle with explicit ids or a sharded one,
+ * kc > 4096 (RSX_ERR_UNSUPPORTED), k < 1 or k > kc (RSX_ERR_INVALID).  rsx_get_timing: "refine_calls", "refine_candidates" (nq * kc,
+ * summed) and, with "profile" = 1, "refine_ms" (HIP events around the call's launches). */
+int rsx_refine(rsx_index_t* flat, int64_t nq, const void* q, int dtype, int kc, const int64_t* labels, int k, float* D, int64_t* I);
 
 /* ---- removal (FAISS Index::remove_ids) --------------------------------------------- */
 

@@ -10,6 +10,7 @@
 // ivf_pq.py:230): the per-query heap / reservoir top-k, quantizer->search top-nprobe, and
 // heap_reorder; and src/search.py:362-367 (multi-shard merge).
 #include "rsx_internal.h"
+#include "k_rescore.h"
 
 namespace rsx {
 
@@ -1360,12 +1361,6 @@ void launch_group_pairs(const int32_t* probe_list, int64_t npairs, int nlist, in
 // once to fp32 — the oracle's canonical arithmetic), sort by (score desc, id asc) and emit k.
 // IVF-PQ scores are already canonical fp32 (sequential LUT sum) and are only re-ordered.
 // ---------------------------------------------------------------------------------------
-__device__ inline double wave_sum_f64(double v) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
-    return v;
-}
-
 // Exact IVF-PQ score of one stored vector: sum over m (ascending, fp32) of the table entry of its code.
 // The codes of a vector sit in CB-byte granules (one per 64*CB-byte slab row block); one granule is
 // fetched ahead so the dependent code -> codeword loads of different m overlap.
@@ -1629,98 +1624,18 @@ __global__ __launch_bounds__(1024) void k_finalize(FinalizeArgs a) {
         }
         __syncthreads();
     }
-    auto rescore_rows = [&](int c_lo, int c_hi) {
-        // one wave per candidate, lanes over the dimensions; FOUR candidates per wave in flight (round 4: at the reference's n_docs =
-        // 1000 a query re-scores 2048 rows of 1.5 KB that sit anywhere in HBM — one row at a time per wave was 3.2 ms per 1024 queries)
-        const float* qv = a.Q32 + q * a.ldq;
-        for (int c0 = c_lo + 4 * wv; c0 < c_hi; c0 += 4 * nwv) {
-            int64_t rows[4]; double acc[4];
-#pragma unroll
-            for (int u = 0; u < 4; u++) { rows[u] = c0 + u < c_hi ? srow[c0 + u] : -1; acc[u] = 0.0; }   // wave-uniform (LDS values)
-            if (a.x_f16 && (a.ldq & 7) == 0 && a.ldq >= a.ld) {
-                // fp16 rows: 16 bytes (8 values) per lane and load — a 1536-byte row is 1.5 wave loads instead of 12 two-byte ones (the
-                // rows' zero padding up to ld contributes exact zeros; fp64 sums of products of fp16-valued numbers do not depend on the order)
-                for (int c8 = lane; c8 < (a.ld >> 3); c8 += 64) {
-                    const float4 qa = *reinterpret_cast<const float4*>(qv + 8 * c8), qb = *reinterpret_cast<const float4*>(qv + 8 * c8 + 4);
-                    const float qf[8] = {qa.x, qa.y, qa.z, qa.w, qb.x, qb.y, qb.z, qb.w};
-                    uint4 xr[4];
-#pragma unroll
-                    for (int u = 0; u < 4; u++) xr[u] = rows[u] >= 0 ? *reinterpret_cast<const uint4*>((const __half*)a.X + rows[u] * a.ld + 8 * c8) : make_uint4(0u, 0u, 0u, 0u);
-#pragma unroll
-                    for (int u = 0; u < 4; u++) {
-                        const uint32_t wds[4] = {xr[u].x, xr[u].y, xr[u].z, xr[u].w};
-#pragma unroll
-                        for (int e = 0; e < 8; e++) {
-                            const __half hx = __ushort_as_half((unsigned short)((wds[e >> 1] >> (16 * (e & 1))) & 0xffffu));
-                            const double qd = (double)qf[e], xd = (double)__half2float(hx);
-                            if (a.metric == 0) acc[u] += qd * xd; else { const double df = qd - xd; acc[u] += df * df; }
-                        }
-                    }
-                }
-            } else
-            for (int t = lane; t < a.d; t += 64) {
-                const double qd = (double)qv[t];
-                double xd[4];
-#pragma unroll
-                for (int u = 0; u < 4; u++) {
-                    xd[u] = 0.0;
-                    if (rows[u] >= 0) xd[u] = a.x_f16 ? (double)__half2float(((const __half*)a.X)[rows[u] * a.ld + t]) : (double)((const float*)a.X)[rows[u] * a.ld + t];
-                }
-#pragma unroll
-                for (int u = 0; u < 4; u++) { if (a.metric == 0) acc[u] += qd * xd[u]; else { const double df = qd - xd[u]; acc[u] += df * df; } }
-            }
-#pragma unroll
-            for (int u = 0; u < 4; u++) {
-                if (rows[u] < 0) continue;
-                const double sacc = wave_sum_f64(acc[u]);
-                if (lane == 0) {
-                    const float sc = (float)sacc;
-                    sord[c0 + u] = f2ord((a.metric == 0 ? sc : 0.0f - sc) + 0.0f);
-                }
-            }
-        }
-        __syncthreads();
+    // exact re-score of the candidates' storage rows (k_rescore.h; shared with k_refine)
+    auto rescore = [&](int c_lo, int c_hi) {
+        rescore_rows(a.X, a.x_f16, a.ld, a.d, a.metric, a.Q32 + q * a.ldq, a.ldq, INT64_MAX, srow, sord, c_lo, c_hi, lane, wv, nwv);
     };
-    if (a.kind != KIND_IVFPQ) rescore_rows(0, KPv);
+    if (a.kind != KIND_IVFPQ) rescore(0, KPv);
 
     // order by (ord desc, id asc); invalid entries (ord 0, id INT64_MAX) sink to the end.  Up to FIN_RANK_MAX candidates by
-    // counting: a candidate's position is the number of candidates that beat it (every thread walks the same LDS words —
-    // broadcasts — and there are two barriers instead of the 28 of a 128-key bitonic network); larger sets by the network.
+    // counting, larger sets by the bitonic network (k_rescore.h: sort_candidates)
     auto sort_all = [&]() {
-    if (a.rank_sort) {
         uint32_t* sord2 = reinterpret_cast<uint32_t*>(reinterpret_cast<unsigned char*>(fin_buf) + (((size_t)KP * 20 + 15) / 16) * 16);
         int64_t* sid2 = reinterpret_cast<int64_t*>(sord2 + KP + (KP & 1));
-        for (int c = tid; c < KP; c += nt) {
-            const uint32_t oi = sord[c];
-            const int64_t ii = sid[c];
-            int rank = 0;
-            for (int j = 0; j < KP; j++) {
-                const uint32_t oj = sord[j];
-                const int64_t ij = sid[j];
-                rank += ((oj > oi) || (oj == oi && (ij < ii || (ij == ii && j < c)))) ? 1 : 0;
-            }
-            sord2[rank] = oi; sid2[rank] = ii;
-        }
-        __syncthreads();
-        for (int c = tid; c < KP; c += nt) { sord[c] = sord2[c]; sid[c] = sid2[c]; }
-        __syncthreads();
-    } else
-    for (int size = 2; size <= KP; size <<= 1) {
-        for (int stride = size >> 1; stride > 0; stride >>= 1) {
-            for (int t = tid; t < (KP >> 1); t += nt) {
-                int i = ((t & ~(stride - 1)) << 1) | (t & (stride - 1));
-                int j = i + stride;
-                bool desc = ((i & size) == 0);
-                uint32_t oi = sord[i], oj = sord[j];
-                int64_t ii = sid[i], ij = sid[j];
-                bool i_worse = (oi < oj) || (oi == oj && ii > ij);
-                if (i_worse == desc) {
-                    sord[i] = oj; sord[j] = oi; sid[i] = ij; sid[j] = ii;
-                }
-            }
-            __syncthreads();
-        }
-    }
+        sort_candidates(sord, sid, KP, a.rank_sort, sord2, sid2, tid, nt);
     };
     sort_all();
     if (a.kind == KIND_IVFPQ && a.pq_rescore && tid == 0) {
@@ -1790,7 +1705,7 @@ __global__ __launch_bounds__(1024) void k_finalize(FinalizeArgs a) {
         int bad = certify_rows(KPv);
         if (bad && KPv < KP) {
             resolve(KPv, KP, KP);         // slots [KPv, KP) held sinks after the first sort
-            rescore_rows(KPv, KP);
+            rescore(KPv, KP);
             sort_all();
             bad = certify_rows(KP);
         }

@@ -66,7 +66,7 @@ static int search_prepass_common(rsx_index_t* h, int64_t nq, const void* q, int 
 extern "C" {
 
 const char* rsx_last_error(void) { return g_err.c_str(); }
-int rsx_version(void) { return 1003; }     // 1001: filtered search (rsx_selector_*, rsx_search_sel, rsx_search_prepass_sel); 1002: rsx_remove_ids; 1003: rsx_pq_create
+int rsx_version(void) { return 1004; }     // 1001: filtered search (rsx_selector_*, rsx_search_sel, rsx_search_prepass_sel); 1002: rsx_remove_ids; 1003: rsx_pq_create; 1004: rsx_refine
 
 int rsx_device_count(int* n) {
     return guarded([&] {
@@ -194,9 +194,10 @@ int rsx_add(rsx_index_t* h, int64_t n, const void* x, int dtype, const int64_t* 
         if (!h->trained) RSX_THROW(RSX_ERR_NOT_TRAINED, "add before train");
         if (ids) refuse_flat_pq(h, RSX_ERR_UNSUPPORTED, "add with ids (FAISS's IndexFlatCodes has no add_with_ids)");
         if (n <= 0) return;
-        if (is_sharded(h)) { sharded_add(h, n, x, dtype, ids); return; }
+        if (is_sharded(h)) { sharded_add(h, n, x, dtype, ids); if (ids) h->ids_given = true; return; }
         use_device(h);
         add_all(h, n, x, dtype, ids);
+        if (ids) h->ids_given = true;
     });
 }
 int rsx_assign(rsx_index_t* h, int64_t n, const void* x, int dtype, int64_t* labels) {
@@ -241,13 +242,13 @@ int rsx_reset(rsx_index_t* h) {
                 s->ntotal = 0; s->ndropped = 0;
                 if (s->d_len.p) upload_dir(s);
             }
-            h->ntotal = 0; h->sh_next_id = 0;
+            h->ntotal = 0; h->sh_next_id = 0; h->ids_given = false;
             return;
         }
         use_device(h);
         HIPCHECK(hipStreamSynchronize(h->st));
         std::fill(h->h_len.begin(), h->h_len.end(), 0);
-        h->ntotal = 0; h->ndropped = 0;
+        h->ntotal = 0; h->ndropped = 0; h->ids_given = false;
         if (h->d_len.p) upload_dir(h);
     });
 }
@@ -339,6 +340,22 @@ int rsx_search_sel(rsx_index_t* h, int64_t nq, const void* q, int dtype, int k, 
         }
         use_device(h);
         search_impl(h, nq, q, dtype, k, D, I);
+    });
+}
+
+int rsx_refine(rsx_index_t* h, int64_t nq, const void* q, int dtype, int kc, const int64_t* labels, int k, float* D, int64_t* I) {
+    return guarded([&] {
+        if (!h) RSX_THROW(RSX_ERR_INVALID, "null pointer");
+        refuse_while_two_call(h, "refine");
+        if (dtype != RSX_F32 && dtype != RSX_F16) RSX_THROW(RSX_ERR_INVALID, "bad dtype %d", dtype);
+        if (public_kind(h) != RSX_KIND_FLAT) RSX_THROW(RSX_ERR_INVALID, "refine: the handle must be a Flat index (its kind is %d): the labels name stored rows", public_kind(h));
+        if (is_sharded(h)) RSX_THROW(RSX_ERR_UNSUPPORTED, "refine: not available on a sharded handle (the rows are split over the shards)");
+        if (h->custom_ids) RSX_THROW(RSX_ERR_UNSUPPORTED, "refine: not available on a Flat handle with explicit ids (labels are positions, as in FAISS's IndexRefineFlat)");
+        if (nq < 0) RSX_THROW(RSX_ERR_INVALID, "refine: nq = %lld", (long long)nq);
+        if (kc > 4096) RSX_THROW(RSX_ERR_UNSUPPORTED, "refine: kc = %d exceeds this build's maximum of 4096 candidates per query", kc);
+        if (k < 1 || k > kc) RSX_THROW(RSX_ERR_INVALID, "refine: k = %d must lie in [1, kc = %d]", k, kc);
+        use_device(h);
+        refine_impl(h, nq, q, dtype, kc, labels, k, D, I);
     });
 }
 
@@ -472,6 +489,7 @@ int rsx_get(rsx_index_t* h, const char* key, int64_t* out) {
         if (!h || !key || !out) RSX_THROW(RSX_ERR_INVALID, "null pointer");
         std::string s(key);
         if (s == "nshards") { *out = (int64_t)h->shards.size(); return; }
+        if (s == "explicit_ids") { *out = (h->ids_given || (h->kind == KIND_FLAT && h->custom_ids)) ? 1 : 0; return; }
         if (is_sharded(h)) {
             if (s == "ntotal") { *out = h->ntotal; return; }
             if (s == "nprobe") { *out = h->nprobe; return; }

@@ -2,6 +2,7 @@
 // (struct rsx_index = the opaque rsx_index_t of include/rsx.h) and the prototypes of the host functions that cross files.
 //   api_build.hip    HBM layout management, add / train, list import / export, persistence
 //   api_search.hip   the search drivers (search_batch = one internal batch, search_impl = one rsx_search call)
+//   api_refine.hip   rsx_refine: exact re-ranking of candidate labels against a Flat row store (k_refine.hip)
 //   api_sharded.hip  the single-process multi-GPU handle
 //   api_remove.hip   rsx_remove_ids: the removal plan and compaction (k_remove.hip) on a handle and on the shards of one
 //   rsx_api.hip      the extern "C" entry points
@@ -211,6 +212,7 @@ struct rsx_index {
     bool storage_decided = false;
     bool custom_ids = false;  // Flat: ids array only when the caller supplied ids (sharded Flat handle: its adds carried ids; the shards
                               // always store the logical ids)
+    bool ids_given = false;   // any kind: an rsx_add since the last reset carried ids (rsx_get "explicit_ids"; IndexRefineFlat refuses such a base)
     DevBuf data, ids, norms;
     DevBuf codes_plain;               // IVF-PQ, block layouts: row-major copy of the codes for large-K' finalizes, built on demand (api_search.hip)
     uint64_t plain_gen = ~0ull; const void* plain_of = nullptr;
@@ -266,7 +268,7 @@ struct rsx_index {
 
     // workspace
     DevBuf w_q32, w_q16, w_coarse, w_keys1, w_probekeys, w_probelist, w_dis0, w_segstart, w_temp, w_lut, w_lutws, w_pgflags, w_state,
-        w_D, w_I, w_qin, w_pairs, w_flag, w_x, w_partial, w_assign, w_dest, w_idsin, w_misc, w_lut8, w_qparam, w_uncertain, w_fbq, w_fbD, w_fbI, w_cand, w_candcnt, w_itemdesc, w_tau, w_excl, w_state2, w_addcnt, w_addstart, w_qitems, w_tiews, w_stagedir;
+        w_D, w_I, w_qin, w_pairs, w_flag, w_x, w_partial, w_assign, w_dest, w_idsin, w_misc, w_lut8, w_qparam, w_uncertain, w_fbq, w_fbD, w_fbI, w_cand, w_candcnt, w_itemdesc, w_tau, w_excl, w_state2, w_addcnt, w_addstart, w_qitems, w_tiews, w_stagedir, w_rlabels, w_rflag;
     std::vector<int32_t> stage_host;      // IndexPQ staged scan: host image of w_stagedir (the stages' item tables), alive while the copy runs
     std::map<std::string, double> timing;
 
@@ -350,6 +352,7 @@ rsx_index* create_flat_pq(int d, int M, int nbits, int metric, int device);
 void add_all(rsx_index* h, int64_t n, const void* x, int dtype, const int64_t* ids);
 void train_impl(rsx_index* h, int64_t n, const void* x, int dtype);
 void search_impl(rsx_index* h, int64_t nq, const void* q, int dtype, int k, float* D, int64_t* I);
+void refine_impl(rsx_index* h, int64_t nq, const void* q, int dtype, int kc, const int64_t* labels, int k, float* D, int64_t* I);
 void get_list_impl(rsx_index* h, int64_t l, int64_t* n_out, void* codes_out, int64_t* ids_out);
 void add_list_impl(rsx_index* h, int64_t l, int64_t n, const void* codes, int dtype, const int64_t* ids);
 void save_impl(rsx_index* h, const char* path);

@@ -10,6 +10,7 @@ written against `faiss`:
     faiss.IndexIVFFlat(q,d,nlist,METRIC_INNER_PRODUCT) ivf_flat.py:144   rsx.IndexIVFFlat(...)
     faiss.IndexIVFPQ(q,d,nlist,M,nbits,METRIC_IP)      ivf_pq.py:147     rsx.IndexIVFPQ(...)
     faiss.IndexPQ(d,M,nbits,METRIC_IP)    contriever/src/index.py:19     rsx.IndexPQ(...)
+    faiss.IndexRefineFlat(base)           (factory "...,RFlat")          rsx.IndexRefineFlat(base)
     index.train / add / search / nprobe / ntotal / is_trained            same
     faiss.read_index / write_index                                        rsx.read_index / write_index
     StandardGpuResources / GpuClonerOptions / index_cpu_to_gpu / index_gpu_to_cpu
@@ -44,7 +45,7 @@ ABI_SYMBOLS = [
     "rsx_set_param",
     "rsx_get_timing", "rsx_save", "rsx_load", "rsx_synth_vectors", "rsx_synth_queries",
     "rsx_selector_create", "rsx_selector_destroy", "rsx_selector_is_member", "rsx_search_sel", "rsx_search_prepass_sel",
-    "rsx_remove_ids",
+    "rsx_remove_ids", "rsx_refine",
 ]
 
 
@@ -692,6 +693,117 @@ class IndexPQ(Index):
         return out
 
 
+class IndexRefineSearchParameters(SearchParameters):
+    """faiss.IndexRefineSearchParameters(k_factor=1, base_index_params=None): k_factor replaces index.k_factor for the call;
+    base_index_params (SearchParameters / SearchParametersIVF) goes to the base index's search unchanged."""
+
+    def __init__(self, k_factor=1, base_index_params=None):
+        super().__init__(None)
+        self.k_factor = k_factor
+        self.base_index_params = base_index_params
+
+
+def refine_k_base(k, k_factor):
+    """Candidates IndexRefineFlat asks its base index for: FAISS 1.8.0 IndexRefine::search computes idx_t(k * k_factor) after
+    FAISS_THROW_IF_NOT(k_factor >= 1)."""
+    if not k_factor >= 1:
+        raise AssertionError(f"IndexRefine: k_factor must be >= 1 (FAISS: 'Error: k_factor >= 1 failed'), got {k_factor}")
+    return int(int(k) * float(k_factor))
+
+
+def _has_explicit_ids(index):
+    return bool(index._get("explicit_ids"))
+
+
+class IndexRefineFlat:
+    """faiss.IndexRefineFlat(base_index): search the base index for k * k_factor candidates, re-score exactly those against the
+    stored vectors (refine_index, an IndexFlat of the base's metric on the base's device) and keep the best k (rsx_refine).
+    Bases: any unsharded IndexIVFPQ, IndexPQ, IndexIVFFlat or IndexFlat of sequential ids (a refined label is a row of refine_index).
+    As in FAISS's IndexRefine there is no add_with_ids and no remove_ids."""
+
+    def __init__(self, base_index, k_factor=1.0):
+        if not isinstance(base_index, (IndexIVFPQ, IndexPQ, IndexIVFFlat, IndexFlat)):
+            raise TypeError(f"IndexRefineFlat: the base must be an IndexIVFPQ, IndexPQ, IndexIVFFlat or IndexFlat, got {type(base_index).__name__}")
+        if base_index.nshards:
+            raise RuntimeError("IndexRefineFlat: a sharded base index is not supported (the refine store lives on one device)")
+        if _has_explicit_ids(base_index):
+            raise RuntimeError("IndexRefineFlat: the base index holds explicit ids; refined labels are positions of the stored rows")
+        self.base_index = base_index
+        self.refine_index = IndexFlat(base_index.d, base_index.metric_type, device=base_index._get("device"))
+        self.k_factor = float(k_factor)
+
+    @classmethod
+    def _from_parts(cls, base_index, refine_index, k_factor):
+        if base_index.nshards or refine_index.nshards:
+            raise RuntimeError("IndexRefineFlat: sharded parts are not supported")
+        if base_index.ntotal != refine_index.ntotal or base_index.d != refine_index.d:
+            raise RuntimeError(f"IndexRefineFlat: the base holds {base_index.ntotal} x {base_index.d} vectors, the refine store "
+                               f"{refine_index.ntotal} x {refine_index.d}")
+        obj = cls.__new__(cls)
+        obj.base_index, obj.refine_index, obj.k_factor = base_index, refine_index, float(k_factor)
+        return obj
+
+    d = property(lambda self: self.base_index.d)
+    metric_type = property(lambda self: self.base_index.metric_type)
+    ntotal = property(lambda self: self.base_index.ntotal)
+    is_trained = property(lambda self: self.base_index.is_trained)
+    nshards = 0
+
+    def train(self, x):
+        self.base_index.train(x)
+
+    def add(self, x):
+        if _has_explicit_ids(self.base_index):
+            raise RuntimeError("IndexRefineFlat.add: the base index holds explicit ids; refined labels are positions of the stored rows")
+        if self.base_index.ntotal != self.refine_index.ntotal:
+            raise RuntimeError(f"IndexRefineFlat.add: the base holds {self.base_index.ntotal} vectors, the refine store {self.refine_index.ntotal}")
+        self.base_index.add(x)
+        self.refine_index.add(x)
+        assert self.base_index.ntotal == self.refine_index.ntotal, "IndexRefineFlat: the two parts disagree on ntotal after add"
+
+    def reset(self):
+        self.base_index.reset()
+        self.refine_index.reset()
+
+    def add_with_ids(self, x, ids):
+        raise RuntimeError("IndexRefineFlat: add_with_ids not implemented for this type of index (FAISS's IndexRefine has none: "
+                           "refined labels are positions in the refine store)")
+
+    def remove_ids(self, x):
+        raise RuntimeError("IndexRefineFlat: remove_ids not implemented for this type of index (FAISS's IndexRefine has none)")
+
+    def search(self, x, k, *, params=None):
+        """-> (D float32 [n,k], I int64 [n,k]); numpy in -> numpy out, CUDA tensor in -> CUDA tensors out.  The queries are uploaded
+        once and the candidate labels stay on the device between the base search and rsx_refine."""
+        k = int(k)
+        assert k > 0, "k must be positive"
+        k_factor, base_params = self.k_factor, None
+        if params is not None:
+            if not isinstance(params, IndexRefineSearchParameters):
+                raise RuntimeError("IndexRefine params have incorrect type")
+            k_factor, base_params = params.k_factor, params.base_index_params
+        k_base = refine_k_base(k, k_factor)
+        if _is_torch(x) and x.is_cuda:
+            xq = x
+        else:
+            import torch
+            xh = x if _is_torch(x) else np.asarray(x)
+            if not _is_torch(xh) and xh.dtype not in (np.float32, np.float16):
+                xh = xh.astype(np.float32)
+            xq = torch.as_tensor(xh).to(f"cuda:{self.refine_index._get('device')}")
+        _, labels = self.base_index.search(xq, k_base, params=base_params)
+        keep, p, n, dt, _ = _as_matrix(xq, self.d, "search")
+        import torch
+        D = torch.empty((n, k), dtype=torch.float32, device=keep.device)
+        I = torch.empty((n, k), dtype=torch.int64, device=keep.device)
+        _sync_producer(keep, True)
+        _check(lib().rsx_refine(self.refine_index._h, ctypes.c_int64(n), p, dt, k_base, ctypes.c_void_p(labels.data_ptr()), k,
+                                ctypes.c_void_p(D.data_ptr()), ctypes.c_void_p(I.data_ptr())))
+        if xq is x:
+            return D, I
+        return D.cpu().numpy(), I.cpu().numpy()
+
+
 # ------------------------------------------------------------------------------------------
 # persistence
 # ------------------------------------------------------------------------------------------
@@ -721,12 +833,52 @@ def write_index(index, path):
     if os.environ.get("RSX_INDEX_FORMAT", "").lower() == "faiss" and index.nshards == 0:
         from rsx_faiss_io import write_faiss_index
         return write_faiss_index(index, os.fspath(path))
+    if isinstance(index, IndexRefineFlat):
+        return _write_refine(index, os.fspath(path))
     _check(lib().rsx_save(index._h, os.fspath(path).encode()))
 
 
+_REFINE_MAGIC = b"RSXR"
+
+
+def _write_refine(index, path):
+    """The RSXR manifest of an IndexRefineFlat: magic | version u32 | k_factor f64 (the Python attribute, exactly; FAISS's IxRF record
+    keeps a float32) | two length-prefixed (u32) file names relative to the manifest's directory — the RSX1 files of the base and the
+    refine store, written beside it (as the RSXS manifest and its shards)."""
+    import struct
+    names = [os.path.basename(path) + ".base", os.path.basename(path) + ".refine"]
+    here = os.path.dirname(path)
+    _check(lib().rsx_save(index.base_index._h, os.path.join(here, names[0]).encode()))
+    _check(lib().rsx_save(index.refine_index._h, os.path.join(here, names[1]).encode()))
+    with open(path, "wb") as f:
+        f.write(_REFINE_MAGIC + struct.pack("<Id", 1, index.k_factor))
+        for nm in names:
+            b = nm.encode()
+            f.write(struct.pack("<I", len(b)) + b)
+
+
+def _read_refine(path, device):
+    import struct
+    with open(path, "rb") as f:
+        f.read(4)
+        version, k_factor = struct.unpack("<Id", f.read(12))
+        if version != 1:
+            raise RuntimeError(f"{path}: RSXR manifest version {version} is not supported")
+        names = []
+        for _ in range(2):
+            n, = struct.unpack("<I", f.read(4))
+            names.append(f.read(n).decode())
+    parts = []
+    for nm in names:
+        h = ctypes.c_void_p()
+        _check(lib().rsx_load(os.path.join(os.path.dirname(path), nm).encode(), default_device() if device is None else int(device), ctypes.byref(h)))
+        parts.append(_wrap_handle(h))
+    return IndexRefineFlat._from_parts(parts[0], parts[1], k_factor)
+
+
 def read_index(path, device=None, devices=None):
-    """faiss.read_index(path): loads an RSX1 container (RSXS: the manifest of a sharded index, one shard per device), or
-    a FAISS-format file via rsx_faiss_io.
+    """faiss.read_index(path): loads an RSX1 container (RSXS: the manifest of a sharded index, one shard per device; RSXR: the
+    manifest of an IndexRefineFlat, one device only), or a FAISS-format file via rsx_faiss_io.
 
     A multi-device request (devices=[...] / "all", cfg.datastore.index.devices, RSX_DEVICES) on a file written from ONE
     index — RSX1 or FAISS — RE-SHARDS it while loading: every inverted list / row block is cut over the devices as it
@@ -745,6 +897,10 @@ def read_index(path, device=None, devices=None):
         return _wrap_handle(h)
     if device is None and devs:        # a one-entry device list names the device of an ordinary handle
         device = devs[0]
+    if magic in (_REFINE_MAGIC, b"IxRF") and multi:
+        raise RuntimeError(f"{path}: an IndexRefineFlat cannot be loaded onto several devices (no sharded form)")
+    if magic == _REFINE_MAGIC:
+        return _read_refine(path, device)
     if magic != b"RSX1":
         from rsx_faiss_io import read_faiss_index
         return read_faiss_index(path, device=device, devices=devs if multi else None)

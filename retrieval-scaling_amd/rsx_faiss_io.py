@@ -1,4 +1,5 @@
-"""FAISS on-disk index format (.faiss) reader / writer for the index types of the path (Flat, IVF-Flat, IVF-PQ) and IndexPQ.
+"""FAISS on-disk index format (.faiss) reader / writer for the index types of the path (Flat, IVF-Flat, IVF-PQ), IndexPQ and
+IndexRefineFlat.
 
 Reference call sites: faiss.read_index / faiss.write_index in src/indicies/flat.py:39,63,69,
 ivf_flat.py:71,167,170,185, ivf_pq.py:75,171,174,190 — and the released MassiveDS artefacts
@@ -18,6 +19,8 @@ FAISS-produced file is available offline, so byte-compatibility with real FAISS 
                 | encode_signs u8 | polysemous_ht i32      (contriever/src/index.py:19 builds this class; like the other
                 containers restated from upstream knowledge of index_write.cpp and UNVERIFIED against a FAISS-produced file;
                 the legacy "IxPQ" / "IxPo" magics are not read)
+  IndexRefineFlat: "IxRF" | header | <base index> | <refine index: IxFI / IxF2> | k_factor f32      (restated from upstream
+                knowledge of index_write.cpp like the others, UNVERIFIED against a FAISS-produced file)
   inv. lists  : "ilar" | nlist u64 | code_size u64 | "full" + sizes (u64 n + u64[n])
                                                    | "sprs" + (list, size) pairs (u64 n + u64[n])
                 then per non-empty list: codes (size*code_size bytes) followed by ids (i64[size])
@@ -149,7 +152,14 @@ def _read_index(r):
         h.update(kind="PQ", fourcc=cc, M=M, nbits=nbits, codebooks=cen.reshape(M, 1 << nbits, pq_d // M),
                  codes=codes.reshape(-1, M), search_type=r.i32(), encode_signs=bool(r.u8()), polysemous_ht=r.i32())
         return h
-    raise RuntimeError(f"unsupported FAISS index type '{cc}' (supported: IxFI, IxF2, IwFl, IwPQ, IxPq)")
+    if cc == "IxRF":
+        h = _read_header(r)
+        h.update(kind="Refine", fourcc=cc, base_index=_read_index(r), refine_index=_read_index(r))
+        h["k_factor"] = struct.unpack("<f", r.raw(4))[0]
+        if h["refine_index"]["kind"] != "Flat":
+            raise RuntimeError("only IndexRefineFlat files are supported (the refine index must be an IndexFlat)")
+        return h
+    raise RuntimeError(f"unsupported FAISS index type '{cc}' (supported: IxFI, IxF2, IwFl, IwPQ, IxPq, IxRF)")
 
 
 def parse_faiss(path_or_bytes):
@@ -212,6 +222,13 @@ def serialize_faiss(p):
     """Inverse of parse_faiss for the dict layout it returns (only the fields it needs)."""
     out = io.BytesIO()
     kind = p["kind"]
+    if kind == "Refine":
+        out.write(b"IxRF")
+        _w_header(out, p["d"], p["ntotal"], p["is_trained"], p["metric"])
+        out.write(serialize_faiss(p["base_index"]))
+        out.write(serialize_faiss(p["refine_index"]))
+        out.write(struct.pack("<f", p["k_factor"]))
+        return out.getvalue()
     if kind == "Flat":
         _w_flat(out, p["d"], p["metric"], p["vectors"])
         return out.getvalue()
@@ -241,6 +258,10 @@ def serialize_faiss(p):
 # ------------------------------------------------------------------------------------------ rsx bridge
 def index_to_parsed(index):
     """rsx index -> the dict layout above (vectors / codes pulled out of HBM list by list)."""
+    if hasattr(index, "refine_index"):
+        return {"kind": "Refine", "d": index.d, "metric": index.metric_type, "ntotal": index.ntotal, "is_trained": index.is_trained,
+                "base_index": index_to_parsed(index.base_index), "refine_index": index_to_parsed(index.refine_index),
+                "k_factor": float(index.k_factor)}
     kind = {0: "Flat", 1: "IVFFlat", 2: "IVFPQ", 3: "PQ"}[index._get("kind")]
     p = {"kind": kind, "d": index.d, "metric": index.metric_type, "ntotal": index.ntotal,
          "is_trained": index.is_trained}
@@ -269,40 +290,49 @@ def write_faiss_index(index, path):
     """rsx index -> .faiss file, STREAMED: the header blocks first, then one inverted list at a time out of HBM (a 100M x 96-byte
     IVF-PQ index is 10.4 GB; nothing here holds more than one list on the host).  Byte-identical to
     serialize_faiss(index_to_parsed(index))."""
+    with open(path, "wb") as out:
+        _write_faiss_stream(index, out)
+
+
+def _write_faiss_stream(index, out):
+    if hasattr(index, "refine_index"):      # IndexRefineFlat: the two nested records as they are written standalone
+        out.write(b"IxRF")
+        _w_header(out, index.d, index.ntotal, index.is_trained, index.metric_type)
+        _write_faiss_stream(index.base_index, out)
+        _write_faiss_stream(index.refine_index, out)
+        out.write(struct.pack("<f", float(index.k_factor)))
+        return
     kind = {0: "Flat", 1: "IVFFlat", 2: "IVFPQ", 3: "PQ"}[index._get("kind")]
     if kind in ("Flat", "PQ"):      # (an IndexPQ of 100M x 96 bytes is 9.6 GB of codes: one list, exported in one piece)
-        data = serialize_faiss(index_to_parsed(index))
-        with open(path, "wb") as f:
-            f.write(data)
+        out.write(serialize_faiss(index_to_parsed(index)))
         return
     d, nlist = index.d, index.nlist
     sizes = np.asarray(index.list_sizes(), dtype=np.uint64)
-    with open(path, "wb") as out:
-        out.write(b"IwFl" if kind == "IVFFlat" else b"IwPQ")
-        _w_header(out, d, index.ntotal, index.is_trained, index.metric_type)
-        out.write(struct.pack("<QQ", nlist, index.nprobe))
-        _w_flat(out, d, METRIC_INNER_PRODUCT, index.get_centroids() if index.is_trained else np.zeros((0, d), np.float32))
-        out.write(struct.pack("<B", 0))
-        _w_vector(out, np.zeros(0, np.int64), np.int64)
-        if kind == "IVFPQ":
-            out.write(struct.pack("<BQ", 1, index.M))
-            out.write(struct.pack("<QQQ", d, index.M, 8))
-            _w_vector(out, index.get_codebooks() if index.is_trained else np.zeros((index.M, 256, d // index.M), np.float32), np.float32)
-        code_size = index.M if kind == "IVFPQ" else d * 4
-        out.write(b"ilar")
-        out.write(struct.pack("<QQ", nlist, code_size))
-        if int((sizes > 0).sum()) > nlist // 2:
-            out.write(b"full")
-            _w_vector(out, sizes, np.uint64)
-        else:
-            out.write(b"sprs")
-            nz = np.nonzero(sizes)[0]
-            _w_vector(out, np.stack([nz.astype(np.uint64), sizes[nz]], 1).reshape(-1), np.uint64)
-        for l in np.nonzero(sizes)[0]:
-            c, i = index.get_list(int(l))
-            c = np.ascontiguousarray(c, dtype=np.uint8 if kind == "IVFPQ" else np.float32)
-            out.write(c.view(np.uint8).tobytes())
-            out.write(np.ascontiguousarray(i, dtype=np.int64).tobytes())
+    out.write(b"IwFl" if kind == "IVFFlat" else b"IwPQ")
+    _w_header(out, d, index.ntotal, index.is_trained, index.metric_type)
+    out.write(struct.pack("<QQ", nlist, index.nprobe))
+    _w_flat(out, d, METRIC_INNER_PRODUCT, index.get_centroids() if index.is_trained else np.zeros((0, d), np.float32))
+    out.write(struct.pack("<B", 0))
+    _w_vector(out, np.zeros(0, np.int64), np.int64)
+    if kind == "IVFPQ":
+        out.write(struct.pack("<BQ", 1, index.M))
+        out.write(struct.pack("<QQQ", d, index.M, 8))
+        _w_vector(out, index.get_codebooks() if index.is_trained else np.zeros((index.M, 256, d // index.M), np.float32), np.float32)
+    code_size = index.M if kind == "IVFPQ" else d * 4
+    out.write(b"ilar")
+    out.write(struct.pack("<QQ", nlist, code_size))
+    if int((sizes > 0).sum()) > nlist // 2:
+        out.write(b"full")
+        _w_vector(out, sizes, np.uint64)
+    else:
+        out.write(b"sprs")
+        nz = np.nonzero(sizes)[0]
+        _w_vector(out, np.stack([nz.astype(np.uint64), sizes[nz]], 1).reshape(-1), np.uint64)
+    for l in np.nonzero(sizes)[0]:
+        c, i = index.get_list(int(l))
+        c = np.ascontiguousarray(c, dtype=np.uint8 if kind == "IVFPQ" else np.float32)
+        out.write(c.view(np.uint8).tobytes())
+        out.write(np.ascontiguousarray(i, dtype=np.int64).tobytes())
 
 
 def index_from_parsed(p, device=None, devices=None):
@@ -312,6 +342,12 @@ def index_from_parsed(p, device=None, devices=None):
     kind, d, metric = p["kind"], p["d"], p["metric"]
     if metric not in (METRIC_INNER_PRODUCT, METRIC_L2):
         raise RuntimeError(f"unsupported metric {metric}")
+    if kind == "Refine":
+        if devices is not None and len(devices) > 1:
+            raise RuntimeError("an IndexRefineFlat file cannot be loaded onto several devices (no sharded form)")
+        base = index_from_parsed(p["base_index"], device=device)
+        refine = index_from_parsed(p["refine_index"], device=base._get("device"))
+        return rsx.IndexRefineFlat._from_parts(base, refine, p["k_factor"])
     if kind == "Flat":
         ix = rsx.IndexFlat(d, metric, device=device, devices=devices)
         if len(p["vectors"]):

@@ -66,7 +66,11 @@ class Indexer(object):
                                             sample_train_size=self.args.sample_train_size, prev_index_path=None,
                                             ncentroids=self.args.ncentroids, probe=self.args.probe, **common)
         elif self.index_type == "IVFPQ":
-            self.datastore = IVFPQIndexer(trained_index_path=trained_index_path,
+            # optional key, IVF-PQ only (absent -> the plain index, unchanged): cfg.datastore.index.refine_k_factor = f wraps the index
+            # in IndexRefineFlat — search the codes for k * f candidates, re-score them exactly from stored rows, keep k
+            refine = self._opt("refine_k_factor", None)
+            extra = {} if refine is None else {"refine_k_factor": float(refine)}
+            self.datastore = IVFPQIndexer(trained_index_path=trained_index_path, **extra,
                                           sample_train_size=self.args.sample_train_size, prev_index_path=None,
                                           ncentroids=self.args.ncentroids, probe=self.args.probe,
                                           n_subquantizers=self.args.n_subquantizers, code_size=self.args.n_bits,

@@ -37,7 +37,7 @@ class IVFFlatIndexer(BackendBase):
             print("Loading index...")
             self.index = engine().read_index(index_path)
             self.index_id_to_db_id = self.load_index_id_to_db_id()
-            self.index.nprobe = self.probe
+            self._set_probe(self.index)
         else:
             self.index_id_to_db_id = []
             if not os.path.exists(self.trained_index_path):
@@ -55,6 +55,13 @@ class IVFFlatIndexer(BackendBase):
     def _new_index(self):
         quantizer = engine().IndexFlatIP(self.dimension)
         return engine().IndexIVFFlat(quantizer, self.dimension, self.ncentroids, engine().METRIC_INNER_PRODUCT)
+
+    # the index the vectors are added to, made from the trained one, and where its nprobe lives (overridden by IVFPQIndexer)
+    def _for_adding(self, trained_index):
+        return trained_index
+
+    def _set_probe(self, index):
+        index.nprobe = self.probe
 
     # ---- training (reference ivf_flat.py:122-167)
     def _sample_and_train_index(self):
@@ -81,9 +88,10 @@ class IVFFlatIndexer(BackendBase):
     def _add_keys(self, index_path, trained_index_path):
         index = engine().read_index(trained_index_path)
         assert index.is_trained and index.ntotal == 0
+        index = self._for_adding(index)
         start_time = time.time()
         self._add_shards(index)
-        index.nprobe = self.probe
+        self._set_probe(index)
         engine().write_index(index, index_path)
         self._save_meta()
         print(f"Adding took {time.time() - start_time} s")

@@ -3,8 +3,10 @@
   C2  Flat  N x 768 (default 10M), batch 1024, k 10  — MFMA-bound:  TFLOP/s = 2*nq*N*d / t
   C3  IVF-Flat N x 768 (default 20M: 100M fp16 = 153.6 GB needs an exact two-pass reserve),
       nlist 4096, nprobe 32                          — HBM-bound:   GB/s   = scanned rows * 1536 B / t
+  refine  IndexRefineFlat over the headline IVF-PQ index (M 96, nlist 4096, nprobe 32) + the fp16 rows: ms per 1024-query batch at
+      k 10 with k_factor 1 / 4 / 10 beside the base's own search(k_base), refine_ms, recall@10 against the exact Flat ground truth
 Each prints one JSON line; ids/scores of a sample of queries are checked against the CPU oracle.
-usage: bench_configs.py [flat|ivfflat] [--n N] [--steps K]
+usage: bench_configs.py [flat|ivfflat|refine] [--n N] [--steps K]
 """
 import argparse, json, os, sys, time
 import numpy as np
@@ -220,9 +222,74 @@ def measure_ivfpq(n=100_000_000, M=16, nlist=8192, nprobe=512, ks=(10, 1000), st
     return res
 
 
+def measure_refine(n=100_000_000, M=96, nlist=4096, nprobe=32, k=10, k_factors=(1, 4, 10), steps=5, batch=1024, mixture="standard"):
+    """IndexRefineFlat(IndexIVFPQ) on n synthetic vectors, codes AND fp16 rows resident (100M: 9.6 GB + 153.6 GB).  Per k_factor: ms per
+    batch of the refined search, of the base's own search(k_base) on the same index, the refine stage's HIP-event time, and recall@10
+    of both against the exact ground truth (the refine store's own Flat search).  mixture: "standard" (the headline's) or
+    "informative" (n / 8 centres, sigma 0.1: neighbours a 96-byte code can resolve — bench.py's recall_informative)."""
+    import ctypes
+    import torch, rsx
+    dev = torch.device("cuda", 0)
+    nq = batch
+    nc, sig, sigq = (max(1, n // 8), 0.1, 0.02) if mixture == "informative" else (NC, 0.5, 0.1)
+    t0 = time.time()
+    base = rsx.IndexIVFPQ(None, D, nlist, M, 8, rsx.METRIC_INNER_PRODUCT)
+    nt = min(n, 256 * nlist)
+    xt = torch.empty((nt, D), dtype=torch.float16, device=dev)
+    stride = max(1, n // nt)
+    for b in range(0, nt, 4096):
+        nb = min(4096, nt - b)
+        rsx.synth_vectors(D, nc, SC, SX, sig, (b * stride) % max(1, n - nb), nb, out=xt[b:b + nb])
+    base.train(xt); del xt
+    base.nprobe = nprobe
+    ix = rsx.IndexRefineFlat(base)
+    # the row store is sized once: growing a 153.6 GB allocation would need two copies of it
+    rsx._check(rsx.lib().rsx_reserve_lists(ix.refine_index._h, np.array([n], dtype=np.int64).ctypes.data_as(ctypes.c_void_p)))
+    buf = torch.empty((1_000_000, D), dtype=torch.float16, device=dev)
+    for c0 in range(0, n, buf.shape[0]):
+        nb = min(buf.shape[0], n - c0)
+        rsx.synth_vectors(D, nc, SC, SX, sig, c0, nb, out=buf[:nb]); ix.add(buf[:nb])
+    del buf
+    torch.cuda.synchronize()
+    build_s = time.time() - t0
+    Q = torch.empty((nq * (steps + 2), D), dtype=torch.float16, device=dev)
+    rsx.synth_queries(D, nc, SC, SX, sig, n, SQ, sigq, 0, Q.shape[0], out=Q)
+    Qgt = Q[(steps + 1) * nq:]
+    gt = ix.refine_index.search(Qgt, k)[1].cpu().numpy()
+    recall = lambda I: round(float(np.mean([len(set(x.tolist()) & set(y.tolist())) / k for x, y in zip(I.cpu().numpy(), gt)])), 4)
+
+    def timed(fn):
+        fn(Q[:nq])
+        torch.cuda.synchronize(); t0 = time.perf_counter()
+        for s in range(1, steps + 1):
+            fn(Q[s * nq:(s + 1) * nq])
+        torch.cuda.synchronize()
+        return round((time.perf_counter() - t0) / steps * 1e3, 3)
+
+    res = {"config": f"refine {n}x{D} {mixture} mixture, IVF-PQ M={M} nlist={nlist} nprobe={nprobe} + fp16 rows, batch={nq} k={k}",
+           "build_s": round(build_s, 1), "hbm_bytes": {"codes": int(base._get("hbm_bytes")), "rows": int(ix.refine_index._get("hbm_bytes"))},
+           "refine_storage_dtype": ix.refine_index.storage_dtype, "base_recall_at_10": recall(base.search(Qgt, k)[1]), "by_k_factor": {}}
+    for f in k_factors:
+        ix.k_factor = f
+        kb = rsx.refine_k_base(k, f)
+        r = {"k_base": kb, "base_search_k_base_ms": timed(lambda q: base.search(q, kb)), "refined_search_ms": timed(lambda q: ix.search(q, k))}
+        ix.refine_index.set_param("profile", 1)
+        for s in range(1, steps + 1):
+            ix.search(Q[s * nq:(s + 1) * nq], k)
+        r["refine_ms"] = round(ix.refine_index.get_timing("refine_ms") / steps, 4)
+        r["refine_candidates_per_batch"] = ix.refine_index.get_timing("refine_candidates") / steps
+        ix.refine_index.set_param("profile", 0)
+        r["gathered_MB_per_batch"] = round(nq * kb * D * 2 / 1e6, 1)
+        r["recall_at_10"] = recall(ix.search(Qgt, k)[1])
+        res["by_k_factor"][f"k_factor{f}"] = r
+    del ix, base, Q
+    torch.cuda.synchronize()
+    return res
+
+
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("which", choices=["flat", "ivfflat", "latency", "ivfpq_ref", "largek"])
+    ap.add_argument("which", choices=["flat", "ivfflat", "latency", "ivfpq_ref", "largek", "refine"])
     ap.add_argument("--n", type=int, default=0)
     ap.add_argument("--steps", type=int, default=5)
     ap.add_argument("--batch", type=int, default=1024)
@@ -234,6 +301,7 @@ def main():
     ap.add_argument("--k", type=int, default=10, help="flat / ivfflat: results per query")
     ap.add_argument("--metric", default="ip", choices=["ip", "l2"])
     ap.add_argument("--m", type=int, default=0, help="largek: sub-quantisers of the index (default 96)")
+    ap.add_argument("--mixture", default="standard", choices=["standard", "informative"], help="refine: the data distribution")
     a = ap.parse_args()
     params = [(kv.split("=")[0], int(kv.split("=")[1])) for kv in a.param]
     if a.which == "latency":
@@ -241,6 +309,9 @@ def main():
     if a.which == "ivfpq_ref":
         ks = tuple(int(t) for t in a.ks.split(",")) if a.ks else (10, 1000)
         print(json.dumps(measure_ivfpq(a.n or 100_000_000, ks=ks, steps=a.steps, check=a.check, params=params)), flush=True)
+        return
+    if a.which == "refine":
+        print(json.dumps(measure_refine(a.n or 100_000_000, a.m or 96, a.nlist, a.nprobe, k=a.k, steps=a.steps, mixture=a.mixture)), flush=True)
         return
     if a.which == "largek":      # the headline index (M = 96, nlist 4096, nprobe 32) at the reference's n_docs
         ks = tuple(int(t) for t in a.ks.split(",")) if a.ks else (10, 100, 1000, 2000)
