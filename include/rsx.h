@@ -224,7 +224,8 @@ int rsx_get(rsx_index_t* h, const char* key, int64_t* out);
  * 0 = the exact scan of its metric), "pq_fast_kp" (candidates kept by the
  * fast scan, 0 = auto), "pq_filter" (fast scan: 1 = candidates filtered inside the scan kernel [default], 0 = full
  * score buffer), "pq_pre_rows" (filtered fast scan: vectors of each query's closest list scored by the threshold
- * pre-pass, default 2048, 0 = one scan tile), "ivf_filter" (IVF-Flat: candidates filtered inside the list scan: 1 = when
+ * pre-pass, default 2048, 0 = one scan tile), "pq_tau_anchor" (filtered fast scan, four-query pre-pass: 1 = the threshold is anchored on the
+ * exact scores of the sample's k best rows [default], 0 = the approximate k-th best minus 2 eps alone; read per search), "ivf_filter" (IVF-Flat: candidates filtered inside the list scan: 1 = when
  * the score rows of the batch would exceed ~2 GB [default], 2 = always, 0 = never = full score rows), "pq_prepass_fused" (filtered fast scan: 1 = threshold pre-pass in one launch [default], 0 = grouping +
  * scan + selection launches), "lut_tiled" (IVFPQ fast scan, dsub = 8: 1 = 8-bit tables built by
  * codebook-slice tiles shared by 32 queries [default], 0 = one workgroup per query), "flat_filter" (Flat: 1 = one filtered GEMM launch after the first chunk [default], 0 = score buffer

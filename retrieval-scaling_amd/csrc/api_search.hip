@@ -635,6 +635,11 @@ static void build_pq_tables(rsx_index* h, const BatchPlan& P, void* lut_ws, cons
 }
 // the fast scan's tiles and its threshold pre-pass: vectors per lane (vpl, tile_rows = 1024 vpl), the pre-pass sample and its form
 struct PqGeometry { int vpl, tile_rows, pre_vpl, pre_rows; bool fused_pre, pre4; };
+// the four-query pre-pass anchors its threshold on exact scores (k_pq_prepass4): inner-product IVF-PQ searches; IndexPQ's
+// staged thresholds keep a_k - 2 eps (its L2 form has negated tables, and its stages tighten the threshold themselves)
+static bool pq_anchor_applies(const rsx_index* h, const BatchPlan& P) {
+    return h->pq_tau_anchor != 0 && !P.staged && h->metric == RSX_METRIC_INNER_PRODUCT && h->M == h->Mpad;
+}
 static PqGeometry pq_geometry(const rsx_index* h, const BatchPlan& P, bool filtered) {
     const int nlist = h->nlist, k = P.k; const int64_t pairs = P.nq * P.nprobe;
     PqGeometry g{};
@@ -678,7 +683,10 @@ static PqGeometry pq_geometry(const rsx_index* h, const BatchPlan& P, bool filte
         want_rows = std::min<int64_t>(round_up(want_rows, 64), round_up(std::max<int64_t>(P.maxlen, 64), 64));
         // small k, full batch, rotated layout: the 4-queries-per-workgroup form (k_pq_prepass4) — its sample is what fits the LDS
         // beside the four-query table image (3520 rows at M = 96)
-        g.pre4 = P.rot && h->pq_prepass4 != 0 && P.nq >= 64 && (int64_t)160 * k <= base_rows && pq_prepass4_max_rows(h->Mpad) >= 1024;
+        // (k <= 25 at the default pq_pre_rows; an explicit smaller pq_pre_rows shrinks the sample, not the range of k)
+        g.pre4 = P.rot && h->pq_prepass4 != 0 && P.nq >= 64 && (int64_t)160 * k <= std::max<int64_t>(base_rows, 4096) && pq_prepass4_max_rows(h->Mpad) >= 1024;
+        // (with the exact anchor, pq_tau_anchor, the sample stays what it was: 2048 anchored rows measured the same ms per batch on the
+        // headline as 3520, but on the informative mixture they let more keys through than the parent rule's 3520 — profiles/tau_anchor.md)
         if (g.pre4) want_rows = std::min<int64_t>(want_rows, pq_prepass4_max_rows(h->Mpad));
         g.pre_rows = (int)want_rows;
         g.fused_pre = (size_t)g.pre_rows * 2 + (size_t)h->Mpad * 256 + 2048 <= 150 * 1024;
@@ -699,6 +707,7 @@ static bool pq_prepass(rsx_index* h, const BatchPlan& P, BatchResult& R, const P
     pa.nprobe = P.nprobe; pa.Mpad = h->Mpad; pa.pre_rows = g.pre_rows; pa.KP = P.KP; pa.CB = h->CB; pa.k = P.k;
     pa.state = h->w_state.as<uint64_t>(); pa.cand_cnt = h->w_candcnt.as<unsigned long long>();
     h->w_tau.ensure((size_t)nq * 8); pa.tau = h->w_tau.as<uint64_t>();
+    if (pq_anchor_applies(h, P)) { pa.codebooks = h->d_codebooks.as<float>(); pa.dsub = h->dsub; pa.Q32 = h->w_q32.as<float>(); pa.ldq = h->ld; }
     if (P.rot && !P.staged) {       // the sample's own candidates leave from the pre-pass; the scan drops that (query, list, tile 0)
         h->w_excl.ensure((size_t)nq * 2);
         pa.cand = h->w_cand.as<uint64_t>(); pa.cand_cap = R.cand_cap; pa.tile_rows = g.tile_rows; pa.excl = h->w_excl.as<uint16_t>();
@@ -726,7 +735,9 @@ static bool pq_prepass(rsx_index* h, const BatchPlan& P, BatchResult& R, const P
     }
     // large k: the histogram form of the four-query pre-pass (any sample size, several lists; pq_prepass4 = 2 keeps k_pq_prepass)
     const bool pre4big = P.rot && !g.pre4 && h->pq_prepass4 == 1 && nq >= 64 && h->Mpad >= 32 && g.pre_rows <= 32768;
-    if (!(g.pre4 && launch_pq_prepass4(pa, nq, h->st) == 0) && !(pre4big && launch_pq_prepass4_big(pa, nq, h->st) == 0))
+    if (g.pre4 && launch_pq_prepass4(pa, nq, h->st) == 0) {
+        if (h->profile >= 2) { h->timing["pq_prepass4_batches"] += 1; h->timing["pq_anchored_batches"] += pa.codebooks ? 1 : 0; h->timing["pq_pre_rows_used"] = (double)g.pre_rows; }
+    } else if (!(pre4big && launch_pq_prepass4_big(pa, nq, h->st) == 0))
         launch_pq_prepass(pa, nq, h->st);
     R.fused_pre_used = true;
     if (!P.staged && h->tc && h->tc->active && P.allow_fast && std::this_thread::get_id() == h->tc->worker) {

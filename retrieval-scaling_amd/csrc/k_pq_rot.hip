@@ -35,6 +35,7 @@
 #include <cstdlib>
 
 #include "rsx_internal.h"
+#include "k_rescore.h"
 
 namespace rsx {
 
@@ -1720,6 +1721,7 @@ extern "C" int rsx_debug_pp4_trace(uint64_t* out) { return hipMemcpyFromSymbol(o
 // per-query byte table: 0.77 ms per 1024 queries x 16384 rows; this form shares the table image between four queries and uses
 // the scan's conflict-free gathers and the MFMA adder.
 constexpr int PP4_MAXSEG = 8;
+constexpr int PP4_ANCH = 32;     // anchor rows of a slot at most (>= k: larger k keeps a_k - 2 eps alone)
 // SL > 0 (round 6): the SLICED layout (PQ_SLICED) with SL slices: 32-vector blocks, a 1 KiB slice = 16 bytes per lane; the four-query
 // table image keeps 256-byte rows — slices 2 p and 2 p + 1 share plane p (bytes 0-127 / 128-255: bank = m % 32 either way) — and an
 // MFMA tile holds 32 vectors x 4 queries (K groups 0, 1: vector i -> columns 0-3; K groups 2, 3: vector 16 + i -> columns 4-7).
@@ -1827,7 +1829,8 @@ __global__ __launch_bounds__(1024) void k_pq_prepass4(PQPrepassArgs a, int64_t n
     l = __builtin_amdgcn_readfirstlane(l); j0 = __builtin_amdgcn_readfirstlane(j0);
     int nrows = (int)(len < a.pre_rows ? len : a.pre_rows);
     int nblk = __builtin_amdgcn_readfirstlane((nrows + BVEC - 1) / BVEC);
-    const uint8_t* lp = a.codes + ((l >= 0 ? a.list_base[l] : 0) / BVEC) * (int64_t)(BVEC * M);
+    const int64_t lrow0 = l >= 0 ? a.list_base[l] : 0;       // the list's first storage row
+    const uint8_t* lp = a.codes + (lrow0 / BVEC) * (int64_t)(BVEC * M);
     uint16_t* mysum = sums + (size_t)grp * a.pre_rows;
     int nseg = 1;
     if (BIG) {
@@ -2029,6 +2032,96 @@ __global__ __launch_bounds__(1024) void k_pq_prepass4(PQPrepassArgs a, int64_t n
         const int dlo = cs[2];
         if (dhi >= 0 && dlo >= 0) kth = (dhi << 8) | dlo;
     }
+    // ---- exact anchor: the sample's rows with sum >= kth — at least k distinct vectors — in position order, at most
+    // PP4_ANCH of them; their canonical scores (dis0 + the table entries by the builder's chain, added in m order: k_finalize's value, the
+    // one eps is defined against); s_k = the k-th largest of those scores is a lower bound of the query's exact k-th best score, so a
+    // vector with a(v) + eps < s_k cannot reach the top k: tau' = s_k - eps, one eps instead of the two of a_k - 2 eps.  The histogram
+    // and the table image are dead here: the row lists live in the slot's histogram, code bytes and entries in its quarter of the image.
+    float s_k = 0.0f; bool anchored = false;
+    if constexpr (!BIG) {
+    if (a.codebooks) {
+        constexpr int es = M + 1, nrun = M / 16;
+        static_assert(PP4_ANCH * nrun <= 256 && PP4_ANCH <= 32 && (size_t)PP4_ANCH * (es * 4 + M) <= (size_t)TAB / 4, "anchor rows: one piece per thread, a quarter of the image per slot");
+        float* ent = reinterpret_cast<float*>(sb + (size_t)grp * (TAB / 4));                  // [PP4_ANCH][M + 1]
+        uint8_t* cbytes = reinterpret_cast<uint8_t*>(ent + PP4_ANCH * es);                     // [PP4_ANCH][M], m order
+        const bool ok = kth >= 1 && l >= 0 && grp < np && a.k <= PP4_ANCH;                    // slot-uniform
+        int cnt = 0;
+        if (ok) {       // wave wq of the slot: the hits of its quarter of the sample, in position order
+            const int per = ((N + 255) >> 8) << 6;
+            const int t1 = (wq + 1) * per < N ? (wq + 1) * per : N;
+            for (int t0 = wq * per; t0 < t1 && cnt < PP4_ANCH; t0 += 64) {
+                const int t = t0 + lane;
+                const bool hit = t < t1 && (int)mysum[t] >= kth;
+                const uint64_t mk = __builtin_amdgcn_ballot_w64(hit);
+                const int p = cnt + (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(mk >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mk, 0u));
+                if (hit && p < PP4_ANCH) hs[wq * PP4_ANCH + p] = t;
+                cnt += __builtin_popcountll((unsigned long long)mk);
+            }
+            if (cnt > PP4_ANCH) cnt = PP4_ANCH;
+        }
+        if (lane == 0) hs[4 * PP4_ANCH + wq] = cnt;
+        __syncthreads();
+        const int c0 = hs[4 * PP4_ANCH], c1 = hs[4 * PP4_ANCH + 1], c2 = hs[4 * PP4_ANCH + 2], c3 = hs[4 * PP4_ANCH + 3];
+        const int call = c0 + c1 + c2 + c3;
+        const int C = call < PP4_ANCH ? call : PP4_ANCH;       // >= k whenever ok: kth is the k-th largest sum of the sample
+        auto row_of = [&](int c) -> int64_t {                  // anchor c of the slot: the four waves' lists one after the other
+            int wv = 0, j = c;
+            if (j >= c0) { j -= c0; wv = 1; if (j >= c1) { j -= c1; wv = 2; if (j >= c2) { j -= c2; wv = 3; } } }
+            return lrow0 + hs[wv * PP4_ANCH + j];
+        };
+        if (tg < C * nrun) {       // one thread per (anchor, run of 16 sub-quantisers): its piece, rotated back into m order
+            const int c = tg / nrun, run = tg - c * nrun;
+            const int64_t row = row_of(c);
+            const uint8_t* p0; const uint8_t* p1;
+            pq_piece_ptrs(a.codes, row, M, a.CB, run, p0, p1);
+            const uint2 lo2 = *reinterpret_cast<const uint2*>(p0), hi2 = *reinterpret_cast<const uint2*>(p1);
+            uint32_t wd[4] = {lo2.x, lo2.y, hi2.x, hi2.y};
+            rot16_bytes(wd, (int)(row & 15));
+            *reinterpret_cast<uint4*>(cbytes + c * M + run * 16) = make_uint4(wd[0], wd[1], wd[2], wd[3]);
+        }
+        __syncthreads();
+        if (C > 0) {       // table entries, four per thread in flight (k = 10 at M = 96: 960 entries = one round of codeword loads)
+            const float* qv = a.Q32 + q * a.ldq;
+            for (int e0 = tg; e0 < C * M; e0 += 4 * 256) {
+                int at[4]; const float* cw[4]; const float* qs[4]; float t[4];
+#pragma unroll
+                for (int u = 0; u < 4; u++) {
+                    const int e = e0 + 256 * u < C * M ? e0 + 256 * u : e0;
+                    const int c = e / M, m = e - c * M;
+                    at[u] = c * es + m; qs[u] = qv + m * a.dsub;
+                    cw[u] = a.codebooks + ((int64_t)m * 256 + cbytes[c * M + m]) * a.dsub;
+                }
+#pragma unroll
+                for (int u = 0; u < 4; u++) t[u] = pq_ip_entry(qs[u], cw[u], a.dsub);
+#pragma unroll
+                for (int u = 0; u < 4; u++) if (e0 + 256 * u < C * M) ent[at[u]] = t[u];
+            }
+        }
+        __syncthreads();
+        if (wq == 0 && C >= a.k && ok) {       // wave 0 of the slot: a lane per anchor
+            float sc = -__builtin_inff();
+            if (lane < C) {
+                float sum = 0.0f;
+                for (int m0 = 0; m0 < M; m0 += 16) {       // sixteen entries in flight, added in m order
+                    float v[16];
+#pragma unroll
+                    for (int j = 0; j < 16; j++) v[j] = ent[lane * es + m0 + j];
+#pragma unroll
+                    for (int j = 0; j < 16; j++) sum += v[j];
+                }
+                sc = (a.probe_dis0[q * a.nprobe + j0] + sum) + 0.0f;
+            }
+            const bool fin = lane >= C || fabsf(sc) < __builtin_inff();
+            int rank = 0;
+            for (int j = 0; j < C; j++) { const float sj = __shfl(sc, j); rank += (sj > sc || (sj == sc && j < lane)) ? 1 : 0; }
+            const uint64_t at = __builtin_amdgcn_ballot_w64(lane < C && rank == a.k - 1);
+            if (__builtin_amdgcn_ballot_w64(!fin) == 0ull && at != 0ull) {
+                s_k = __shfl(sc, (int)__builtin_ctzll((unsigned long long)at));
+                anchored = true;
+            }
+        }
+    }
+    }
     PP4_MARK(5);
     // ---- the threshold (k_pq_prepass's arithmetic), the empty merge state, the candidate counter
     if (grp < np) {
@@ -2043,6 +2136,12 @@ __global__ __launch_bounds__(1024) void k_pq_prepass4(PQPrepassArgs a, int64_t n
                 float t = __fmaf_rn(-2.0002f, eps, a_k);
                 t -= fabsf(t) * 4.8e-7f + 1e-30f;
                 tau = make_key(t, 0xFFFFFFFFu);
+                if (anchored && scale > 0.0f) {       // never looser than a_k - 2 eps, whatever the rounding does
+                    float t2 = __fmaf_rn(-1.0001f, eps, s_k);
+                    t2 -= fabsf(t2) * 4.8e-7f + 1e-30f;
+                    const uint64_t tau2 = fabsf(t2) < __builtin_inff() ? make_key(t2, 0xFFFFFFFFu) : 0ull;
+                    if (tau2 > tau) tau = tau2;
+                }
             }
             a.tau[q] = tau;
             a.cand_cnt[q * CCS] = 0ull;

@@ -1,6 +1,7 @@
 // k_rescore.h — the exact re-score of stored rows and the (score desc, id asc) sort of a candidate set in LDS, shared by k_finalize
 // (k_select.hip: candidates of a Flat / IVF-Flat scan) and k_refine (k_refine.hip: candidates named by label, rsx_refine), and k_refine's
-// launch interface (api_refine.hip).
+// launch interface (api_refine.hip); the pieces of the canonical IVF-PQ score (code bytes of a 16-sub-quantiser run in m order, one table
+// entry by the table builder's chain) that k_finalize and the threshold pre-pass's anchor rows (k_pq_rot.hip: k_pq_prepass4) both use.
 #pragma once
 #include "rsx_internal.h"
 
@@ -10,6 +11,31 @@ __device__ inline double wave_sum_f64(double v) {
 #pragma unroll
     for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
     return v;
+}
+
+// The 16-byte piece of a 16-sub-quantiser run (pq_piece_ptrs, rsx_internal.h) rotated left by i = row & 15 bytes: the codes in m order.
+__device__ inline void rot16_bytes(uint32_t (&w)[4], int i) {     // byte t of the result = byte (t - i) & 15 of the input
+    const int wi = i >> 2, bi = i & 3;
+    if (wi & 1) { const uint32_t t = w[3]; w[3] = w[2]; w[2] = w[1]; w[1] = w[0]; w[0] = t; }
+    if (wi & 2) { uint32_t t = w[0]; w[0] = w[2]; w[2] = t; t = w[1]; w[1] = w[3]; w[3] = t; }
+    if (bi) {
+        const int l = 8 * bi, r = 32 - l;
+        const uint32_t r0 = (w[0] << l) | (w[3] >> r), r1 = (w[1] << l) | (w[0] >> r), r2 = (w[2] << l) | (w[1] >> r), r3 = (w[3] << l) | (w[2] >> r);
+        w[0] = r0; w[1] = r1; w[2] = r2; w[3] = r3;
+    }
+}
+// Inner-product table entry of one (sub-quantiser, code): <qs, cw> by the table builder's fmaf chain from +0 (k_pq_lut / k_pq_lut8f), hence
+// the same bits; the canonical IVF-PQ score is dis0 + the sum of a vector's M entries added in m order.
+__device__ __forceinline__ float pq_ip_entry(const float* qs, const float* cw, int dsub) {
+    float t = 0.0f;
+    if (dsub == 8) {
+        const float4 x = ((const float4*)cw)[0], y = ((const float4*)cw)[1];
+        t = __fmaf_rn(qs[0], x.x, t); t = __fmaf_rn(qs[1], x.y, t); t = __fmaf_rn(qs[2], x.z, t); t = __fmaf_rn(qs[3], x.w, t);
+        t = __fmaf_rn(qs[4], y.x, t); t = __fmaf_rn(qs[5], y.y, t); t = __fmaf_rn(qs[6], y.z, t); t = __fmaf_rn(qs[7], y.w, t);
+    } else {
+        for (int tt = 0; tt < dsub; tt++) t = __fmaf_rn(qs[tt], cw[tt], t);
+    }
+    return t;
 }
 
 // Candidates c of [c_lo, c_hi) whose storage row srow[c] lies in [0, nrows) get sord[c] = the order word of their exact score against the

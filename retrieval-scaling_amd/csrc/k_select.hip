@@ -1443,18 +1443,8 @@ __device__ inline float pq_exact_sum_rot(const uint8_t* codes, int64_t row, int 
 
 // The same sum with the vector's code bytes fetched as the 16-byte (8-byte) pieces the rotated layout stores (rsx_internal.h):
 // for every run of 16 sub-quantisers the piece of lane group g, rotated left by i = row & 15 bytes, holds the codes in m
-// order.  One round trip for all M codes instead of M byte loads, and 16 independent codeword loads per run; table entries
+// order (rot16_bytes, k_rescore.h).  One round trip for all M codes instead of M byte loads, and 16 independent codeword loads per run; table entries
 // by the table builder's fmaf chain, added in m order — the identical fp32 value.  dsub == 8, M in {32, 64, 96, 128}.
-__device__ inline void rot16_bytes(uint32_t (&w)[4], int i) {     // byte t of the result = byte (t - i) & 15 of the input
-    const int wi = i >> 2, bi = i & 3;
-    if (wi & 1) { const uint32_t t = w[3]; w[3] = w[2]; w[2] = w[1]; w[1] = w[0]; w[0] = t; }
-    if (wi & 2) { uint32_t t = w[0]; w[0] = w[2]; w[2] = t; t = w[1]; w[1] = w[3]; w[3] = t; }
-    if (bi) {
-        const int l = 8 * bi, r = 32 - l;
-        const uint32_t r0 = (w[0] << l) | (w[3] >> r), r1 = (w[1] << l) | (w[0] >> r), r2 = (w[2] << l) | (w[1] >> r), r3 = (w[3] << l) | (w[2] >> r);
-        w[0] = r0; w[1] = r1; w[2] = r2; w[3] = r3;
-    }
-}
 __device__ inline float pq_exact_sum_rot_wide(const uint8_t* codes, int64_t row, int M, const float* qv, const float* codebooks, int CB = 0,
                                               const uint8_t* plain = nullptr, int plain_stride = 0) {
     const int i = plain ? 0 : (int)(row & 15);       // the row-major copy holds the bytes in m order already: nothing to rotate back

@@ -559,6 +559,7 @@ int rsx_set_param(rsx_index_t* h, const char* key, double value) {
         else if (s == "ivf_pre_lists") h->ivf_pre_lists = std::max(0, (int)value);
         else if (s == "ivf_pre_mult") h->ivf_pre_mult = std::max(1, (int)value);
         else if (s == "pq_pre_rows") h->pq_pre_rows = (int)value;
+        else if (s == "pq_tau_anchor") h->pq_tau_anchor = (int)value;
         else if (s == "pq_flat_first") h->pq_flat_first = std::max(0, (int)value);
         else if (s == "pq_flat_growth") h->pq_flat_growth = std::max(0, (int)value);
         else if (s == "pq_flat_max_stages") h->pq_flat_max_stages = std::min(64, std::max(0, (int)value));

@@ -253,6 +253,7 @@ struct rsx_index {
     int pq_flat_growth = 0;      // ... percent by which a stage outgrows the one before it (0 = 300: each stage three times the rows scanned so far)
     int pq_flat_max_stages = 0;  // ... most stages (0 = 12; the last stage takes whatever is left)
     int pq_pre_rows = 4096;  // filtered fast scan: vectors of each query's closest list the threshold pre-pass scores (0 = one scan tile)
+    int pq_tau_anchor = 1;   // four-query threshold pre-pass: raise the threshold to (k-th best CANONICAL score of the sample's k best rows) - eps; 0 = a_k - 2 eps alone.  Read per batch
     int add_list_mod = 1, add_list_rem = 0;   // IVF add keeps only lists l with l % mod == rem (list-sharded multi-GPU index)
     int64_t ndropped = 0;                     // vectors seen by add but owned by other shards
     int flat_filter = 1;  // Flat: filtered GEMM launches after the threshold phase (0 = score buffer per chunk)

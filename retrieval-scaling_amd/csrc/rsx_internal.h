@@ -152,7 +152,7 @@ __device__ __forceinline__ float pq_l2_entry(const float* qs, const float* cw, i
     return acc;
 }
 // The two 8-byte halves of the piece that holds sub-quantisers 16 run .. 16 run + 15 of vector `row` (M >= 32, rotated or sliced layout);
-// rotated left by row & 15 bytes (rot16_bytes, k_select.hip) the 16 bytes are the codes in m order.
+// rotated left by row & 15 bytes (rot16_bytes, k_rescore.h) the 16 bytes are the codes in m order.
 __device__ inline void pq_piece_ptrs(const uint8_t* codes, int64_t row, int M, int CB, int run, const uint8_t*& p0, const uint8_t*& p1) {
     const int i = (int)(row & 15);
     if (CB == PQ_SLICED) {
@@ -455,6 +455,10 @@ struct PQPrepassArgs {
     // emission (null cand = off): the sample's keys above the threshold go straight to cand[q][..] when the sample covers the
     // first scan tile (tile_rows) of the list; excl[q] = 0x8000 | probe rank tells the scan to drop that (query, list, tile 0)
     uint64_t* cand; int cand_cap; int tile_rows; uint16_t* excl;
+    // exact anchor (k_pq_prepass4, the form that keeps the sample's sums; null codebooks = off, the threshold is a_k - 2 eps alone): the
+    // canonical scores of the sample's k best rows raise the threshold to (their minimum) - eps.  Inner product only.
+    const float* codebooks; int dsub;                      // [Mpad][256][dsub]
+    const float* Q32; int ldq;                             // the fp32 queries the tables were built from, rows of ldq values
 };
 void launch_pq_prepass(const PQPrepassArgs& a, int64_t nq, hipStream_t st);
 // the same threshold from four queries per workgroup on the scan's table format (k_pq_rot.hip: k_pq_prepass4; no emission);
