@@ -46,7 +46,7 @@ enum rsx_status {
 
 enum rsx_metric { RSX_METRIC_INNER_PRODUCT = 0, RSX_METRIC_L2 = 1 }; /* = faiss.METRIC_* */
 enum rsx_dtype { RSX_F32 = 0, RSX_F16 = 1 };
-enum rsx_kind { RSX_KIND_FLAT = 0, RSX_KIND_IVFFLAT = 1, RSX_KIND_IVFPQ = 2, RSX_KIND_PQ = 3 };
+enum rsx_kind { RSX_KIND_FLAT = 0, RSX_KIND_IVFFLAT = 1, RSX_KIND_IVFPQ = 2, RSX_KIND_PQ = 3, RSX_KIND_IVFSQ = 4 };
 
 /* Thread-local message of the last error raised on the calling thread ("" if none). */
 const char* rsx_last_error(void);
@@ -92,6 +92,20 @@ int rsx_ivfpq_create(int d, int nlist, int M, int nbits, int metric, int device,
  * rsx_set_centroids / rsx_get_centroids (RSX_ERR_INVALID). */
 int rsx_pq_create(int d, int M, int nbits, int metric, int device, rsx_index_t** out);
 
+/* faiss.IndexIVFScalarQuantizer(quantizer, d, nlist, ScalarQuantizer.QT_8bit, metric, by_residual) — factory "IVF<nlist>,SQ8": one byte
+ * per dimension, half of what IndexIVFFlat's fp16 rows take.  qtype must be 0 (QT_8bit: per-dimension range, RS_minmax
+ * with argument 0); any other qtype is RSX_ERR_UNSUPPORTED (QT_fp16 rows are what rsx_ivfflat_create stores).  The coarse quantiser is
+ * the inner-product one of the other IVF kinds for either metric; list membership is the argmax-IP list of x.  A stored vector is
+ * x^ = the decoded code (by_residual = 0) or fl(c_l + the decoded residual) (by_residual = 1), and a search returns the canonical
+ * Flat scores of the queries against x^ over the probed lists (fp64 accumulation, rounded once; squared L2 = distance to x^), ties by
+ * id: a certified fp16-MFMA scan over the code bytes (k_sq_list_scan), exact re-score of the candidates from their decoded rows,
+ * exact re-run of the queries the certificate cannot clear.  rsx_train trains the coarse quantiser, then the per-dimension minimum and
+ * maximum - minimum over ALL training vectors (their residuals when by_residual) on the GPU; the handle is trained once centroids AND
+ * parameters are present.  rsx_add_list / rsx_get_list carry uint8 [n, d] codes; rsx_get "kind" = RSX_KIND_IVFSQ, "code_size" = d,
+ * plus "qtype" and "by_residual".  Refused with RSX_ERR_UNSUPPORTED and a message naming the kind: selectors, rsx_remove_ids, sharded
+ * handles (rsx_sharded_create, rsx_load_sharded), the two-call search, "scan_chunk". */
+int rsx_ivfsq_create(int d, int nlist, int qtype, int metric, int by_residual, int device, rsx_index_t** out);
+
 /* ONE handle over several GPUs of the node, single process — SURVEY.md 8(b)/(e).  The reference's offline driver makes one
  * index.search(all_queries, k) call (src/search.py:296) and its serving tier fans a query out to shard workers over HTTP and
  * re-sorts (api/serve_main_node.py:281-323); with this handle the same `Indexer(cfg).search` spans the node:
@@ -127,6 +141,9 @@ int rsx_set_centroids(rsx_index_t* h, const float* centroids);
 int rsx_set_codebooks(rsx_index_t* h, const float* codebooks);
 int rsx_get_centroids(rsx_index_t* h, float* centroids_out);
 int rsx_get_codebooks(rsx_index_t* h, float* codebooks_out);
+/* IVFSQ: the scalar quantiser's parameters, [2 d] f32 = vmin[d] then vdiff[d] (faiss ScalarQuantizer::trained). */
+int rsx_set_sq_trained(rsx_index_t* h, const float* trained);
+int rsx_get_sq_trained(rsx_index_t* h, float* trained_out);
 
 /* ---- population -------------------------------------------------------------------- */
 
@@ -211,7 +228,7 @@ int rsx_merge_packed(int nshards, int64_t nq, int k, int metric, const int64_t* 
 /* ---- introspection / knobs --------------------------------------------------------- */
 
 /* Integer properties: "ntotal", "nlist", "d", "is_trained", "nprobe", "M", "nbits", "kind",
- * "metric", "storage_dtype", "code_size", "device", "max_k", "pq_layout" (IVFPQ: 1 = rotated code layout), "nshards"
+ * "metric", "storage_dtype", "code_size", "qtype" / "by_residual" (IVFSQ), "device", "max_k", "pq_layout" (IVFPQ: 1 = rotated code layout), "nshards"
  * (0 = single-device handle), "hbm_bytes", "explicit_ids" (1 = a Flat handle that stores caller ids, or any handle one of whose
  * rsx_add calls since the last rsx_reset carried ids).
  * (index.ntotal / index.is_trained — ivf_flat.py:171; ivf_pq.py:175) */

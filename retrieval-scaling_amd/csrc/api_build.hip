@@ -22,7 +22,7 @@ int64_t workspace_bytes(const rsx_index* h) {
     const DevBuf* bufs[] = {&h->w_q32, &h->w_q16, &h->w_coarse, &h->w_keys1, &h->w_probekeys, &h->w_probelist, &h->w_dis0, &h->w_segstart,
                             &h->w_temp, &h->w_lut, &h->w_lutws, &h->w_state, &h->w_D, &h->w_I, &h->w_qin, &h->w_pairs, &h->w_flag, &h->w_x,
                             &h->w_partial, &h->w_assign, &h->w_dest, &h->w_idsin, &h->w_misc, &h->w_lut8, &h->w_qparam, &h->w_uncertain,
-                            &h->w_fbq, &h->w_fbD, &h->w_fbI, &h->w_cand, &h->w_candcnt, &h->w_itemdesc, &h->w_tau, &h->w_excl, &h->w_state2, &h->w_addcnt, &h->w_addstart, &h->w_qitems, &h->w_tiews, &h->w_stagedir, &h->w_rlabels, &h->sh_D, &h->sh_I, &h->sh_q,
+                            &h->w_fbq, &h->w_fbD, &h->w_fbI, &h->w_cand, &h->w_candcnt, &h->w_itemdesc, &h->w_tau, &h->w_excl, &h->w_state2, &h->w_addcnt, &h->w_addstart, &h->w_qitems, &h->w_tiews, &h->w_stagedir, &h->w_rlabels, &h->w_sqhi, &h->w_sqlo, &h->w_sqc, &h->sh_D, &h->sh_I, &h->sh_q,
                             &h->sh_oD, &h->sh_oI, &h->sel_mask, &h->sel_dev, &h->codes_plain /* derived from the payload on demand, dropped by the next add */};
     int64_t t = 0;
     for (const DevBuf* b : bufs) t += (int64_t)b->bytes;
@@ -135,8 +135,21 @@ void set_codebooks(rsx_index* h, const float* c) {
     HIPCHECK(hipMemcpyAsync(h->d_codebooks.p, h->h_codebooks.data(), n * 4, hipMemcpyHostToDevice, h->st));
     HIPCHECK(hipStreamSynchronize(h->st));
 }
+// QT_8bit parameters: vmin[d] then vdiff[d].  The norms are certificate terms (finalize_args): rounded up, like cent_cmax
+void set_sq_trained(rsx_index* h, const float* t) {
+    const size_t n = (size_t)2 * h->d;
+    h->h_sq.assign(t, t + n);
+    double a = 0.0, b = 0.0; float vm = 0.0f;
+    for (int j = 0; j < h->d; j++) { a += (double)t[j] * t[j]; b += (double)t[h->d + j] * t[h->d + j]; vm = std::max(vm, std::fabs(t[h->d + j])); }
+    h->sq_vdmax = vm;
+    h->sq_nvmin = (float)(std::sqrt(a) * 1.000001); h->sq_nvdiff = (float)(std::sqrt(b) * 1.000001);
+    h->d_sq.ensure(n * 4);
+    HIPCHECK(hipMemcpyAsync(h->d_sq.p, h->h_sq.data(), n * 4, hipMemcpyHostToDevice, h->st));
+    HIPCHECK(hipStreamSynchronize(h->st));
+}
 void update_trained(rsx_index* h) {
     if (h->kind == KIND_FLAT) h->trained = true;
+    else if (h->kind == KIND_IVFSQ) h->trained = !h->h_centroids.empty() && !h->h_sq.empty();
     else if (h->kind == KIND_IVFFLAT) h->trained = !h->h_centroids.empty();
     else h->trained = !h->h_centroids.empty() && !h->h_codebooks.empty();
 }
@@ -199,6 +212,16 @@ rsx_index* create_common(int kind, int d, int nlist, int M, int nbits, int metri
     return h.release();
 }
 
+// faiss.IndexIVFScalarQuantizer(quantizer, d, nlist, qtype, metric, by_residual): QT_8bit only
+rsx_index* create_ivfsq(int d, int nlist, int qtype, int metric, int by_residual, int device) {
+    if (qtype != 0)
+        RSX_THROW(RSX_ERR_UNSUPPORTED, "IVFSQ: only QT_8bit (qtype 0) is implemented (got qtype %d); fp16 rows (QT_fp16) are what IndexIVFFlat stores", qtype);
+    std::unique_ptr<rsx_index> h(create_common(KIND_IVFSQ, d, nlist, 0, 8, metric, device));
+    h->sq_qtype = qtype; h->by_residual = by_residual != 0;
+    h->storage_f16 = 1; h->storage_decided = true;      // (no row dtype to decide: the rows are code bytes)
+    return h.release();
+}
+
 // faiss.IndexPQ: one list, zero centroid (rsx_index::flat_pq); trained once the codebooks are there
 rsx_index* create_flat_pq(int d, int M, int nbits, int metric, int device) {
     std::unique_ptr<rsx_index> h(create_common(KIND_IVFPQ, d, 1, M, nbits, metric, device));
@@ -213,7 +236,7 @@ rsx_index* create_flat_pq(int d, int M, int nbits, int metric, int device) {
 // add
 // ---------------------------------------------------------------------------------------
 static void decide_storage(rsx_index* h, const void* dx, int64_t n, int dtype) {
-    if (h->kind == KIND_IVFPQ) return;
+    if (h->kind == KIND_IVFPQ || h->kind == KIND_IVFSQ) return;
     if (dtype == RSX_F16) { h->storage_decided = true; return; }
     if (h->storage_decided && !h->storage_f16) return;
     h->w_flag.ensure(sizeof(int));
@@ -237,6 +260,20 @@ static void track_max_norm(rsx_index* h, const void* dx, int64_t n, int dtype) {
     HIPCHECK(hipStreamSynchronize(h->st));
 }
 
+// IVFSQ: the device word the encoder folds |x^|^2 into (the largest over everything ever added, as track_max_norm keeps it for stored rows)
+// ([1]: the largest sum_j (code_j - 128)^2 of a stored row, the other data-dependent term of the scan's certificate)
+static void sq_maxnorm_begin(rsx_index* h) {
+    if (h->d_maxnorm.p) return;
+    h->d_maxnorm.ensure(2 * sizeof(unsigned int));
+    unsigned int w[2]; memcpy(&w[0], &h->max_norm2, 4); w[1] = h->sq_bn2;
+    HIPCHECK(hipMemcpyAsync(h->d_maxnorm.p, w, sizeof(w), hipMemcpyHostToDevice, h->st));
+    HIPCHECK(hipStreamSynchronize(h->st));      // w is a local
+}
+static void sq_maxnorm_end(rsx_index* h) {      // (the caller synchronises the stream before it reads the two)
+    HIPCHECK(hipMemcpyAsync(&h->max_norm2, h->d_maxnorm.p, sizeof(float), hipMemcpyDeviceToHost, h->st));
+    HIPCHECK(hipMemcpyAsync(&h->sq_bn2, h->d_maxnorm.as<unsigned int>() + 1, sizeof(unsigned int), hipMemcpyDeviceToHost, h->st));
+}
+
 static void add_batch(rsx_index* h, int64_t n, const void* x, int dtype, const int64_t* ids) {
     const void* dx = stage_rows(h, h->w_x, x, n, h->d, dtype);
     const int64_t* dids = nullptr;
@@ -249,7 +286,7 @@ static void add_batch(rsx_index* h, int64_t n, const void* x, int dtype, const i
         }
     }
     decide_storage(h, dx, n, dtype);
-    if (h->kind != KIND_IVFPQ) track_max_norm(h, dx, n, dtype);
+    if (h->kind != KIND_IVFPQ && h->kind != KIND_IVFSQ) track_max_norm(h, dx, n, dtype);      // (IVFSQ: over the decoded vectors, by the encoder)
 
     if (h->kind == KIND_FLAT) {
         if (ids && !h->custom_ids) {
@@ -323,6 +360,14 @@ static void add_batch(rsx_index* h, int64_t n, const void* x, int dtype, const i
                          h->w_assign.as<int32_t>(), h->d_codebooks.as<float>(), h->w_dest.as<int64_t>(),
                          h->data.as<uint8_t>(), nullptr, h->st);
         launch_write_ids(h->w_dest.as<int64_t>(), dids, h->ntotal + h->ndropped, n, h->ids.as<int64_t>(), h->st);
+    } else if (h->kind == KIND_IVFSQ) {
+        // codes, and the norm term of the vector the re-score will decode, in one pass (k_sq_encode); the running maximum of |x^|^2 with them
+        sq_maxnorm_begin(h);
+        launch_sq_encode(dx, dtype == RSX_F16, n, h->d, h->ld, h->d_sq.as<float>(), h->by_residual ? h->d_centroids.as<float>() : nullptr,
+                         h->w_assign.as<int32_t>(), h->w_dest.as<int64_t>(), h->data.as<uint8_t>(), h->norms.p ? h->norms.as<float>() : nullptr,
+                         h->d_maxnorm.as<unsigned int>(), h->st);
+        launch_write_ids(h->w_dest.as<int64_t>(), dids, h->ntotal + h->ndropped, n, h->ids.as<int64_t>(), h->st);
+        sq_maxnorm_end(h);
     } else {
         launch_scatter_rows(dx, dtype == RSX_F16, n, h->d, h->w_dest.as<int64_t>(), h->data.p, h->storage_f16, h->ld,
                             h->norms.p ? h->norms.as<float>() : nullptr, dids, h->ntotal + h->ndropped, h->ids.as<int64_t>(), h->st);
@@ -428,12 +473,14 @@ void train_impl(rsx_index* h, int64_t n, const void* x, int dtype) {
     const int d = h->d;
     // training set as fp32 on the host (the reference passes host numpy: ivf_flat.py:135)
     std::vector<float> hx((size_t)n * d);
+    DevBuf t32;                                   // the same on the device: kept for the scalar quantiser's min / max pass, else released here
     {
         const void* dx = stage_rows(h, h->w_x, x, n, d, dtype);
-        DevBuf t32; t32.ensure((size_t)n * d * 4);
+        t32.ensure((size_t)n * d * 4);
         launch_convert_to_f32(dx, dtype == RSX_F16, d, n, d, t32.as<float>(), d, h->st);
         HIPCHECK(hipMemcpyAsync(hx.data(), t32.p, (size_t)n * d * 4, hipMemcpyDeviceToHost, h->st));
         HIPCHECK(hipStreamSynchronize(h->st));
+        if (h->kind != KIND_IVFSQ) t32.release();
     }
     const uint64_t seed = 1234;
     std::vector<float> cen((size_t)h->nlist * d), cb;
@@ -528,8 +575,33 @@ void train_impl(rsx_index* h, int64_t n, const void* x, int dtype) {
         }
         HIPCHECK(hipGetLastError());
     }
+    // ---- scalar quantiser: per-dimension min and max - min over ALL training vectors (or their residuals to the new centroids), on the GPU
+    std::vector<float> sqt;
+    if (h->kind == KIND_IVFSQ) {
+        DevBuf& dxa = t32;
+        DevBuf dmm;
+        dmm.ensure((size_t)2 * d * 4);
+        if (h->by_residual) {
+            int ct = (h->nlist + 127) / 128;
+            h->w_partial.ensure((size_t)n * 2 * ct * 8);
+            h->w_assign.ensure((size_t)n * 4);
+            launch_gemm_exact_argmax(dxa.p, 0, n, d, dcen.as<float>(), h->nlist, d, h->w_partial.as<uint64_t>(), h->w_assign.as<int32_t>(), nullptr, h->st);
+        }
+        launch_sq_minmax(dxa.as<float>(), n, d, h->by_residual ? dcen.as<float>() : nullptr, h->w_assign.as<int32_t>(), dmm.as<uint32_t>(), h->st);
+        std::vector<uint32_t> mm((size_t)2 * d);
+        HIPCHECK(hipMemcpyAsync(mm.data(), dmm.p, (size_t)2 * d * 4, hipMemcpyDeviceToHost, h->st));
+        HIPCHECK(hipStreamSynchronize(h->st));
+        HIPCHECK(hipGetLastError());
+        sqt.resize((size_t)2 * d);
+        for (int j = 0; j < d; j++) {
+            const float mn = ord2f(mm[(size_t)j]), mx = ord2f(mm[(size_t)d + j]);
+            const float df = mx - mn;           // one fp32 rounding
+            sqt[(size_t)j] = mn; sqt[(size_t)d + j] = df;
+        }
+    }
     set_centroids(h, cen.data());
     if (h->kind == KIND_IVFPQ) set_codebooks(h, cb.data());
+    if (h->kind == KIND_IVFSQ) set_sq_trained(h, sqt.data());
     update_trained(h);
 }
 
@@ -550,13 +622,18 @@ void get_list_impl(rsx_index* h, int64_t l, int64_t* n_out, void* codes_out, int
             bytes = (size_t)n * h->M;
             t.ensure(bytes);
             launch_pq_export_list(h->data.as<uint8_t>(), base, n, h->M, h->Mpad, h->CB, t.as<uint8_t>(), h->st);
+        } else if (h->kind == KIND_IVFSQ) {      // uint8 [n, d]: the rows without their padding, straight to the caller
+            HIPCHECK(hipMemcpy2DAsync(codes_out, (size_t)h->d, h->data.as<uint8_t>() + (size_t)base * h->ld, (size_t)h->ld, (size_t)h->d, (size_t)n,
+                                      is_device_ptr(codes_out) ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, h->st));
+            HIPCHECK(hipStreamSynchronize(h->st));
+            bytes = 0;
         } else {
             bytes = (size_t)n * h->d * 4;
             t.ensure(bytes);
             size_t esz = h->storage_f16 ? 2 : 4;
             launch_convert_to_f32(h->data.as<uint8_t>() + (size_t)base * h->ld * esz, h->storage_f16, h->ld, n, h->d, t.as<float>(), h->d, h->st);
         }
-        HIPCHECK(hipMemcpyAsync(codes_out, t.p, bytes, is_device_ptr(codes_out) ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, h->st));
+        if (bytes) HIPCHECK(hipMemcpyAsync(codes_out, t.p, bytes, is_device_ptr(codes_out) ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, h->st));
         HIPCHECK(hipStreamSynchronize(h->st));
     }
     if (ids_out) {
@@ -571,6 +648,19 @@ void get_list_impl(rsx_index* h, int64_t l, int64_t* n_out, void* codes_out, int
     }
 }
 
+// The destination rows row0 .. row0 + n - 1 of a list import in w_dest and the caller's ids on the device (returned; `dest` and `ti` hold the
+// host image and a staged copy until the caller has synchronised the stream).
+static const int64_t* stage_list_dest(rsx_index* h, int64_t row0, int64_t n, const int64_t* ids, std::vector<int64_t>& dest, DevBuf& ti) {
+    dest.resize((size_t)n);
+    for (int64_t i = 0; i < n; i++) dest[(size_t)i] = row0 + i;
+    h->w_dest.ensure((size_t)n * 8);
+    HIPCHECK(hipMemcpyAsync(h->w_dest.p, dest.data(), (size_t)n * 8, hipMemcpyHostToDevice, h->st));
+    if (is_device_ptr(ids)) return ids;
+    ti.ensure((size_t)n * 8);
+    HIPCHECK(hipMemcpyAsync(ti.p, ids, (size_t)n * 8, hipMemcpyHostToDevice, h->st));
+    return ti.as<int64_t>();
+}
+
 void add_list_impl(rsx_index* h, int64_t l, int64_t n, const void* codes, int dtype, const int64_t* ids) {
     if (h->kind == KIND_FLAT) RSX_THROW(RSX_ERR_INVALID, "add_list: use rsx_add for Flat");
     if (!h->trained) RSX_THROW(RSX_ERR_NOT_TRAINED, "add_list before train");
@@ -580,7 +670,8 @@ void add_list_impl(rsx_index* h, int64_t l, int64_t n, const void* codes, int dt
     std::vector<int64_t> need(h->h_len);
     int64_t pos0 = need[(size_t)l];
     need[(size_t)l] += n;
-    std::vector<int64_t> dest((size_t)n);
+    std::vector<int64_t> dest;
+    DevBuf ti;
     if (h->kind == KIND_IVFPQ) {
         ensure_capacity(h, need, true);
         DevBuf t;
@@ -591,16 +682,22 @@ void add_list_impl(rsx_index* h, int64_t l, int64_t n, const void* codes, int dt
             dc = t.p;
         }
         launch_pq_import_list((const uint8_t*)dc, h->h_base[(size_t)l], pos0, n, h->M, h->Mpad, h->CB, h->data.as<uint8_t>(), h->st);
-        for (int64_t i = 0; i < n; i++) dest[(size_t)i] = h->h_base[(size_t)l] + pos0 + i;
-        h->w_dest.ensure((size_t)n * 8);
-        HIPCHECK(hipMemcpyAsync(h->w_dest.p, dest.data(), (size_t)n * 8, hipMemcpyHostToDevice, h->st));
-        const int64_t* dids = ids;
-        DevBuf ti;
-        if (!is_device_ptr(ids)) {
-            ti.ensure((size_t)n * 8);
-            HIPCHECK(hipMemcpyAsync(ti.p, ids, (size_t)n * 8, hipMemcpyHostToDevice, h->st));
-            dids = ti.as<int64_t>();
-        }
+        const int64_t* dids = stage_list_dest(h, h->h_base[(size_t)l] + pos0, n, ids, dest, ti);
+        launch_write_ids(h->w_dest.as<int64_t>(), dids, 0, n, h->ids.as<int64_t>(), h->st);
+        HIPCHECK(hipStreamSynchronize(h->st));
+    } else if (h->kind == KIND_IVFSQ) {
+        // uint8 [n, d] codes into rows of ld bytes, then the norm terms of the decoded rows as the encoder computes them.  The ld - d padding
+        // bytes of the rows are NOT written (they hold what the buffer held): the query factors of dimensions >= d are zero and every byte
+        // widens to a finite value, so they contribute nothing to a score; norms and the re-score read d bytes.
+        ensure_capacity(h, need, true);
+        const int64_t row0 = h->h_base[(size_t)l] + pos0;
+        HIPCHECK(hipMemcpy2DAsync(h->data.as<uint8_t>() + (size_t)row0 * h->ld, (size_t)h->ld, codes, (size_t)h->d, (size_t)h->d, (size_t)n,
+                                  is_device_ptr(codes) ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, h->st));
+        sq_maxnorm_begin(h);
+        launch_sq_norms(h->data.as<uint8_t>(), row0, n, h->d, h->ld, h->d_sq.as<float>(), h->by_residual ? h->d_centroids.as<float>() + (size_t)l * h->d : nullptr,
+                        h->norms.p ? h->norms.as<float>() : nullptr, h->d_maxnorm.as<unsigned int>(), h->st);
+        sq_maxnorm_end(h);
+        const int64_t* dids = stage_list_dest(h, row0, n, ids, dest, ti);
         launch_write_ids(h->w_dest.as<int64_t>(), dids, 0, n, h->ids.as<int64_t>(), h->st);
         HIPCHECK(hipStreamSynchronize(h->st));
     } else {
@@ -608,16 +705,7 @@ void add_list_impl(rsx_index* h, int64_t l, int64_t n, const void* codes, int dt
         decide_storage(h, dx, n, dtype);
         track_max_norm(h, dx, n, dtype);
         ensure_capacity(h, need, true);
-        for (int64_t i = 0; i < n; i++) dest[(size_t)i] = h->h_base[(size_t)l] + pos0 + i;
-        h->w_dest.ensure((size_t)n * 8);
-        HIPCHECK(hipMemcpyAsync(h->w_dest.p, dest.data(), (size_t)n * 8, hipMemcpyHostToDevice, h->st));
-        const int64_t* dids = ids;
-        DevBuf ti;
-        if (!is_device_ptr(ids)) {
-            ti.ensure((size_t)n * 8);
-            HIPCHECK(hipMemcpyAsync(ti.p, ids, (size_t)n * 8, hipMemcpyHostToDevice, h->st));
-            dids = ti.as<int64_t>();
-        }
+        const int64_t* dids = stage_list_dest(h, h->h_base[(size_t)l] + pos0, n, ids, dest, ti);
         launch_scatter_rows(dx, dtype == RSX_F16, n, h->d, h->w_dest.as<int64_t>(), h->data.p, h->storage_f16, h->ld,
                             h->norms.p ? h->norms.as<float>() : nullptr, dids, 0, h->ids.as<int64_t>(), h->st);
         HIPCHECK(hipStreamSynchronize(h->st));
@@ -642,6 +730,11 @@ void save_impl(rsx_index* h, const char* path) {
         int64_t nc = (int64_t)h->h_centroids.size(), ncb = (int64_t)h->h_codebooks.size();
         wr(f, &nc, 8); wr(f, h->h_centroids.data(), (size_t)nc * 4);
         wr(f, &ncb, 8); wr(f, h->h_codebooks.data(), (size_t)ncb * 4);
+        if (h->kind == KIND_IVFSQ) {      // the kind's own record: qtype, by_residual, then the 2 d parameters (0 = untrained)
+            const int32_t rec[2] = {h->sq_qtype, h->by_residual ? 1 : 0};
+            const int64_t nsq = (int64_t)h->h_sq.size();
+            wr(f, rec, sizeof(rec)); wr(f, &nsq, 8); wr(f, h->h_sq.data(), (size_t)nsq * 4);
+        }
         std::vector<uint8_t> buf; std::vector<int64_t> ib;
         if (h->kind == KIND_FLAT) {
             // one list of ntotal rows, streamed in bounded chunks (a 10M x 768 index is 30 GB as fp32: no whole-index temporaries)
@@ -669,7 +762,7 @@ void save_impl(rsx_index* h, const char* path) {
             int64_t n = h->h_len[(size_t)l];
             wr(f, &n, 8);
             if (n == 0) continue;
-            size_t pb = (h->kind == KIND_IVFPQ) ? (size_t)n * h->M : (size_t)n * h->d * 4;
+            size_t pb = (h->kind == KIND_IVFPQ) ? (size_t)n * h->M : (h->kind == KIND_IVFSQ) ? (size_t)n * h->d : (size_t)n * h->d * 4;
             buf.resize(pb); ib.resize((size_t)n);
             get_list_impl(h, l, nullptr, buf.data(), ib.data());
             wr(f, buf.data(), pb);
@@ -687,7 +780,9 @@ rsx_index* load_impl(const char* path, int device) {
         FileHeader hd{};
         rd(f, &hd, sizeof(hd));
         if (memcmp(hd.magic, "RSX1", 4) != 0) RSX_THROW(RSX_ERR_IO, "%s is not an RSX1 index file", path);
-        h = hd.kind == 3 ? create_flat_pq(hd.d, hd.M, hd.nbits, hd.metric, device) : create_common(hd.kind, hd.d, hd.nlist, hd.M, hd.nbits, hd.metric, device);
+        if (hd.kind < 0 || hd.kind > 4) RSX_THROW(RSX_ERR_IO, "%s: unknown index kind %d", path, hd.kind);
+        h = hd.kind == 3 ? create_flat_pq(hd.d, hd.M, hd.nbits, hd.metric, device) : hd.kind == KIND_IVFSQ ? create_ivfsq(hd.d, hd.nlist, 0, hd.metric, 1, device)
+                         : create_common(hd.kind, hd.d, hd.nlist, hd.M, hd.nbits, hd.metric, device);
         h->nprobe = hd.nprobe;
         FileHeaderV2 h2{0, 1, 0};
         if (hd.version >= 2) rd(f, &h2, sizeof(h2));
@@ -698,13 +793,22 @@ rsx_index* load_impl(const char* path, int device) {
         std::vector<float> cb((size_t)ncb); rd(f, cb.data(), (size_t)ncb * 4);
         if (nc) { if (nc != (int64_t)h->nlist * h->d) RSX_THROW(RSX_ERR_IO, "bad centroid block"); set_centroids(h, c.data()); }
         if (ncb) { if (ncb != (int64_t)h->M * 256 * h->dsub) RSX_THROW(RSX_ERR_IO, "bad codebook block"); set_codebooks(h, cb.data()); }
+        if (h->kind == KIND_IVFSQ) {
+            int32_t rec[2] = {0, 0}; int64_t nsq = 0;
+            rd(f, rec, sizeof(rec)); rd(f, &nsq, 8);
+            if (rec[0] != 0) RSX_THROW(RSX_ERR_IO, "scalar-quantiser record: unknown qtype %d", rec[0]);
+            if (nsq != 0 && nsq != (int64_t)2 * h->d) RSX_THROW(RSX_ERR_IO, "bad scalar-quantiser block");
+            h->by_residual = rec[1] != 0;
+            std::vector<float> sqv((size_t)nsq); rd(f, sqv.data(), (size_t)nsq * 4);
+            if (nsq) set_sq_trained(h, sqv.data());
+        }
         update_trained(h);
         std::vector<int64_t> lens((size_t)h->nlist);
         long dir_pos = ftell(f);
         // first pass: list sizes (to reserve exactly)
         for (int l = 0; l < h->nlist; l++) {
             int64_t n = 0; rd(f, &n, 8); lens[(size_t)l] = n;
-            size_t pb = (h->kind == KIND_IVFPQ) ? (size_t)n * h->M : (size_t)n * h->d * 4;
+            size_t pb = (h->kind == KIND_IVFPQ) ? (size_t)n * h->M : (h->kind == KIND_IVFSQ) ? (size_t)n * h->d : (size_t)n * h->d * 4;
             if (n && fseek(f, (long)(pb + (size_t)n * 8), SEEK_CUR) != 0) RSX_THROW(RSX_ERR_IO, "seek failed");
         }
         fseek(f, dir_pos, SEEK_SET);
@@ -733,7 +837,7 @@ rsx_index* load_impl(const char* path, int device) {
         for (int l = 0; l < h->nlist; l++) {
             int64_t n = 0; rd(f, &n, 8);
             if (n == 0) continue;
-            size_t pb = (h->kind == KIND_IVFPQ) ? (size_t)n * h->M : (size_t)n * h->d * 4;
+            size_t pb = (h->kind == KIND_IVFPQ) ? (size_t)n * h->M : (h->kind == KIND_IVFSQ) ? (size_t)n * h->d : (size_t)n * h->d * 4;
             buf.resize(pb); ib.resize((size_t)n);
             rd(f, buf.data(), pb); rd(f, ib.data(), (size_t)n * 8);
             add_list_impl(h, l, n, buf.data(), RSX_F32, ib.data());

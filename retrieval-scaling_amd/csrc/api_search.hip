@@ -386,6 +386,14 @@ static void fork_side_tables(rsx_index* h, const BatchPlan& P) {
                    h->w_lut8.as<uint8_t>(), h->w_qparam.p, h->w_lutws.p, P.sliced ? 2 : P.rot ? 1 : 0, h->st2, h->metric, 1, lut32_out(h, P));
     HIPCHECK(hipEventRecord(h->ev_lut, h->st2));
 }
+// >= the largest centroid norm (certificate term of a by_residual scalar-quantiser index), once per centroid set
+static float sq_cent_cmax(rsx_index* h) {
+    if (h->sq_cmax_gen == h->cent_gen) return h->sq_cmax;
+    double mx = 0.0;
+    for (int l = 0; l < h->nlist; l++) { double n2 = 0.0; for (int t = 0; t < h->d; t++) { const double v = h->h_centroids[(size_t)l * h->d + t]; n2 += v * v; } mx = std::max(mx, n2); }
+    h->sq_cmax = (float)(std::sqrt(mx) * 1.000001); h->sq_cmax_gen = h->cent_gen;
+    return h->sq_cmax;
+}
 static FinalizeArgs finalize_args(rsx_index* h, const BatchPlan& P, float* dD, int64_t* dI) {
     const int d = h->d, ld = h->ld;
     FinalizeArgs fa{};
@@ -411,6 +419,32 @@ static FinalizeArgs finalize_args(rsx_index* h, const BatchPlan& P, float* dD, i
         fa.cert_rel = ((float)d + 2.0f) * u24 * 1.01f + (h->storage_f16 ? 0.0f : u11 * 1.002f);
         fa.cert_rel_qlossy = u11 * 1.002f + u11 * u11; fa.cert_qflag = h->w_flag.as<int>();
         fa.cert_abs = sqrtf((float)d) * u24 + (h->metric == RSX_METRIC_L2 ? ((float)d + 4.0f) * u24 * xmax : 0.0f);
+    }
+    if (h->kind == KIND_IVFSQ) {
+        fa.sq = SqRows{h->data.as<uint8_t>(), h->d_sq.as<float>(), h->by_residual ? h->d_centroids.as<float>() : nullptr, h->d_base.as<int64_t>(), h->nlist};
+        fa.X = nullptr;
+        if (P.certify) {
+            // The scan's score of a stored vector x^ (k_sq_list_scan) is  (sum_j (hi_j + lo_j) b_j) / s + const_q (+ <q, c_l>) (+ -|x^|^2/2)
+            // with b_j = code_j - 128, q'_j = q_j vdiff_j / 255, (hi, lo) the fp16 split of q' s, const_q = sum_j q_j vmin_j + 128.5 sum_j q'_j;
+            // the exact score is the fp64 product of q with x^_j = fl(c_lj + fl(vmin_j + fl(vdiff_j fl((code_j + 0.5) / 255)))).  Per unit of |q|,
+            // with r = max_j vdiff_j / 255 (|q'| <= r |q|), B = the largest |b| of a stored row (tracked by the encoder), V = |vdiff|, W = |vmin|,
+            // C = the largest centroid norm, X = the largest |x^| (Cauchy-Schwarz: sum_j |q'_j b_j| <= |q'| B):
+            //   fp32 accumulation of the 2 ld products of a row (hi and lo)               (2 d + 2) 2^-24 r B
+            //   the split: |q' s - hi - lo| <= 2^-22 |q' s|                                2^-21 r B        (2^-22 (1 + 2^-11), rounded up)
+            //   ... or <= 2^-14 where a half is below the fp16 normal range (s puts the largest |q'_j| at >= 2^13)   sqrt(d) 2^-27 r B
+            //   q' itself: two fp32 roundings                                              2 2^-24 r B
+            //   the decode's three roundings (|x^_j - its real-number value| <= 2^-24 (3 |vdiff_j| + |vmin_j|)), const_q rounded to fp32
+            //   (|const_q| <= |q| (W + V)), the three fp32 operations that assemble the score  10 2^-24 (V + W)
+            //   by_residual: the coarse score <q, c_l> is a chain of d fp32 fmaf, it enters two of those operations, and c + r^ is rounded   2^-24 ((d + 4) C + 2 X)
+            // No term for the queries' own precision: the factors come from the fp32 queries.  cert_abs (the score's own fp32 rounding, the L2
+            // norm term) stays as for stored rows.  tests/sq_ref.py restates this bound (cert_eps) for the host-side precondition test.
+            const float u24 = 5.9604645e-8f, fd = (float)d;
+            const float rel_b = ((2.0f * fd + 2.0f) * u24 + 4.76837158e-7f + sqrtf(fd) * 7.4505806e-9f + 2.0f * u24) * 1.01f;
+            const float rB = (h->sq_vdmax / 255.0f) * sqrtf((float)h->sq_bn2) * 1.00001f;
+            float cq = rel_b * rB + 10.0f * u24 * 1.01f * (h->sq_nvdiff + h->sq_nvmin);
+            if (h->by_residual) cq += u24 * 1.01f * ((fd + 4.0f) * sq_cent_cmax(h) + 2.0f * fa.cert_xmax);
+            fa.cert_rel = 0.0f; fa.cert_rel_qlossy = 0.0f; fa.cert_q = cq;
+        }
     }
     return fa;
 }
@@ -987,10 +1021,15 @@ static void pq_scan(rsx_index* h, const BatchPlan& P, BatchResult& R, StageTimer
 // exact mode (see the Flat path): fp64 scores of every row of the probed lists into the score rows
 static void ivf_flat_exact(rsx_index* h, const BatchPlan& P, StageTimer& tm) {
     ExactScoreArgs ea{};
-    ea.kind = KIND_IVFFLAT; ea.metric = h->metric; ea.nq = P.nq; ea.Q32 = h->w_q32.as<float>(); ea.ldq = h->ld; ea.d = h->d;
+    ea.kind = h->kind; ea.metric = h->metric; ea.nq = P.nq; ea.Q32 = h->w_q32.as<float>(); ea.ldq = h->ld; ea.d = h->d;
     ea.X = h->data.p; ea.x_f16 = h->storage_f16; ea.ld = h->ld; ea.temp = h->w_temp.as<float>(); ea.tstride = P.tmax;
     ea.probe_list = h->w_probelist.as<int32_t>(); ea.seg_start = h->w_segstart.as<int64_t>(); ea.nprobe = P.nprobe;
     ea.list_base = h->d_base.as<int64_t>(); ea.list_len = h->d_len.as<int64_t>();
+    if (h->kind == KIND_IVFSQ) {      // the same fp64 scores against the decoded rows
+        ea.X = nullptr;
+        ea.sq = SqRows{h->data.as<uint8_t>(), h->d_sq.as<float>(), h->by_residual ? h->d_centroids.as<float>() : nullptr, h->d_base.as<int64_t>(), h->nlist};
+        launch_sq_exact_scores(ea, h->st);
+    } else
     launch_exact_scores(ea, h->st);
     tm.mark("scan");
 }
@@ -1026,6 +1065,7 @@ static bool ivf_flat_filtered(rsx_index* h, const BatchPlan& P, BatchResult& R, 
     }
     pr.group(h, 16, 0, pre_lists, 0, h->st);       // ... the closest list(s) only
     launch_list_scan(a, h->st);
+    if (a.sq_codes) h->timing["ivfsq_scan_launches"] += 1;
     tm.mark("scan0");
     R.cand_cap = alloc_cand_rows(h, P, 0);
     // the pre-pass is only a threshold (see the IVF-PQ path): the K'-th key, candidate counters reset
@@ -1047,6 +1087,7 @@ static bool ivf_flat_filtered(rsx_index* h, const BatchPlan& P, BatchResult& R, 
     a.tau_key = state + (KP - 1); a.tau_stride = KP;
     a.cand = h->w_cand.as<uint64_t>(); a.cand_cnt = h->w_candcnt.as<unsigned long long>(); a.cand_cap = R.cand_cap;
     launch_list_scan(a, h->st);
+    if (a.sq_codes) h->timing["ivfsq_scan_launches"] += 1;
     tm.mark("scan");
     std::vector<unsigned long long> cnts((size_t)nq * CCS);
     HIPCHECK(hipMemcpyAsync(cnts.data(), h->w_candcnt.p, (size_t)nq * 8 * CCS, hipMemcpyDeviceToHost, h->st));
@@ -1127,6 +1168,47 @@ static void ivf_flat_scan(rsx_index* h, const BatchPlan& P, BatchResult& R, Stag
         tm.mark("scan");
     }
 }
+// KIND_IVFSQ: the same stages over rows of code bytes (k_sq.hip).  The batch's query factors first (k_sq_query_factors), then ivf_flat_scan's
+// grouping and, where the filter applies, ivf_flat_filtered's threshold pre-pass and candidate rows — with k_sq_list_scan behind
+// launch_list_scan.  Two group forms: 16 probing queries (four waves, 512 rows per work item) and 64 (eight waves, 1024 rows), chosen as
+// for IVF-Flat from the probing queries per list; "ivf_qtiles" 0 forces 16, >= 2 forces 64.  "scan_chunk" does not apply to this kind.
+static void ivf_sq_scan(rsx_index* h, const BatchPlan& P, BatchResult& R, StageTimer& tm) {
+    const int64_t nq = P.nq, npairs = nq * P.nprobe; const int nlist = h->nlist, nprobe = P.nprobe, ld = h->ld;
+    h->w_sqhi.ensure((size_t)nq * ld * 2); h->w_sqlo.ensure((size_t)nq * ld * 2); h->w_sqc.ensure((size_t)nq * 8);
+    launch_sq_query_factors(h->w_q32.as<float>(), ld, nq, nq, h->d, ld, h->d_sq.as<float>(), h->w_sqhi.as<__half>(), h->w_sqlo.as<__half>(),
+                            h->w_sqc.as<float>(), h->st);
+    tm.mark("sq_factors");
+    const PairArea pr(h, nq, nprobe, nlist);
+    const int64_t qpl = npairs / std::max(1, nlist);
+    const int ls_qt = h->ivf_qtiles == 0 ? 1 : h->ivf_qtiles > 1 ? 4 : (qpl >= 12 ? 4 : 1);
+    const int base_rows = sq_list_scan_chunk_rows(1), item_rows = sq_list_scan_chunk_rows(ls_qt);
+    pr.group(h, 16 * ls_qt, item_rows, nprobe, 0, h->st);
+    tm.mark("group");
+    ListScanArgs a{};
+    a.ld = ld; a.sq_codes = h->data.as<uint8_t>(); a.sq_qhi = h->w_sqhi.as<__half>(); a.sq_qlo = h->w_sqlo.as<__half>(); a.sq_qc = h->w_sqc.as<float>();
+    a.sq_dis0 = h->by_residual ? h->w_dis0.as<float>() : nullptr;
+    a.bias = h->metric == RSX_METRIC_L2 ? h->w_misc.as<float>() : nullptr;
+    a.list_base = h->d_base.as<int64_t>(); a.list_len = h->d_len.as<int64_t>();
+    a.pairs_sorted = pr.pairs_sorted; a.pair_off = pr.pair_off; a.group_off = pr.group_off; a.total_groups = pr.total_groups;
+    a.probe_list = h->w_probelist.as<int32_t>(); a.seg_start = h->w_segstart.as<int64_t>();
+    a.nlist = nlist; a.nprobe = nprobe; a.flat_mode = 0; a.nq = (int)nq;
+    a.temp = h->w_temp.as<float>(); a.tstride = P.tmax;
+    a.max_groups = (int)std::min<int64_t>(npairs, npairs / 16 + std::min<int64_t>(nlist, npairs));
+    a.chunk_rows = base_rows; a.qtiles = ls_qt;
+    a.max_chunks = (int)std::max<int64_t>(1, (P.maxlen + base_rows - 1) / base_rows);
+    const int64_t pre_chunks = std::max<int64_t>(1, ((int64_t)P.KP * std::max(1, h->ivf_pre_mult) + base_rows - 1) / base_rows);
+    const bool want_filter = P.ivf_filter != 0 && nprobe > 1 && pre_chunks <= 32 && (P.ivf_filter > 1 || nq * P.tmax >= (int64_t)500000000);
+    if (want_filter) R.filtered = ivf_flat_filtered(h, P, R, a, pr, ls_qt, item_rows, pre_chunks, tm);
+    if (!R.filtered) {
+        a.chunk_rows = item_rows; a.qtiles = ls_qt;
+        a.max_chunks = (int)std::max<int64_t>(1, (P.maxlen + item_rows - 1) / item_rows);
+        // (after a filtered attempt the grouping in place is the filtered scan's: the same groups and items)
+        a.item_off = pr.item_off; a.total_items = pr.total_items; a.max_items = (int)max_scan_items(h, nq, nprobe, 16 * ls_qt, item_rows);
+        launch_list_scan(a, h->st);
+        h->timing["ivfsq_scan_launches"] += 1;
+        tm.mark("scan");
+    }
+}
 // per-query k-selection over the score rows (after a filtered search's selector mask) or the candidate rows
 static void select_stage(rsx_index* h, const BatchPlan& P, const BatchResult& R, StageTimer& tm) {
     const int64_t nq = P.nq; uint64_t* state = h->w_state.as<uint64_t>();
@@ -1153,7 +1235,7 @@ static void select_stage(rsx_index* h, const BatchPlan& P, const BatchResult& R,
         // fast scan: the certificate needs the TRUE top-K' by approximate score, so the selection threshold
         // is the K'-th key, not the k-th
         select_rows(h, h->w_temp.as<float>(), P.tmax, h->w_segstart.as<int64_t>() + P.nprobe, P.nprobe + 1, P.tmax, 0, nq, P.KP, P.BUF,
-                    (P.fast || h->kind == KIND_IVFFLAT) ? P.KP : P.k, state, false);
+                    (P.fast || h->kind == KIND_IVFFLAT || h->kind == KIND_IVFSQ) ? P.KP : P.k, state, false);
     }
     tm.mark("select");
     if (R.filtered && h->profile >= 2) {   // diagnostics: keys that passed the in-kernel filter
@@ -1269,6 +1351,7 @@ static void search_batch(rsx_index* h, int64_t nq, const void* dq, int dtype, in
     BatchResult R;
     if (h->kind == KIND_IVFPQ) pq_scan(h, P, R, tm);
     else if (!allow_fast) ivf_flat_exact(h, P, tm);
+    else if (h->kind == KIND_IVFSQ) ivf_sq_scan(h, P, R, tm);
     else ivf_flat_scan(h, P, R, tm);
     select_stage(h, P, R, tm);
     finalize_stage(h, P, R, fa, tm);

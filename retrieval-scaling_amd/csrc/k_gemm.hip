@@ -1332,6 +1332,7 @@ int list_scan2_max_qtiles(int ld) {
 
 void launch_list_scan(const ListScanArgs& a, hipStream_t st) {
     if (a.max_groups <= 0 || a.max_chunks <= 0) return;
+    if (a.sq_codes) { launch_sq_list_scan(a, st); return; }      // rows of scalar-quantiser codes: k_sq.hip
     dim3 grid((unsigned)a.max_groups, (unsigned)a.max_chunks);
     const int base_rows = list_scan2_chunk_rows(a.x_f16, a.ld);
     if (base_rows > 0 && (a.chunk_rows == base_rows || ((a.qtiles == 4 || a.qtiles == 8) && a.chunk_rows == 2 * base_rows))) {

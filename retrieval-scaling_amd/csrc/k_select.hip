@@ -11,6 +11,7 @@
 // heap_reorder; and src/search.py:362-367 (multi-shard merge).
 #include "rsx_internal.h"
 #include "k_rescore.h"
+#include "k_sq.h"
 
 namespace rsx {
 
@@ -1485,6 +1486,8 @@ __device__ inline float pq_exact_sum_rot_wide(const uint8_t* codes, int64_t row,
     return sum;
 }
 
+// SQ: the candidates' rows are scalar-quantiser codes, decoded by the re-score (k_sq.h); everything else is the stored-row form's
+template <bool SQ>
 __global__ __launch_bounds__(1024) void k_finalize(FinalizeArgs a) {
     extern __shared__ __attribute__((aligned(16))) uint64_t fin_buf[];
     const int KP = a.KP;
@@ -1616,7 +1619,8 @@ __global__ __launch_bounds__(1024) void k_finalize(FinalizeArgs a) {
     }
     // exact re-score of the candidates' storage rows (k_rescore.h; shared with k_refine)
     auto rescore = [&](int c_lo, int c_hi) {
-        rescore_rows(a.X, a.x_f16, a.ld, a.d, a.metric, a.Q32 + q * a.ldq, a.ldq, INT64_MAX, srow, sord, c_lo, c_hi, lane, wv, nwv);
+        if (SQ) rescore_rows_sq(a.sq, a.ld, a.d, a.metric, a.Q32 + q * a.ldq, srow, sord, c_lo, c_hi, lane, wv, nwv);
+        else rescore_rows(a.X, a.x_f16, a.ld, a.d, a.metric, a.Q32 + q * a.ldq, a.ldq, INT64_MAX, srow, sord, c_lo, c_hi, lane, wv, nwv);
     };
     if (a.kind != KIND_IVFPQ) rescore(0, KPv);
 
@@ -1663,7 +1667,7 @@ __global__ __launch_bounds__(1024) void k_finalize(FinalizeArgs a) {
                 if (last != 0) {     // K' candidates were kept: vectors were excluded on their approximate score
                     const float qn = (float)sqrt(q2) * 1.0000002f;
                     const float rel = a.cert_rel + ((a.cert_qflag && *a.cert_qflag) ? a.cert_rel_qlossy : 0.0f);
-                    const float eps = rel * qn * a.cert_xmax + a.cert_abs * (qn + a.cert_xmax);
+                    const float eps = rel * qn * a.cert_xmax + a.cert_abs * (qn + a.cert_xmax) + (SQ ? a.cert_q * qn : 0.0f);
                     const float a_last = key_score(last);
                     const bool have_k = sord[a.k - 1] != 0 && sid[a.k - 1] != INT64_MAX;
                     const float s_k = have_k ? ord2f(sord[a.k - 1]) : -__builtin_inff();
@@ -2376,8 +2380,14 @@ void launch_finalize(const FinalizeArgs& a0, hipStream_t st) {
         shm = probe_end;
     }
     static DevSize big;
-    if (shm > 48 * 1024) big.grow(shm, [&] { hipFuncSetAttribute((const void*)k_finalize, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm); });
-    hipLaunchKernelGGL(k_finalize, dim3((unsigned)a.nq), dim3(64 * waves), shm, st, a);
+    if (a.kind == KIND_IVFSQ) {
+        static DevSize big_sq;
+        if (shm > 48 * 1024) big_sq.grow(shm, [&] { hipFuncSetAttribute((const void*)k_finalize<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm); });
+        hipLaunchKernelGGL(k_finalize<true>, dim3((unsigned)a.nq), dim3(64 * waves), shm, st, a);
+        return;
+    }
+    if (shm > 48 * 1024) big.grow(shm, [&] { hipFuncSetAttribute((const void*)k_finalize<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm); });
+    hipLaunchKernelGGL(k_finalize<false>, dim3((unsigned)a.nq), dim3(64 * waves), shm, st, a);
 }
 
 // ---------------------------------------------------------------------------------------

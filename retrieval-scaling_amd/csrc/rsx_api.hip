@@ -35,6 +35,7 @@ static int search_prepass_common(rsx_index_t* h, int64_t nq, const void* q, int 
         if (dtype != RSX_F32 && dtype != RSX_F16) RSX_THROW(RSX_ERR_INVALID, "bad dtype %d", dtype);
         if (nprobe_override < 0) RSX_THROW(RSX_ERR_INVALID, "nprobe override must be positive or 0 (got %d)", nprobe_override);
         if (sel) refuse_flat_pq(h, RSX_ERR_UNSUPPORTED, "search with a selector (FAISS 1.8.0 IndexPQ::search takes no search parameters)");
+        refuse_ivfsq(h, "search_prepass (the two-call search)");
         if (is_sharded(h)) RSX_THROW(RSX_ERR_UNSUPPORTED, "search_prepass: not available on a sharded handle (its shards share one process)");
         if (nq > h->query_batch) RSX_THROW(RSX_ERR_UNSUPPORTED, "search_prepass: nq = %lld exceeds query_batch = %d (one internal batch per two-call search)", (long long)nq, h->query_batch);
         if (!h->tc) h->tc.reset(new rsx_index::TwoCall());
@@ -66,7 +67,7 @@ static int search_prepass_common(rsx_index_t* h, int64_t nq, const void* q, int 
 extern "C" {
 
 const char* rsx_last_error(void) { return g_err.c_str(); }
-int rsx_version(void) { return 1004; }     // 1001: filtered search (rsx_selector_*, rsx_search_sel, rsx_search_prepass_sel); 1002: rsx_remove_ids; 1003: rsx_pq_create; 1004: rsx_refine
+int rsx_version(void) { return 1005; }     // 1001: filtered search (rsx_selector_*, rsx_search_sel, rsx_search_prepass_sel); 1002: rsx_remove_ids; 1003: rsx_pq_create; 1004: rsx_refine; 1005: rsx_ivfsq_create
 
 int rsx_device_count(int* n) {
     return guarded([&] {
@@ -90,9 +91,13 @@ int rsx_ivfpq_create(int d, int nlist, int M, int nbits, int metric, int device,
 int rsx_pq_create(int d, int M, int nbits, int metric, int device, rsx_index_t** out) {
     return guarded([&] { if (!out) RSX_THROW(RSX_ERR_INVALID, "null out"); *out = create_flat_pq(d, M, nbits, metric, device); });
 }
+int rsx_ivfsq_create(int d, int nlist, int qtype, int metric, int by_residual, int device, rsx_index_t** out) {
+    return guarded([&] { if (!out) RSX_THROW(RSX_ERR_INVALID, "null out"); *out = create_ivfsq(d, nlist, qtype, metric, by_residual, device); });
+}
 int rsx_sharded_create(int kind, int d, int nlist, int M, int nbits, int metric, int ndev, const int* devices, rsx_index_t** out) {
     return guarded([&] {
         if (!out) RSX_THROW(RSX_ERR_INVALID, "null out");
+        if (kind == RSX_KIND_IVFSQ) RSX_THROW(RSX_ERR_UNSUPPORTED, "sharded_create: IndexIVFScalarQuantizer (kind 4) has no sharded form in this build");
         if (kind == RSX_KIND_PQ) RSX_THROW(RSX_ERR_UNSUPPORTED, "sharded_create: IndexPQ (kind 3) has no sharded form in this build");
         if (kind != KIND_FLAT && kind != KIND_IVFFLAT && kind != KIND_IVFPQ) RSX_THROW(RSX_ERR_INVALID, "unknown index kind %d", kind);
         *out = sharded_create(kind, d, nlist, M, nbits, metric, ndev, devices);
@@ -166,6 +171,23 @@ int rsx_set_codebooks(rsx_index_t* h, const float* c) {
             return;
         }
         use_device(h); set_codebooks(h, c); update_trained(h);
+    });
+}
+int rsx_set_sq_trained(rsx_index_t* h, const float* t) {
+    return guarded([&] {
+        if (!h || !t) RSX_THROW(RSX_ERR_INVALID, "null pointer");
+        refuse_while_two_call(h, "set_sq_trained");
+        if (h->kind != KIND_IVFSQ) RSX_THROW(RSX_ERR_INVALID, "only an IndexIVFScalarQuantizer handle (kind 4) has scalar-quantiser parameters");
+        if (h->ntotal) RSX_THROW(RSX_ERR_INVALID, "cannot replace the scalar-quantiser parameters of a populated index");
+        use_device(h); set_sq_trained(h, t); update_trained(h);
+    });
+}
+int rsx_get_sq_trained(rsx_index_t* h, float* out) {
+    return guarded([&] {
+        if (!h || !out) RSX_THROW(RSX_ERR_INVALID, "null pointer");
+        if (h->kind != KIND_IVFSQ) RSX_THROW(RSX_ERR_INVALID, "only an IndexIVFScalarQuantizer handle (kind 4) has scalar-quantiser parameters");
+        if (h->h_sq.empty()) RSX_THROW(RSX_ERR_NOT_TRAINED, "no scalar-quantiser parameters");
+        memcpy(out, h->h_sq.data(), h->h_sq.size() * 4);
     });
 }
 int rsx_get_centroids(rsx_index_t* h, float* out) {
@@ -332,6 +354,7 @@ int rsx_search_sel(rsx_index_t* h, int64_t nq, const void* q, int dtype, int k, 
         if (dtype != RSX_F32 && dtype != RSX_F16) RSX_THROW(RSX_ERR_INVALID, "bad dtype %d", dtype);
         if (nprobe_override < 0) RSX_THROW(RSX_ERR_INVALID, "nprobe override must be positive or 0 (got %d)", nprobe_override);
         if (sel) refuse_flat_pq(h, RSX_ERR_UNSUPPORTED, "search with a selector (FAISS 1.8.0 IndexPQ::search takes no search parameters)");
+        if (sel) refuse_ivfsq(h, "search with a selector");
         SelScope sc(h, sel, h->flat_pq ? 0 : nprobe_override);
         if (is_sharded(h)) {
             if (!h->trained) RSX_THROW(RSX_ERR_NOT_TRAINED, "search before train");
@@ -364,6 +387,7 @@ int rsx_remove_ids(rsx_index_t* h, const rsx_selector_t* sel, int64_t* nremoved)
         if (!h || !sel || !nremoved) RSX_THROW(RSX_ERR_INVALID, "null pointer");
         refuse_while_two_call(h, "remove_ids");
         refuse_flat_pq(h, RSX_ERR_UNSUPPORTED, "remove_ids");
+        refuse_ivfsq(h, "remove_ids");
         *nremoved = 0;
         if (is_sharded(h)) { *nremoved = sharded_remove(h, sel); return; }
         use_device(h);
@@ -512,8 +536,10 @@ int rsx_get(rsx_index_t* h, const char* key, int64_t* out) {
         else if (s == "nbits") *out = h->nbits;
         else if (s == "kind") *out = public_kind(h);
         else if (s == "metric") *out = h->metric;
-        else if (s == "storage_dtype") *out = (h->kind == KIND_IVFPQ) ? -1 : (h->storage_f16 ? RSX_F16 : RSX_F32);
-        else if (s == "code_size") *out = (h->kind == KIND_IVFPQ) ? h->M : (int64_t)h->d * (h->storage_f16 ? 2 : 4);
+        else if (s == "storage_dtype") *out = (h->kind == KIND_IVFPQ || h->kind == KIND_IVFSQ) ? -1 : (h->storage_f16 ? RSX_F16 : RSX_F32);
+        else if (s == "code_size") *out = (h->kind == KIND_IVFPQ) ? h->M : (h->kind == KIND_IVFSQ) ? h->d : (int64_t)h->d * (h->storage_f16 ? 2 : 4);
+        else if (s == "qtype" && h->kind == KIND_IVFSQ) *out = h->sq_qtype;
+        else if (s == "by_residual" && h->kind == KIND_IVFSQ) *out = h->by_residual ? 1 : 0;
         else if (s == "device") *out = h->device;
         else if (s == "max_k") *out = 4096;
         else if (s == "query_batch") *out = h->query_batch;
@@ -533,7 +559,7 @@ int rsx_set_param(rsx_index_t* h, const char* key, double value) {
             return;
         }
         if (s == "query_batch") h->query_batch = std::max(1, (int)value);
-        else if (s == "scan_chunk") h->scan_chunk = std::max(0, (int)value);
+        else if (s == "scan_chunk") { refuse_ivfsq(h, "scan_chunk (the code-row scan has its own work items)"); h->scan_chunk = std::max(0, (int)value); }
         else if (s == "scan_kernel") h->scan_kernel = (int)value;
         else if (s == "pq_fast") h->pq_fast = (int)value;
         else if (s == "pq_fast_kp") h->pq_fast_kp = std::min(4096, std::max(0, (int)value));     // k_finalize sorts K' <= 4096 candidates in LDS

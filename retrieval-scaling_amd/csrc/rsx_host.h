@@ -183,6 +183,16 @@ struct rsx_index {
     // layouts, encoder, table builders, finalize and the RSX1 writer are shared; residual = x - 0 = x, dis0 = <q, 0> = +0) that reports
     // kind 3, refuses what a flat index has not, and searches through the staged filtered scan (api_search.hip: pq_staged_scan)
     bool flat_pq = false;
+    // KIND_IVFSQ (faiss.IndexIVFScalarQuantizer, QT_8bit; rsx_ivfsq_create): rows of ld code bytes in the IVF-Flat directory, ids
+    // and (L2) norm terms of the DECODED vectors beside them; sq_trained = vmin[d] then vdiff[d]; max_norm2 is over the decoded vectors
+    int sq_qtype = 0; bool by_residual = false;
+    std::vector<float> h_sq; DevBuf d_sq;
+    float sq_nvmin = 0.0f, sq_nvdiff = 0.0f;      // >= the L2 norms of vmin / vdiff (certificate terms, with the parameters)
+    float sq_vdmax = 0.0f;                        // the largest vdiff_j
+    unsigned int sq_bn2 = 0;                      // the largest sum_j (code_j - 128)^2 of a row ever stored (with max_norm2).  Like max_norm2 of the
+                                                  // row kinds, both survive rsx_reset: maxima over everything EVER stored — conservative for the certificate
+    float sq_cmax = 0.0f; uint64_t sq_cmax_gen = ~0ull;   // >= the largest centroid norm, of centroid set sq_cmax_gen (by_residual certificate term)
+    DevBuf w_sqhi, w_sqlo, w_sqc;                 // per-batch query factors (k_sq_query_factors)
     bool trained = false;
     int64_t ntotal = 0;
     hipStream_t st = nullptr;
@@ -312,7 +322,7 @@ struct rsx_index {
 
     // rows a list's storage starts on and grows by: 64-vector slabs of PQ codes — 512 (a slice-major group of 16 blocks) in the sliced layout
     int row_align() const { return kind == KIND_IVFPQ ? (CB == PQ_SLICED ? 32 * PQ_SLICED_GB : 64) : (kind == KIND_FLAT ? 128 : 64); }
-    size_t row_bytes() const { return kind == KIND_IVFPQ ? (size_t)Mpad : (size_t)ld * (storage_f16 ? 2 : 4); }
+    size_t row_bytes() const { return kind == KIND_IVFPQ ? (size_t)Mpad : kind == KIND_IVFSQ ? (size_t)ld : (size_t)ld * (storage_f16 ? 2 : 4); }
 };
 
 
@@ -347,9 +357,11 @@ void ensure_capacity(rsx_index* h, const std::vector<int64_t>& need, bool exact)
 const void* stage_rows(rsx_index* h, DevBuf& buf, const void* x, int64_t n, int d, int dtype);
 void set_centroids(rsx_index* h, const float* c);
 void set_codebooks(rsx_index* h, const float* c);
+void set_sq_trained(rsx_index* h, const float* t);
 void update_trained(rsx_index* h);
 rsx_index* create_common(int kind, int d, int nlist, int M, int nbits, int metric, int device);
 rsx_index* create_flat_pq(int d, int M, int nbits, int metric, int device);
+rsx_index* create_ivfsq(int d, int nlist, int qtype, int metric, int by_residual, int device);
 void add_all(rsx_index* h, int64_t n, const void* x, int dtype, const int64_t* ids);
 void train_impl(rsx_index* h, int64_t n, const void* x, int dtype);
 void search_impl(rsx_index* h, int64_t nq, const void* q, int dtype, int k, float* D, int64_t* I);
@@ -389,6 +401,10 @@ void launch_rm_flat_chunk(const uint32_t* mask, const int32_t* word_pre, const i
 }  // namespace rsx
 
 static inline bool is_sharded(const rsx_index* h) { return !h->shards.empty(); }
+// what this build does not offer on an IndexIVFScalarQuantizer handle: the message names the kind, the handle stays untouched
+static inline void refuse_ivfsq(const rsx_index* h, const char* what) {
+    if (h && h->kind == KIND_IVFSQ) RSX_THROW(RSX_ERR_UNSUPPORTED, "%s: not available on an IndexIVFScalarQuantizer handle (kind 4) in this build", what);
+}
 static inline int public_kind(const rsx_index* h) { return h->flat_pq ? 3 : h->kind; }      // rsx_kind as callers and files see it
 
 template <typename F>

@@ -32,7 +32,14 @@ __device__ inline uint64_t make_key(float s, uint32_t idx) {
 __host__ __device__ inline uint32_t key_idx(uint64_t k) { return 0xFFFFFFFFu - (uint32_t)(k & 0xFFFFFFFFull); }
 __host__ __device__ inline float key_score(uint64_t k) { return ord2f((uint32_t)(k >> 32)); }
 
-enum { KIND_FLAT = 0, KIND_IVFFLAT = 1, KIND_IVFPQ = 2 };
+enum { KIND_FLAT = 0, KIND_IVFFLAT = 1, KIND_IVFPQ = 2, KIND_IVFSQ = 4 };     // (3 = RSX_KIND_PQ is a public kind only: rsx_index::flat_pq)
+
+// IVF scalar-quantiser rows (KIND_IVFSQ, k_sq.hip): a stored row is ld bytes, byte j < d the QT_8bit code of dimension j.
+// trained = vmin[d] then vdiff[d]; centroids non-null = by_residual (the decoded residual is added to the centroid of the row's list).
+struct SqRows {
+    const uint8_t* codes; const float* trained; const float* centroids;
+    const int64_t* list_base; int nlist;          // the list directory: a candidate's list is found from its storage row (by_residual)
+};
 
 // Environment switches between kernel generations / cost-split variants exist ONLY in the -DRSX_MEASURE build that tools/ load
 // through RSX_LIB (csrc/Makefile: librsx_measure.so).  In the shipped librsx.so this is the constant `dflt`: no environment
@@ -266,6 +273,10 @@ struct ListScanArgs {
     // unfiltered k_list_scan2, optional: the scores of (query q, probe rank j) go to temp[q * tstride + j * pre_stride + row] instead of
     // the query's concatenated row (threshold pre-pass over the first rows of several lists: every list gets its own slice)
     int64_t pre_stride;
+    // KIND_IVFSQ (sq_codes != null: launch_list_scan hands the launch to k_sq_list_scan, k_sq.hip): X / Q16 are unused, the rows are ld code
+    // bytes, the queries the scaled factors q' = q vdiff / 255 split into two fp16 halves, and a score is
+    //   acc * sq_qc[2 q] + sq_qc[2 q + 1] (+ sq_dis0[q * nprobe + j], by_residual) (+ bias[row], L2)
+    const uint8_t* sq_codes; const __half* sq_qhi; const __half* sq_qlo; const float* sq_qc; const float* sq_dis0;
 };
 int list_scan2_chunk_rows(int x_f16, int ld);   // work-item rows of the LDS-DMA list scan, 0 if it does not apply
 int list_scan2_max_qtiles(int ld);              // ... and the 16-query tiles per group its LDS holds
@@ -693,6 +704,8 @@ struct FinalizeArgs {
     int probe_lds_off;             // set by launch_finalize: byte offset of the query's probe table in the dynamic LDS (0 = keep it in global memory)
     int par_entries;               // set by launch_finalize: parallel table-entry form of the IVF-PQ re-score (small batches)
     int rank_sort;                 // set by launch_finalize: order the candidates by counting (K' <= 1024) instead of a bitonic network
+    SqRows sq;                     // KIND_IVFSQ: the re-score decodes the candidates' code rows (k_sq.h: rescore_rows_sq) instead of reading X
+    float cert_q;                  // certificate: a further absolute term per unit of |q| (0 for stored rows)
 };
 void launch_finalize(const FinalizeArgs& a, hipStream_t st);
 // out[row * M + m] = the code of (storage row, sub-quantiser m) for every row < nrows of a rotated / sliced layout (M % 16 == 0, M >= 32)
@@ -714,8 +727,28 @@ struct ExactScoreArgs {
     const void* X; int x_f16; int ld; int64_t flat_n;
     const int32_t* probe_list; const int64_t* seg_start; int nprobe; const int64_t* list_base; const int64_t* list_len;
     float* temp; int64_t tstride;
+    SqRows sq;                     // KIND_IVFSQ (launch_sq_exact_scores)
 };
 void launch_exact_scores(const ExactScoreArgs& a, hipStream_t st);
+
+// k_sq.hip — IVF scalar quantiser (QT_8bit)
+// per-dimension min / max of y over n rows (y = x, or the fp32 residual x - centroids[assign] when centroids != null); mnmx: [2 d] order
+// words (f2ord), initialised by the launch; the caller turns them into vmin / vdiff
+void launch_sq_minmax(const float* x, int64_t n, int d, const float* centroids, const int32_t* assign, uint32_t* mnmx, hipStream_t st);
+// codes of a batch into rows dest_row[i] (ld bytes each, padding zeroed); norms != null: |x^|^2 of the decoded row; maxnorm_bits: running
+// maximum of |x^|^2 (float bits, atomicMax)
+void launch_sq_encode(const void* x, int x_f16, int64_t n, int d, int ld, const float* trained, const float* centroids, const int32_t* assign,
+                      const int64_t* dest_row, uint8_t* codes, float* norms, unsigned int* maxnorm_bits, hipStream_t st);
+// the same norm terms for rows [row0, row0 + n) that hold imported codes (add_list); centroid: the list's, or null
+void launch_sq_norms(const uint8_t* codes, int64_t row0, int64_t n, int d, int ld, const float* trained, const float* centroid, float* norms,
+                     unsigned int* maxnorm_bits, hipStream_t st);
+// per-batch query factors: qhi / qlo [nq_pad, ld] (rows >= nq and columns >= d zero), qc [nq, 2] = {1 / scale, constant}
+void launch_sq_query_factors(const float* Q32, int ldq, int64_t nq, int64_t nq_pad, int d, int ld, const float* trained, __half* qhi, __half* qlo,
+                             float* qc, hipStream_t st);
+int sq_list_scan_chunk_rows(int qtiles);           // rows per work item of k_sq_list_scan for groups of 16 x qtiles queries (qtiles 1 or 4)
+void launch_sq_list_scan(const ListScanArgs& a, hipStream_t st);
+void launch_sq_exact_scores(const ExactScoreArgs& a, hipStream_t st);
+
 // any nshards x k with k <= 8192 (rounds of groups when nshards * k > 16384; stream-ordered round buffers); false: k too large or
 // no memory for the round buffers
 bool launch_merge_topk(int nshards, int64_t nq, int k, int metric, const float* D, const int64_t* I,

@@ -46,6 +46,7 @@ ABI_SYMBOLS = [
     "rsx_get_timing", "rsx_save", "rsx_load", "rsx_synth_vectors", "rsx_synth_queries",
     "rsx_selector_create", "rsx_selector_destroy", "rsx_selector_is_member", "rsx_search_sel", "rsx_search_prepass_sel",
     "rsx_remove_ids", "rsx_refine",
+    "rsx_ivfsq_create", "rsx_set_sq_trained", "rsx_get_sq_trained",
 ]
 
 
@@ -424,6 +425,8 @@ class Index:
 
     @property
     def storage_dtype(self):
+        if self._get("kind") == 4:
+            return "sq8"
         return {0: "float32", 1: "float16", -1: "pq"}[self._get("storage_dtype")]
 
     def set_param(self, key, value):
@@ -531,12 +534,14 @@ class Index:
 
     # -- inspection (parity tests, writer)
     def get_list(self, list_no=0):
-        """-> (payload, ids): IVFPQ payload = codes uint8 [n, M]; Flat/IVFFlat payload = float32 [n, d]."""
+        """-> (payload, ids): IVFPQ payload = codes uint8 [n, M]; IVFSQ payload = codes uint8 [n, d]; Flat/IVFFlat payload = float32 [n, d]."""
         n = ctypes.c_int64(0)
         _check(lib().rsx_get_list(self._h, ctypes.c_int64(list_no), ctypes.byref(n), None, None))
         n = n.value
         if self._get("kind") in (2, 3):
             payload = np.empty((n, self._get("M")), dtype=np.uint8)
+        elif self._get("kind") == 4:
+            payload = np.empty((n, self.d), dtype=np.uint8)
         else:
             payload = np.empty((n, self.d), dtype=np.float32)
         ids = np.empty(n, dtype=np.int64)
@@ -610,8 +615,9 @@ class _IndexIVF(Index):
 
     def add_list(self, list_no, payload, ids):
         ids = np.ascontiguousarray(ids, dtype=np.int64)
-        if self._get("kind") == 2:
+        if self._get("kind") in (2, 4):
             payload = np.ascontiguousarray(payload, dtype=np.uint8)
+            assert payload.ndim == 2 and payload.shape[1] == (self.d if self._get("kind") == 4 else self._get("M")), "add_list: codes of the wrong width"
             dt = _F32
         else:
             payload = np.ascontiguousarray(payload)
@@ -654,6 +660,67 @@ class IndexIVFPQ(_IndexIVF):
         cb = np.empty((self.M, 256, self.d // self.M), dtype=np.float32)
         _check(lib().rsx_get_codebooks(self._h, cb.ctypes.data_as(ctypes.c_void_p)))
         return cb
+
+
+class ScalarQuantizer:
+    """faiss.ScalarQuantizer: the quantiser-type constants, and — as IndexIVFScalarQuantizer.sq — the type and trained parameters of an index."""
+    QT_8bit, QT_4bit, QT_8bit_uniform, QT_4bit_uniform, QT_fp16, QT_8bit_direct, QT_6bit = 0, 1, 2, 3, 4, 5, 6
+
+    def __init__(self, index=None):
+        self._index = index
+
+    @property
+    def qtype(self):
+        return self._index._get("qtype")
+
+    @property
+    def code_size(self):
+        return self._index._get("code_size")
+
+    @property
+    def trained(self):
+        """float32 [2 d]: vmin[d] then vdiff[d] (faiss ScalarQuantizer::trained for QT_8bit)."""
+        t = np.empty(2 * self._index.d, dtype=np.float32)
+        _check(lib().rsx_get_sq_trained(self._index._h, t.ctypes.data_as(ctypes.c_void_p)))
+        return t
+
+
+class IndexIVFScalarQuantizer(_IndexIVF):
+    """faiss.IndexIVFScalarQuantizer(quantizer, d, nlist, qtype, metric=METRIC_L2, by_residual=True) — factory "IVF<nlist>,SQ8": one code
+    byte per dimension in the inverted lists (rsx_ivfsq_create).  Only ScalarQuantizer.QT_8bit.  A search returns the exact
+    Flat scores of the queries against the DECODED vectors of the probed lists.  Not in this build (each refused with a message naming the
+    kind): selectors / SearchParameters with a selector, remove_ids, sharded handles, the two-call search, IndexRefineFlat over it, FAISS-format files."""
+
+    def __init__(self, quantizer, d, nlist, qtype=ScalarQuantizer.QT_8bit, metric=METRIC_L2, by_residual=True, device=None, devices=None):
+        _quantizer_metric(quantizer, metric)
+        devs = _resolve_devices(device, devices)
+        if devs is not None and len(devs) > 1:
+            raise RuntimeError("IndexIVFScalarQuantizer (kind 4) has no sharded form in this build: name one device")
+        if devs is not None:
+            device = devs[0]
+        h = ctypes.c_void_p()
+        _check(lib().rsx_ivfsq_create(int(d), int(nlist), int(qtype), int(metric), 1 if by_residual else 0,
+                                      default_device() if device is None else int(device), ctypes.byref(h)))
+        super().__init__(h, int(d), int(metric))
+        self.quantizer = quantizer
+        self.sq = ScalarQuantizer(self)
+
+    @property
+    def by_residual(self):
+        return bool(self._get("by_residual"))
+
+    @property
+    def code_size(self):
+        return self._get("code_size")
+
+    def set_sq_trained(self, trained):
+        """Import the scalar quantiser's parameters (float32 [2 d]: vmin then vdiff), the counterpart of set_codebooks."""
+        t = np.ascontiguousarray(trained, dtype=np.float32)
+        assert t.shape == (2 * self.d,)
+        _check(lib().rsx_set_sq_trained(self._h, t.ctypes.data_as(ctypes.c_void_p)))
+
+    def search_prepass(self, x, k, params=None):
+        raise RuntimeError("search_prepass (the two-call search): not available on an IndexIVFScalarQuantizer (kind 4) in this build")
 
 
 class IndexPQ(Index):
@@ -722,6 +789,8 @@ class IndexRefineFlat:
     As in FAISS's IndexRefine there is no add_with_ids and no remove_ids."""
 
     def __init__(self, base_index, k_factor=1.0):
+        if isinstance(base_index, IndexIVFScalarQuantizer):
+            raise RuntimeError("IndexRefineFlat: an IndexIVFScalarQuantizer base (kind 4) is not supported in this build")
         if not isinstance(base_index, (IndexIVFPQ, IndexPQ, IndexIVFFlat, IndexFlat)):
             raise TypeError(f"IndexRefineFlat: the base must be an IndexIVFPQ, IndexPQ, IndexIVFFlat or IndexFlat, got {type(base_index).__name__}")
         if base_index.nshards:
@@ -815,13 +884,15 @@ def _wrap_handle(h):
         return v.value
 
     kind, d, metric = g("kind"), g("d"), g("metric")
-    cls = {0: IndexFlat, 1: IndexIVFFlat, 2: IndexIVFPQ, 3: IndexPQ}[kind]
+    cls = {0: IndexFlat, 1: IndexIVFFlat, 2: IndexIVFPQ, 3: IndexPQ, 4: IndexIVFScalarQuantizer}[kind]
     obj = cls.__new__(cls)
     Index.__init__(obj, h, d, metric)
     if kind in (2, 3):
         obj.M, obj.nbits = g("M"), g("nbits")
-    if kind in (1, 2):
+    if kind in (1, 2, 4):
         obj.quantizer = None
+    if kind == 4:
+        obj.sq = ScalarQuantizer(obj)
     return obj
 
 
@@ -831,6 +902,9 @@ def write_index(index, path):
     through rsx_faiss_io instead, for hand-over to a real faiss.read_index (written from upstream knowledge of the format,
     unverified against a FAISS-produced file: DESIGN.md)."""
     if os.environ.get("RSX_INDEX_FORMAT", "").lower() == "faiss" and index.nshards == 0:
+        if isinstance(index, IndexIVFScalarQuantizer):
+            raise RuntimeError("write_index: an IndexIVFScalarQuantizer (kind 4) has no FAISS-format writer in this build (RSX_INDEX_FORMAT=faiss); "
+                               "unset it to write the native RSX1 container")
         from rsx_faiss_io import write_faiss_index
         return write_faiss_index(index, os.fspath(path))
     if isinstance(index, IndexRefineFlat):

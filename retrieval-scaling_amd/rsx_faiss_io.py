@@ -159,6 +159,9 @@ def _read_index(r):
         if h["refine_index"]["kind"] != "Flat":
             raise RuntimeError("only IndexRefineFlat files are supported (the refine index must be an IndexFlat)")
         return h
+    if cc == "IwSq":
+        raise RuntimeError("FAISS IndexIVFScalarQuantizer files ('IwSq') are not read in this build: an IndexIVFScalarQuantizer (kind 4) "
+                           "is persisted in the native RSX1 container only")
     raise RuntimeError(f"unsupported FAISS index type '{cc}' (supported: IxFI, IxF2, IwFl, IwPQ, IxPq, IxRF)")
 
 
@@ -262,6 +265,8 @@ def index_to_parsed(index):
         return {"kind": "Refine", "d": index.d, "metric": index.metric_type, "ntotal": index.ntotal, "is_trained": index.is_trained,
                 "base_index": index_to_parsed(index.base_index), "refine_index": index_to_parsed(index.refine_index),
                 "k_factor": float(index.k_factor)}
+    if index._get("kind") == 4:
+        raise RuntimeError("an IndexIVFScalarQuantizer (kind 4) has no FAISS-format writer in this build")
     kind = {0: "Flat", 1: "IVFFlat", 2: "IVFPQ", 3: "PQ"}[index._get("kind")]
     p = {"kind": kind, "d": index.d, "metric": index.metric_type, "ntotal": index.ntotal,
          "is_trained": index.is_trained}
@@ -302,6 +307,8 @@ def _write_faiss_stream(index, out):
         _write_faiss_stream(index.refine_index, out)
         out.write(struct.pack("<f", float(index.k_factor)))
         return
+    if index._get("kind") == 4:
+        raise RuntimeError("an IndexIVFScalarQuantizer (kind 4) has no FAISS-format writer in this build")
     kind = {0: "Flat", 1: "IVFFlat", 2: "IVFPQ", 3: "PQ"}[index._get("kind")]
     if kind in ("Flat", "PQ"):      # (an IndexPQ of 100M x 96 bytes is 9.6 GB of codes: one list, exported in one piece)
         out.write(serialize_faiss(index_to_parsed(index)))
