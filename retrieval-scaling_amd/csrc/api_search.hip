@@ -243,21 +243,30 @@ static void merge_key_rows(rsx_index* h, const void* keys, const unsigned long l
     b.nrows = nrows; b.KP = KP; b.BUF = BUF; b.k = KP; b.row_filter = row_filter;
     launch_select(b, h->st);
 }
+// what a list-major scan reads of a grouping: the pairs sorted by list, the per-list offsets, the (list, tile, group) work items
+struct PairView {
+    const int32_t *pairs_sorted, *pair_off, *group_off, *total_groups, *item_off, *total_items; int nlist;
+};
 // the (query, probe) pairs of a batch grouped by list (launch_group_pairs), carved out of h->w_pairs
 struct PairArea {
-    int64_t npairs; int nlist, nprobe;
+    rsx_index* h; int64_t npairs; int nlist, nprobe;
     int32_t *pairs_sorted, *cnt, *cursor, *pair_off, *group_off, *item_off, *total_groups, *total_items;
-    PairArea(rsx_index* h, int64_t nq, int np, int nl) : npairs(nq * np), nlist(nl), nprobe(np) {
+    PairArea(rsx_index* hh, int64_t nq, int np, int nl) : h(hh), npairs(nq * np), nlist(nl), nprobe(np) {
         h->w_pairs.ensure((size_t)(npairs + 5 * (size_t)(nlist + 1) + 8) * 4);
         pairs_sorted = h->w_pairs.as<int32_t>(); cnt = pairs_sorted + npairs; cursor = cnt + (nlist + 1); pair_off = cursor + (nlist + 1);
         group_off = pair_off + (nlist + 1); item_off = group_off + (nlist + 1); total_groups = item_off + (nlist + 1); total_items = total_groups + 1;
     }
-    // groups of G probing queries over the probe ranks [0, jmax); tile_rows > 0: also the (list, tile, group) work items
-    void group(rsx_index* h, int G, int tile_rows, int jmax, int tile_cap, hipStream_t st) const {
-        launch_group_pairs(h->w_probelist.as<int32_t>(), npairs, nlist, G, cnt, cursor, pair_off, group_off, total_groups, pairs_sorted,
-                           tile_rows ? h->d_len.as<int64_t>() : nullptr, tile_rows, tile_rows ? item_off : nullptr,
-                           tile_rows ? total_items : nullptr, nprobe, 0, jmax, tile_cap, st);
+    // groups of G probing queries; tile_rows > 0: also the (list, tile, group) work items (at most tile_cap tiles per list, 0 = all)
+    PairGroupArgs args(int G, int tile_rows, int tile_cap) const {
+        PairGroupArgs g{};
+        g.probe_list = h->w_probelist.as<int32_t>(); g.pair_off = pair_off; g.group_off = group_off; g.total_groups = total_groups; g.pairs_sorted = pairs_sorted;
+        if (tile_rows) { g.list_len = h->d_len.as<int64_t>(); g.item_off = item_off; g.total_items = total_items; }
+        g.npairs = (int)npairs; g.nlist = nlist; g.G = G; g.tile_rows = tile_rows; g.tile_cap = tile_cap;
+        return g;
     }
+    // ... over the probe ranks [0, jmax), in launches of its own
+    void group(int G, int tile_rows, int jmax, int tile_cap, hipStream_t st) const { launch_group_pairs(args(G, tile_rows, tile_cap), cnt, cursor, nprobe, jmax, st); }
+    PairView view() const { return PairView{pairs_sorted, pair_off, group_off, total_groups, item_off, total_items, nlist}; }
 };
 // what one batch's stages leave for the later ones
 struct BatchResult {
@@ -377,22 +386,36 @@ static void check_supported(rsx_index* h, const BatchPlan& P) {
 // stream and runs beside the coarse quantiser and the probe selection; the per-query parameters (k_pq_qparam: they need the coarse
 // scores) follow on the main stream once both have finished.  Round 6 measured the three cross-stream joins of a batch at ~12 us
 // each (profiles/r06_fixed_cost.md): the default is one stream, with the table build, the parameters and the pair grouping in two launches.
+// the table build's arguments; its two callers add what they differ in: probe_dis0 / nprobe, phase, mfma, pg
+static PQLutArgs pq_lut_args(rsx_index* h, const BatchPlan& P, void* lut_ws) {
+    PQLutArgs a{};
+    a.lut32 = P.pq_fused_lut ? nullptr : h->w_lut.as<float>();
+    a.Q32 = h->w_q32.as<float>(); a.ldq = h->ld; a.codebooks = h->d_codebooks.as<float>(); a.dsub = h->dsub; a.nq = P.nq; a.M = h->M; a.Mpad = h->Mpad;
+    a.lut8 = h->w_lut8.as<uint8_t>(); a.qparam = h->w_qparam.p; a.ws = lut_ws;
+    a.transposed = P.sliced ? 2 : P.rot ? 1 : 0; a.metric = h->metric; a.lut32_out = lut32_out(h, P);
+    return a;
+}
 static void fork_side_tables(rsx_index* h, const BatchPlan& P) {
     ensure_side_stream(h);
     h->w_lut8.ensure((size_t)P.nq * h->Mpad * 256); h->w_qparam.ensure((size_t)P.nq * 16); h->w_lutws.ensure(pq_lut8_tiled_ws(P.nq, h->Mpad));
     HIPCHECK(hipEventRecord(h->ev_fork, h->st));
     HIPCHECK(hipStreamWaitEvent(h->st2, h->ev_fork, 0));
-    launch_pq_lut8(nullptr, h->w_q32.as<float>(), h->ld, h->d_codebooks.as<float>(), h->dsub, P.nq, h->M, h->Mpad, nullptr, 0,
-                   h->w_lut8.as<uint8_t>(), h->w_qparam.p, h->w_lutws.p, P.sliced ? 2 : P.rot ? 1 : 0, h->st2, h->metric, 1, lut32_out(h, P));
+    PQLutArgs la = pq_lut_args(h, P, h->w_lutws.p);
+    la.phase = PQ_LUT_TABLES;
+    launch_pq_lut8(la, h->st2);
     HIPCHECK(hipEventRecord(h->ev_lut, h->st2));
 }
-// >= the largest centroid norm (certificate term of a by_residual scalar-quantiser index), once per centroid set
-static float sq_cent_cmax(rsx_index* h) {
-    if (h->sq_cmax_gen == h->cent_gen) return h->sq_cmax;
+// >= the largest centroid norm (the fast coarse quantiser's bound; certificate term of a by_residual scalar-quantiser index), once per centroid set
+static float cent_cmax(rsx_index* h) {
+    if (h->cent_cmax_gen == h->cent_gen) return h->cent_cmax;
     double mx = 0.0;
     for (int l = 0; l < h->nlist; l++) { double n2 = 0.0; for (int t = 0; t < h->d; t++) { const double v = h->h_centroids[(size_t)l * h->d + t]; n2 += v * v; } mx = std::max(mx, n2); }
-    h->sq_cmax = (float)(std::sqrt(mx) * 1.000001); h->sq_cmax_gen = h->cent_gen;
-    return h->sq_cmax;
+    h->cent_cmax = (float)(std::sqrt(mx) * 1.000001); h->cent_cmax_gen = h->cent_gen;
+    return h->cent_cmax;
+}
+// the stored rows of a KIND_IVFSQ index, as the exact re-scores decode them
+static SqRows sq_rows(rsx_index* h) {
+    return SqRows{h->data.as<uint8_t>(), h->d_sq.as<float>(), h->by_residual ? h->d_centroids.as<float>() : nullptr, h->d_base.as<int64_t>(), h->nlist};
 }
 static FinalizeArgs finalize_args(rsx_index* h, const BatchPlan& P, float* dD, int64_t* dI) {
     const int d = h->d, ld = h->ld;
@@ -421,7 +444,7 @@ static FinalizeArgs finalize_args(rsx_index* h, const BatchPlan& P, float* dD, i
         fa.cert_abs = sqrtf((float)d) * u24 + (h->metric == RSX_METRIC_L2 ? ((float)d + 4.0f) * u24 * xmax : 0.0f);
     }
     if (h->kind == KIND_IVFSQ) {
-        fa.sq = SqRows{h->data.as<uint8_t>(), h->d_sq.as<float>(), h->by_residual ? h->d_centroids.as<float>() : nullptr, h->d_base.as<int64_t>(), h->nlist};
+        fa.sq = sq_rows(h);
         fa.X = nullptr;
         if (P.certify) {
             // The scan's score of a stored vector x^ (k_sq_list_scan) is  (sum_j (hi_j + lo_j) b_j) / s + const_q (+ <q, c_l>) (+ -|x^|^2/2)
@@ -442,7 +465,7 @@ static FinalizeArgs finalize_args(rsx_index* h, const BatchPlan& P, float* dD, i
             const float rel_b = ((2.0f * fd + 2.0f) * u24 + 4.76837158e-7f + sqrtf(fd) * 7.4505806e-9f + 2.0f * u24) * 1.01f;
             const float rB = (h->sq_vdmax / 255.0f) * sqrtf((float)h->sq_bn2) * 1.00001f;
             float cq = rel_b * rB + 10.0f * u24 * 1.01f * (h->sq_nvdiff + h->sq_nvmin);
-            if (h->by_residual) cq += u24 * 1.01f * ((fd + 4.0f) * sq_cent_cmax(h) + 2.0f * fa.cert_xmax);
+            if (h->by_residual) cq += u24 * 1.01f * ((fd + 4.0f) * cent_cmax(h) + 2.0f * fa.cert_xmax);
             fa.cert_rel = 0.0f; fa.cert_rel_qlossy = 0.0f; fa.cert_q = cq;
         }
     }
@@ -584,12 +607,9 @@ static void coarse_quantiser(rsx_index* h, const BatchPlan& P, const void* dq, i
     if (P.coarse_fast) {
         const int64_t nqp = h->kind == KIND_IVFPQ ? round_up(nq, 128) : P.nq_pad;
         const int64_t nl128 = round_up(nlist, 128);
-        if (h->cent16_gen != h->cent_gen || !h->cent16.p) {       // the centroids' fp16 copy + the norm bound, once per centroid set
+        if (h->cent16_gen != h->cent_gen || !h->cent16.p) {       // the centroids' fp16 copy, once per centroid set
             h->cent16.ensure((size_t)nl128 * ld * 2);
             launch_convert_to_f16(h->d_centroids.p, 0, nlist, d, h->cent16.as<__half>(), ld, nl128, nullptr, h->st);
-            double mx = 0.0;
-            for (int l = 0; l < nlist; l++) { double n2 = 0.0; for (int t = 0; t < d; t++) { const double v = h->h_centroids[(size_t)l * d + t]; n2 += v * v; } mx = std::max(mx, n2); }
-            h->cent_cmax = (float)(std::sqrt(mx) * 1.000001);
             h->cent16_gen = h->cent_gen;
         }
         h->w_coarse.ensure((size_t)nqp * nlp * 4);
@@ -599,7 +619,7 @@ static void coarse_quantiser(rsx_index* h, const BatchPlan& P, const void* dq, i
         h->w_uncertain.ensure((size_t)nq * 8);
         CoarsePickArgs cp{};
         cp.approx = h->w_coarse.as<float>(); cp.nlp = nlp; cp.nlist = nlist; cp.Q32 = h->w_q32.as<float>(); cp.ld = ld; cp.d = d;
-        cp.C = h->d_centroids.as<float>(); cp.cmax = h->cent_cmax;
+        cp.C = h->d_centroids.as<float>(); cp.cmax = cent_cmax(h);
         cp.ef = (dtype == RSX_F16 ? 1.0f : 2.0f) * 4.8828125e-4f;        // centroids rounded to fp16; fp32 queries as well
         cp.nprobe = nprobe; cp.list_len = h->d_len.as<int64_t>(); cp.pad_to = P.pad_to;
         cp.probe_list = h->w_probelist.as<int32_t>(); cp.dis0 = h->w_dis0.as<float>(); cp.seg_start = h->w_segstart.as<int64_t>();
@@ -662,9 +682,11 @@ static void* rot_scan_ws(rsx_index* h, int k, int64_t items, int ngq, int& log_c
 // the 8-bit tables + per-query parameters; pg: the (query, probe) pairs grouped by list in the same launch (matrix-core form only)
 static void build_pq_tables(rsx_index* h, const BatchPlan& P, void* lut_ws, const PairGroupArgs* pg, StageTimer& tm) {
     if (P.side_lut) HIPCHECK(hipStreamWaitEvent(h->st, h->ev_lut, 0));     // the tables were built beside the probe selection
-    launch_pq_lut8(P.pq_fused_lut ? nullptr : h->w_lut.as<float>(), h->w_q32.as<float>(), h->ld, h->d_codebooks.as<float>(), h->dsub, P.nq, h->M,
-                   h->Mpad, h->w_dis0.as<float>(), P.nprobe, h->w_lut8.as<uint8_t>(), h->w_qparam.p, lut_ws, P.sliced ? 2 : P.rot ? 1 : 0, h->st,
-                   h->metric, P.side_lut ? 2 : 0, lut32_out(h, P), (lut_ws && !P.side_lut && h->lut_tiled >= 2) ? (P.lut_pass0_early ? 2 : 1) : 0, pg);
+    PQLutArgs la = pq_lut_args(h, P, lut_ws);
+    la.probe_dis0 = h->w_dis0.as<float>(); la.nprobe = P.nprobe;
+    la.phase = P.side_lut ? PQ_LUT_QPARAM : PQ_LUT_WHOLE;
+    la.mfma = (lut_ws && !P.side_lut && h->lut_tiled >= 2) ? (P.lut_pass0_early ? 2 : 1) : 0; la.pg = pg;
+    launch_pq_lut8(la, h->st);
     tm.mark("lut8");
 }
 // the fast scan's tiles and its threshold pre-pass: vectors per lane (vpl, tile_rows = 1024 vpl), the pre-pass sample and its form
@@ -752,10 +774,8 @@ static bool pq_prepass(rsx_index* h, const BatchPlan& P, BatchResult& R, const P
     bool grouped = false;
     if (group_in_tables) {      // the pairs grouped by list by extra workgroups of the table launch
         if (!h->w_pgflags.p) { h->w_pgflags.ensure((size_t)PG_BLOCKS * 16); HIPCHECK(hipMemsetAsync(h->w_pgflags.p, 0, (size_t)PG_BLOCKS * 16, h->st)); }
-        pg.probe_list = h->w_probelist.as<int32_t>(); pg.list_len = h->d_len.as<int64_t>();
-        pg.pair_off = pr.pair_off; pg.group_off = pr.group_off; pg.item_off = pr.item_off; pg.total_groups = pr.total_groups; pg.total_items = pr.total_items;
-        pg.pairs_sorted = pr.pairs_sorted; pg.flags = h->w_pgflags.as<uint32_t>();
-        pg.npairs = (int)pr.npairs; pg.nlist = nlist; pg.G = 4 * P.ngq; pg.tile_rows = g.tile_rows; pg.tile_cap = 0; pg.nb = PG_BLOCKS;
+        pg = pr.args(4 * P.ngq, g.tile_rows, 0);
+        pg.flags = h->w_pgflags.as<uint32_t>(); pg.nb = PG_BLOCKS;
         if (++h->pg_epoch == 0) h->pg_epoch = 1;
         pg.epoch = h->pg_epoch;
         grouped = true;
@@ -763,7 +783,7 @@ static bool pq_prepass(rsx_index* h, const BatchPlan& P, BatchResult& R, const P
     build_pq_tables(h, P, lut_ws, group_in_tables ? &pg : nullptr, tm);
     if (P.side_lut && !P.staged) {       // the (list, tile, group) work items of the scan: built beside the pre-pass (they need the probes only)
         HIPCHECK(hipStreamWaitEvent(h->st2, h->ev_probe, 0));
-        pr.group(h, 4 * P.ngq, g.tile_rows, P.nprobe, 0, h->st2);
+        pr.group(4 * P.ngq, g.tile_rows, P.nprobe, 0, h->st2);
         HIPCHECK(hipEventRecord(h->ev_group, h->st2));
         grouped = true;
     }
@@ -785,10 +805,30 @@ static bool pq_prepass(rsx_index* h, const BatchPlan& P, BatchResult& R, const P
     }
     return grouped;
 }
+// What every list-major scan takes: the per-pair arguments, the grouping and the bound of its work items (the kernels' grid).  A bound that
+// is not in (0, 0x7fffff00] becomes 0, which every scan launcher refuses (-1): it never wraps into the 32-bit field.
+template <typename Args>
+static void scan_common(Args& A, const PQScanArgs& b, const PairView& v, int64_t max_items) {
+    A.b = b;
+    A.pairs_sorted = v.pairs_sorted; A.pair_off = v.pair_off; A.group_off = v.group_off; A.total_groups = v.total_groups;
+    A.item_off = v.item_off; A.total_items = v.total_items; A.nlist = v.nlist;
+    A.max_items = (max_items <= 0 || max_items > 0x7fffff00) ? 0 : (int)max_items;
+}
+// ... and the batch's 8-bit tables for the fast scans; a call site adds its own: threshold and candidate rows, prune, pace, excl, qitems, the tile set
+static PQScan8Args scan8_args(rsx_index* h, const PQScanArgs& b, const PairView& v, int64_t max_items) {
+    PQScan8Args A{};
+    scan_common(A, b, v, max_items);
+    A.lut8 = h->w_lut8.as<uint8_t>(); A.qp = h->w_qparam.as<PQQParam>();
+    return A;
+}
+// how a work-item scan of the block layouts is launched: its tile (1024 vpl rows), rot_scan_ws' workspace, the plan's eight-query choice
+static PQRotLaunch rot_launch(const rsx_index* h, const BatchPlan& P, int vpl, void* ws, int log_cap) {
+    return PQRotLaunch{vpl, ws, log_cap, P.sliced ? (P.sl_eight ? 1 : 0) : h->pq_q8};
+}
 // the main filtered scan: every (query, probe) pair, only the keys above the query's threshold reach its candidate row
 static bool pq_filtered_scan(rsx_index* h, const BatchPlan& P, BatchResult& R, PQScanArgs& a, const PairArea& pr, const PqGeometry& g,
                              bool grouped, StageTimer& tm) {
-    const int64_t nq = P.nq; const int nlist = h->nlist, nprobe = P.nprobe, KP = P.KP;
+    const int64_t nq = P.nq; const int nprobe = P.nprobe, KP = P.KP;
     uint64_t* state = h->w_state.as<uint64_t>();
     tm.mark("scan0");
     if (!g.fused_pre) {
@@ -806,7 +846,7 @@ static bool pq_filtered_scan(rsx_index* h, const BatchPlan& P, BatchResult& R, P
         tm.mark("select0");
     }
     if (grouped) { if (P.side_lut) HIPCHECK(hipStreamWaitEvent(h->st, h->ev_group, 0)); }
-    else pr.group(h, 4 * P.ngq, g.tile_rows, nprobe, 0, h->st);
+    else pr.group(4 * P.ngq, g.tile_rows, nprobe, 0, h->st);
     if (!(grouped && !P.side_lut)) tm.mark("group");
     const int64_t mi = max_scan_items(h, nq, nprobe, 4 * P.ngq, g.tile_rows);
     int log_cap = 64;
@@ -828,14 +868,15 @@ static bool pq_filtered_scan(rsx_index* h, const BatchPlan& P, BatchResult& R, P
         gs.state = state; gs.KP = KP;
     }
     tm.pre_scan();
-    return (P.rot ? launch_pq_scan_rot(a, h->w_lut8.as<uint8_t>(), h->w_qparam.p, pr.pairs_sorted, pr.pair_off, pr.group_off,
-                                       pr.total_groups, pr.item_off, pr.total_items, nlist, mi, g.vpl, tau_ptr, tau_stride,
-                                       h->w_cand.as<uint64_t>(), h->w_candcnt.as<unsigned long long>(), R.cand_cap,
-                                       rws, log_cap, h->pq_prune, (h->pq_pace & 0xffff), (g.fused_pre && P.rot) ? h->w_excl.as<uint16_t>() : nullptr,
-                                       R.use_gather ? h->w_qitems.as<int32_t>() : nullptr, gs_tmax, h->st, P.sliced ? (P.sl_eight ? 1 : 0) : h->pq_q8)
-                  : launch_pq_scan8_filter(a, h->w_lut8.as<uint8_t>(), h->w_qparam.p, pr.pairs_sorted, pr.pair_off, pr.group_off,
-                                           pr.total_groups, pr.item_off, pr.total_items, nlist, mi, g.vpl, tau_ptr, tau_stride,
-                                           h->w_cand.as<uint64_t>(), h->w_candcnt.as<unsigned long long>(), R.cand_cap, h->st)) == 0;
+    PQScan8Args A = scan8_args(h, a, pr.view(), mi);
+    A.tau_key = tau_ptr; A.tau_stride = tau_stride;
+    A.cand = h->w_cand.as<uint64_t>(); A.cand_cnt = h->w_candcnt.as<unsigned long long>(); A.cand_cap = R.cand_cap;
+    if (!P.rot) return launch_pq_scan8(A, g.vpl, h->st) == 0;
+    A.prune = h->pq_prune; A.pace = h->pq_pace & 0xffff;
+    if (g.fused_pre) A.excl = h->w_excl.as<uint16_t>();
+    if (R.use_gather) A.qitems = h->w_qitems.as<int32_t>();
+    A.qitems_tmax = gs_tmax;
+    return launch_pq_scan_rot(A, rot_launch(h, P, g.vpl, rws, log_cap), h->st) == 0;
 }
 // IndexPQ (faiss.IndexPQ: one list, every query scans every code): the staged filtered scan.  The filtered IVF-PQ scan takes ONE threshold
 // from a sample of its closest list; over N rows in exchangeable order a threshold from R0 rows lets ~N k / R0 rows through — 49 000 per
@@ -896,7 +937,6 @@ static void pq_staged_scan(rsx_index* h, const BatchPlan& P, BatchResult& R, PQS
     h->w_stagedir.ensure(hd.size() * 4);
     HIPCHECK(hipMemcpyAsync(h->w_stagedir.p, hd.data(), hd.size() * 4, hipMemcpyHostToDevice, h->st));
     const int32_t* sd = h->w_stagedir.as<int32_t>();
-    const int32_t *pairs_sorted = sd, *pair_off = sd + nq, *group_off = sd + nq + 2, *total_groups = sd + nq + 4;
     const int64_t mi = (int64_t)ng * tmax + 8;
     int log_cap = 64;
     void* rws = rot_scan_ws(h, P.k, mi, P.ngq, log_cap);
@@ -906,15 +946,18 @@ static void pq_staged_scan(rsx_index* h, const BatchPlan& P, BatchResult& R, PQS
     ga.seg_desc = pq_scan_rot_ws_desc(rws, mi * P.ngq); ga.log_keys = pq_scan_rot_ws_keys(rws, mi * P.ngq);
     ga.cand = h->w_cand.as<uint64_t>(); ga.cand_cnt = h->w_candcnt.as<unsigned long long>(); ga.cand_cap = R.cand_cap;
     ga.qparam = h->w_qparam.as<float>(); ga.k = P.k; ga.tau = h->w_tau.as<uint64_t>();
+    // the one list's grouping in the staged directory; item_off / total_items and the first tile number: per stage
+    PQScan8Args A = scan8_args(h, a, PairView{sd, sd + nq, sd + nq + 2, sd + nq + 4, nullptr, nullptr, 1}, mi);
+    A.tau_key = h->w_tau.as<uint64_t>(); A.tau_stride = 1;
+    A.cand = h->w_cand.as<uint64_t>(); A.cand_cnt = h->w_candcnt.as<unsigned long long>(); A.cand_cap = R.cand_cap;
+    A.pace = h->pq_pace & 0xffff;
+    A.qitems = h->w_qitems.as<int32_t>(); A.qitems_tmax = tmax;
+    A.tile_mul = mul; A.tile_mod = T;
     for (int s_ = 0; s_ < S; s_++) {
         const int j0 = s_ ? ends[(size_t)s_ - 1] : 0, nt = ends[(size_t)s_] - j0;
-        const int32_t* item_off = sd + nq + 8 + 4 * s_;
+        A.item_off = sd + nq + 8 + 4 * s_; A.total_items = A.item_off + 2; A.tile_j0 = j0;
         if (s_ == S - 1) tm.pre_scan();
-        PQTileSet ts; ts.j0 = j0; ts.mul = mul; ts.mod = T;
-        if (launch_pq_scan_rot(a, h->w_lut8.as<uint8_t>(), h->w_qparam.p, pairs_sorted, pair_off, group_off, total_groups, item_off, item_off + 2,
-                               1, mi, g.vpl, h->w_tau.as<uint64_t>(), 1, h->w_cand.as<uint64_t>(), h->w_candcnt.as<unsigned long long>(), R.cand_cap,
-                               rws, log_cap, 0, (h->pq_pace & 0xffff), nullptr, h->w_qitems.as<int32_t>(), tmax, h->st,
-                               P.sliced ? (P.sl_eight ? 1 : 0) : h->pq_q8, ts) != 0)
+        if (launch_pq_scan_rot(A, rot_launch(h, P, g.vpl, rws, log_cap), h->st) != 0)
             RSX_THROW(RSX_ERR_UNSUPPORTED, "IndexPQ staged scan: no kernel for M=%d at a batch of %lld queries (the sliced 8-query scan takes at most 4 GiB of 8-bit tables per batch)", h->M, (long long)P.nq);
         tm.mark("scan");
         ga.ntiles = nt; ga.nrecs = (int64_t)ng * nt * P.ngq; ga.last = s_ == S - 1;
@@ -951,17 +994,14 @@ static void pq_fast_scan(rsx_index* h, const BatchPlan& P, BatchResult& R, PQSca
         build_pq_tables(h, P, lut_ws, nullptr, tm);
         h->w_temp.ensure((size_t)nq * P.tmax * 4);       // this form scores a prefix / everything into the score rows
         a.temp = h->w_temp.as<float>();
-        pr.group(h, 4, g.pre_rows, R.filtered ? 1 : nprobe, R.filtered ? 1 : 0, h->st);
+        pr.group(4, g.pre_rows, R.filtered ? 1 : nprobe, R.filtered ? 1 : 0, h->st);
         tm.mark("group");
         const int64_t mi = R.filtered ? (nq + nlist + 8) : max_scan_items(h, nq, nprobe, 4, g.tile_rows);
         int log_cap = 64;
         void* rws = P.rot ? rot_scan_ws(h, P.k, mi, 1, log_cap) : nullptr;
         const int vpl = R.filtered ? g.pre_vpl : g.vpl;
-        done = (P.rot ? launch_pq_scan_rot(a, h->w_lut8.as<uint8_t>(), h->w_qparam.p, pr.pairs_sorted, pr.pair_off, pr.group_off,
-                                           pr.total_groups, pr.item_off, pr.total_items, nlist, mi, vpl,
-                                           nullptr, 0, nullptr, nullptr, 0, rws, log_cap, 0, 0, nullptr, nullptr, 0, h->st)
-                      : launch_pq_scan8(a, h->w_lut8.as<uint8_t>(), h->w_qparam.p, pr.pairs_sorted, pr.pair_off, pr.group_off,
-                                        pr.total_groups, pr.item_off, pr.total_items, nlist, mi, vpl, h->st)) == 0;
+        const PQScan8Args A = scan8_args(h, a, pr.view(), mi);      // no threshold: every score goes to the score rows
+        done = (P.rot ? launch_pq_scan_rot(A, rot_launch(h, P, vpl, rws, log_cap), h->st) : launch_pq_scan8(A, vpl, h->st)) == 0;
     }
     if (done && R.filtered && !P.staged) done = pq_filtered_scan(h, P, R, a, pr, g, grouped, tm);
     if (!done) RSX_THROW(RSX_ERR_UNSUPPORTED, "IVFPQ fast scan: no kernel for M=%d at a batch of %lld queries (the sliced 8-query scan takes at most 4 GiB of 8-bit tables per batch)", h->M, (long long)P.nq);
@@ -982,10 +1022,11 @@ static void pq_exact_scan(rsx_index* h, const BatchPlan& P, PQScanArgs& a, Stage
         if (vpl != 8 && vpl != 4 && vpl != 2) vpl = 1;
         const int tile_rows = 64 * 16 * vpl;
         const PairArea pr(h, nq, P.nprobe, nlist);
-        pr.group(h, 2, tile_rows, P.nprobe, 0, h->st);
+        pr.group(2, tile_rows, P.nprobe, 0, h->st);
         tm.mark("group");
-        if (launch_pq_scan2(a, pr.pairs_sorted, pr.pair_off, pr.group_off, pr.total_groups, pr.item_off, pr.total_items, nlist,
-                            max_scan_items(h, nq, P.nprobe, 2, tile_rows), vpl, h->st) == 0) return;
+        PQScan2Args A{};
+        scan_common(A, a, pr.view(), max_scan_items(h, nq, P.nprobe, 2, tile_rows));
+        if (launch_pq_scan2(A, vpl, h->st) == 0) return;
     }
     const int64_t max_slabs = std::max<int64_t>(1, P.maxlen / 64); int64_t spc;
     if (h->scan_chunk > 0) spc = std::max<int64_t>(16, h->scan_chunk / 64);
@@ -1027,7 +1068,7 @@ static void ivf_flat_exact(rsx_index* h, const BatchPlan& P, StageTimer& tm) {
     ea.list_base = h->d_base.as<int64_t>(); ea.list_len = h->d_len.as<int64_t>();
     if (h->kind == KIND_IVFSQ) {      // the same fp64 scores against the decoded rows
         ea.X = nullptr;
-        ea.sq = SqRows{h->data.as<uint8_t>(), h->d_sq.as<float>(), h->by_residual ? h->d_centroids.as<float>() : nullptr, h->d_base.as<int64_t>(), h->nlist};
+        ea.sq = sq_rows(h);
         launch_sq_exact_scores(ea, h->st);
     } else
     launch_exact_scores(ea, h->st);
@@ -1063,7 +1104,7 @@ static bool ivf_flat_filtered(rsx_index* h, const BatchPlan& P, BatchResult& R, 
         a.pre_stride = pre_stride; a.tstride = pre_lists * pre_stride;
         launch_fill_f32(h->w_temp.as<float>(), nq * a.tstride, -INFINITY, h->st);
     }
-    pr.group(h, 16, 0, pre_lists, 0, h->st);       // ... the closest list(s) only
+    pr.group(16, 0, pre_lists, 0, h->st);       // ... the closest list(s) only
     launch_list_scan(a, h->st);
     if (a.sq_codes) h->timing["ivfsq_scan_launches"] += 1;
     tm.mark("scan0");
@@ -1078,7 +1119,7 @@ static bool ivf_flat_filtered(rsx_index* h, const BatchPlan& P, BatchResult& R, 
                     std::min<int64_t>(P.maxlen, pre_chunks * chunk_rows), 0, nq, KP, P.BUF, KP, state, false,
                     h->w_candcnt.as<unsigned long long>());
     tm.mark("select0");
-    pr.group(h, 16 * ls_qt, item_rows, nprobe, 0, h->st);
+    pr.group(16 * ls_qt, item_rows, nprobe, 0, h->st);
     tm.mark("group");
     a.qtiles = ls_qt;
     if (ls_qt >= 4) { chunk_rows *= 2; a.chunk_rows = (int)chunk_rows; }      // 8 waves, 1024 rows per work item
@@ -1103,6 +1144,20 @@ static bool ivf_flat_filtered(rsx_index* h, const BatchPlan& P, BatchResult& R, 
     if (filtered && n_over > 0) { R.flag_overflows = true; h->timing["ivf_filter_overflow_queries"] += (double)n_over; }
     a.tau_key = nullptr; a.cand = nullptr; a.cand_cnt = nullptr; a.cand_cap = 0;
     return filtered;
+}
+// what the list scans of IVF-Flat and IVF-SQ share: lists, grouping, probes, score rows, the group bound, the L2 bias; each adds its rows and queries
+static ListScanArgs list_scan_args(rsx_index* h, const BatchPlan& P, const PairArea& pr) {
+    const int64_t npairs = pr.npairs;
+    ListScanArgs a{};
+    a.ld = h->ld;
+    a.bias = h->metric == RSX_METRIC_L2 ? h->w_misc.as<float>() : nullptr;
+    a.list_base = h->d_base.as<int64_t>(); a.list_len = h->d_len.as<int64_t>();
+    a.pairs_sorted = pr.pairs_sorted; a.pair_off = pr.pair_off; a.group_off = pr.group_off; a.total_groups = pr.total_groups;
+    a.probe_list = h->w_probelist.as<int32_t>(); a.seg_start = h->w_segstart.as<int64_t>();
+    a.nlist = pr.nlist; a.nprobe = pr.nprobe; a.flat_mode = 0; a.nq = (int)P.nq;
+    a.temp = h->w_temp.as<float>(); a.tstride = P.tmax;
+    a.max_groups = (int)std::min<int64_t>(npairs, npairs / 16 + std::min<int64_t>(pr.nlist, npairs));
+    return a;
 }
 // group (query, probe) pairs by list, then list-major MFMA scan
 static void ivf_flat_scan(rsx_index* h, const BatchPlan& P, BatchResult& R, StageTimer& tm) {
@@ -1130,17 +1185,10 @@ static void ivf_flat_scan(rsx_index* h, const BatchPlan& P, BatchResult& R, Stag
     const int ls2_rows = list_scan2_chunk_rows(h->storage_f16, ld);
     const bool ls_wide = ls_qt >= 4;     // the 8-wave forms: 1024 rows per work item
     const int item_rows = (h->scan_chunk <= 0 && ls2_rows > 0) ? (ls_wide ? 2 * ls2_rows : ls2_rows) : 0;
-    pr.group(h, 16 * ls_qt, item_rows, nprobe, 0, h->st);
+    pr.group(16 * ls_qt, item_rows, nprobe, 0, h->st);
     tm.mark("group");
-    ListScanArgs a{};
-    a.Q16 = h->w_q16.as<__half>(); a.ld = ld; a.X = h->data.p; a.x_f16 = h->storage_f16;
-    a.bias = h->metric == RSX_METRIC_L2 ? h->w_misc.as<float>() : nullptr;
-    a.list_base = h->d_base.as<int64_t>(); a.list_len = h->d_len.as<int64_t>();
-    a.pairs_sorted = pr.pairs_sorted; a.pair_off = pr.pair_off; a.group_off = pr.group_off; a.total_groups = pr.total_groups;
-    a.probe_list = h->w_probelist.as<int32_t>(); a.seg_start = h->w_segstart.as<int64_t>();
-    a.nlist = nlist; a.nprobe = nprobe; a.flat_mode = 0; a.nq = (int)nq;
-    a.temp = h->w_temp.as<float>(); a.tstride = P.tmax;
-    a.max_groups = (int)std::min<int64_t>(npairs, npairs / 16 + std::min<int64_t>(nlist, npairs));
+    ListScanArgs a = list_scan_args(h, P, pr);
+    a.Q16 = h->w_q16.as<__half>(); a.X = h->data.p; a.x_f16 = h->storage_f16;
     int64_t chunk_rows = h->scan_chunk > 0 ? round_up(h->scan_chunk, 64) : 2048;
     int64_t want = 2048;  // work items
     while (chunk_rows > 256 && (int64_t)a.max_groups * ((P.maxlen + chunk_rows - 1) / chunk_rows) < want) chunk_rows /= 2;
@@ -1182,18 +1230,11 @@ static void ivf_sq_scan(rsx_index* h, const BatchPlan& P, BatchResult& R, StageT
     const int64_t qpl = npairs / std::max(1, nlist);
     const int ls_qt = h->ivf_qtiles == 0 ? 1 : h->ivf_qtiles > 1 ? 4 : (qpl >= 12 ? 4 : 1);
     const int base_rows = sq_list_scan_chunk_rows(1), item_rows = sq_list_scan_chunk_rows(ls_qt);
-    pr.group(h, 16 * ls_qt, item_rows, nprobe, 0, h->st);
+    pr.group(16 * ls_qt, item_rows, nprobe, 0, h->st);
     tm.mark("group");
-    ListScanArgs a{};
-    a.ld = ld; a.sq_codes = h->data.as<uint8_t>(); a.sq_qhi = h->w_sqhi.as<__half>(); a.sq_qlo = h->w_sqlo.as<__half>(); a.sq_qc = h->w_sqc.as<float>();
+    ListScanArgs a = list_scan_args(h, P, pr);
+    a.sq_codes = h->data.as<uint8_t>(); a.sq_qhi = h->w_sqhi.as<__half>(); a.sq_qlo = h->w_sqlo.as<__half>(); a.sq_qc = h->w_sqc.as<float>();
     a.sq_dis0 = h->by_residual ? h->w_dis0.as<float>() : nullptr;
-    a.bias = h->metric == RSX_METRIC_L2 ? h->w_misc.as<float>() : nullptr;
-    a.list_base = h->d_base.as<int64_t>(); a.list_len = h->d_len.as<int64_t>();
-    a.pairs_sorted = pr.pairs_sorted; a.pair_off = pr.pair_off; a.group_off = pr.group_off; a.total_groups = pr.total_groups;
-    a.probe_list = h->w_probelist.as<int32_t>(); a.seg_start = h->w_segstart.as<int64_t>();
-    a.nlist = nlist; a.nprobe = nprobe; a.flat_mode = 0; a.nq = (int)nq;
-    a.temp = h->w_temp.as<float>(); a.tstride = P.tmax;
-    a.max_groups = (int)std::min<int64_t>(npairs, npairs / 16 + std::min<int64_t>(nlist, npairs));
     a.chunk_rows = base_rows; a.qtiles = ls_qt;
     a.max_chunks = (int)std::max<int64_t>(1, (P.maxlen + base_rows - 1) / base_rows);
     const int64_t pre_chunks = std::max<int64_t>(1, ((int64_t)P.KP * std::max(1, h->ivf_pre_mult) + base_rows - 1) / base_rows);

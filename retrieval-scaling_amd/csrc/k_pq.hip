@@ -155,12 +155,7 @@ int launch_pq_scan(const PQScanArgs& a, hipStream_t st) {
 // kept in registers; the additions still happen in m = 0..M-1 order, so scores stay bit-identical
 // to v1 / the oracle.
 // NCH = Mpad/16 granules per vector, VPL = slabs per wave per tile (register accumulators).
-struct PQScan2Args {
-    PQScanArgs b;
-    const int32_t* pairs_sorted; const int32_t* pair_off; const int32_t* group_off; const int32_t* total_groups;
-    const int32_t* item_off; const int32_t* total_items;   // work items = (list, tile, group), list-major
-    int nlist; int max_items;
-};
+// (PQScan2Args: rsx_internal.h)
 
 template <int NCH, int VPL>
 __global__ __launch_bounds__(1024) void k_pq_scan2(PQScan2Args A) {
@@ -270,14 +265,9 @@ static int launch_pq_scan2_v(const PQScan2Args& A, int vpl, hipStream_t st) {
     }
 }
 // returns 0 on launch, -1 if this (M, layout) has no v2 kernel (caller falls back to k_pq_scan)
-int launch_pq_scan2(const PQScanArgs& a, const int32_t* pairs_sorted, const int32_t* pair_off, const int32_t* group_off,
-                    const int32_t* total_groups, const int32_t* item_off, const int32_t* total_items, int nlist,
-                    int64_t max_items, int vpl, hipStream_t st) {
-    if (a.CB != 16 || max_items <= 0 || max_items > 0x7fffff00) return -1;
-    PQScan2Args A;
-    A.b = a; A.pairs_sorted = pairs_sorted; A.pair_off = pair_off; A.group_off = group_off; A.total_groups = total_groups;
-    A.item_off = item_off; A.total_items = total_items;
-    A.nlist = nlist; A.max_items = (int)max_items;
+int launch_pq_scan2(const PQScan2Args& A, int vpl, hipStream_t st) {
+    const PQScanArgs& a = A.b;
+    if (a.CB != 16 || A.max_items <= 0) return -1;
     switch (a.Mpad / 16) {
         case 1: return launch_pq_scan2_v<1>(A, vpl, st);
         case 2: return launch_pq_scan2_v<2>(A, vpl, st);
@@ -791,39 +781,41 @@ int pq_lut_pass0_blocks(int64_t nq, int Mpad) { return (int)(((Mpad + LM_MB - 1)
 
 size_t pq_lut8_fused_lds(int M, int Mpad, int dsub) { return ((size_t)Mpad * 256 + (size_t)M * dsub + 3 * (size_t)Mpad) * 4; }
 
-void launch_pq_lut8(const float* lut32, const float* Q32, int ldq, const float* codebooks, int dsub, int64_t nq, int M,
-                    int Mpad, const float* probe_dis0, int nprobe, uint8_t* lut8, void* qparam, void* ws, int transposed,
-                    hipStream_t st, int metric, int phase, float* lut32_out, int mfma, const PairGroupArgs* pg) {
+void launch_pq_lut8(const PQLutArgs& a, hipStream_t st) {
+    const float *lut32 = a.lut32, *Q32 = a.Q32, *codebooks = a.codebooks, *probe_dis0 = a.probe_dis0;
+    const int ldq = a.ldq, dsub = a.dsub, M = a.M, Mpad = a.Mpad, nprobe = a.nprobe, transposed = a.transposed, phase = a.phase, mfma = a.mfma;
+    const int64_t nq = a.nq;
+    uint8_t* lut8 = a.lut8; PQQParam* qparam = (PQQParam*)a.qparam; float* lut32_out = a.lut32_out;
     if (nq <= 0) return;
-    if (metric != 0) {      // L2 (rsx_metric, as FinalizeArgs::metric): a squared difference is no contraction, so never the matrix-core builder
-        if (ws && dsub == 8) {      // the VALU tiles (measured at M = 96, batch 1024: the per-query builder below takes 0.30 ms): two passes + the parameters
-            float* mnmx = reinterpret_cast<float*>(ws);
-            float* errb = mnmx + (size_t)nq * Mpad * 2;
-            const int64_t nmb = (Mpad + LT_MB - 1) / LT_MB, nqt8 = (((nq + LT_QC - 1) / LT_QC) + 7) / 8;
-            const dim3 grid((unsigned)(nmb * nqt8 * 8));
-            const size_t osm = transposed ? (size_t)LT_QC * 256 * LT_MB : 0;
+    // the tiled builds (codebook slices shared by 32 queries): their workspace, grid and output staging
+    const bool tiled = a.ws && dsub == 8;
+    float* mnmx = reinterpret_cast<float*>(a.ws);
+    float* errb = tiled ? mnmx + (size_t)nq * Mpad * 2 : nullptr;
+    const int64_t nmb = (Mpad + LT_MB - 1) / LT_MB, nqt8 = (((nq + LT_QC - 1) / LT_QC) + 7) / 8;
+    const dim3 grid((unsigned)(nmb * nqt8 * 8));
+    const size_t osm = transposed ? (size_t)LT_QC * 256 * LT_MB : 0;
+    if (a.metric != 0) {      // L2 (rsx_metric, as FinalizeArgs::metric): a squared difference is no contraction, so never the matrix-core builder
+        if (tiled) {      // the VALU tiles (measured at M = 96, batch 1024: the per-query builder below takes 0.30 ms): two passes + the parameters
             static DevOnce once_t;
             if (osm) once_t.once([&] { hipFuncSetAttribute((const void*)k_pq_lut_tiled<1, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)osm); });
             hipLaunchKernelGGL((k_pq_lut_tiled<0, true>), grid, dim3(256), 0, st, Q32, ldq, codebooks, M, Mpad, nq, mnmx, errb, lut8, transposed, (float*)nullptr);
             hipLaunchKernelGGL((k_pq_lut_tiled<1, true>), grid, dim3(256), osm, st, Q32, ldq, codebooks, M, Mpad, nq, mnmx, errb, lut8, transposed, lut32_out);
-            hipLaunchKernelGGL(k_pq_qparam, dim3((unsigned)nq), dim3(64), 0, st, nq, M, Mpad, mnmx, errb, probe_dis0, nprobe, (PQQParam*)qparam);
+            hipLaunchKernelGGL(k_pq_qparam, dim3((unsigned)nq), dim3(64), 0, st, nq, M, Mpad, mnmx, errb, probe_dis0, nprobe, qparam);
             return;
         }
         const size_t lds = pq_lut8_fused_lds(M, Mpad, dsub);
         auto kern = dsub == 8 ? k_pq_lut8f<8, true> : k_pq_lut8f<0, true>;
         static DevOnce once8, once0;
         (dsub == 8 ? once8 : once0).once([&] { hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); });
-        hipLaunchKernelGGL(kern, dim3((unsigned)nq), dim3(256), lds, st, Q32, ldq, codebooks, dsub, M, Mpad, probe_dis0, nprobe,
-                           lut8, (PQQParam*)qparam, transposed, lut32_out);
+        hipLaunchKernelGGL(kern, dim3((unsigned)nq), dim3(256), lds, st, Q32, ldq, codebooks, dsub, M, Mpad, probe_dis0, nprobe, lut8, qparam, transposed, lut32_out);
         return;
     }
-    if (phase != 0 && !(ws && dsub == 8 && !lut32)) return;     // only the tiled build splits into tables (1) + per-query parameters (2)
+    if (phase != PQ_LUT_WHOLE && !(tiled && !lut32)) return;     // only the tiled build splits into tables (1) + per-query parameters (2)
     if (lut32) {
-        hipLaunchKernelGGL(k_pq_lut8, dim3((unsigned)nq), dim3(256), 0, st, lut32, M, Mpad, probe_dis0, nprobe, lut8,
-                           (PQQParam*)qparam, transposed);
+        hipLaunchKernelGGL(k_pq_lut8, dim3((unsigned)nq), dim3(256), 0, st, lut32, M, Mpad, probe_dis0, nprobe, lut8, qparam, transposed);
         return;
     }
-    if (ws && dsub == 8) {   // tiled: codebook slices shared by 32 queries
+    if (tiled) {
 #ifdef RSX_MEASURE
         static int lut_step = -1;
         if (lut_step < 0) {
@@ -833,42 +825,35 @@ void launch_pq_lut8(const float* lut32, const float* Q32, int ldq, const float* 
             (void)hipMemcpyToSymbol(HIP_SYMBOL(g_lut_step), &lut_step, sizeof(int));
         }
 #endif
-        float* mnmx = reinterpret_cast<float*>(ws);
-        float* errb = mnmx + (size_t)nq * Mpad * 2;
-        const int64_t nmb = (Mpad + LT_MB - 1) / LT_MB, nqt8 = (((nq + LT_QC - 1) / LT_QC) + 7) / 8;
-        dim3 grid((unsigned)(nmb * nqt8 * 8));
-        const size_t osm = transposed ? (size_t)LT_QC * 256 * LT_MB : 0;
         static DevOnce once;
         if (osm) once.once([&] { hipFuncSetAttribute((const void*)k_pq_lut_tiled<1>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)osm); });
-        if (mfma && phase == 0) {      // matrix-core form: tables + per-query parameters in two launches (needs the coarse scores: phase 0 only)
+        if (mfma && phase == PQ_LUT_WHOLE) {      // matrix-core form: tables + per-query parameters in two launches (needs the coarse scores: phase 0 only)
             const int64_t nmb4 = (Mpad + LM_MB - 1) / LM_MB, nqt4 = (((nq + LM_Q - 1) / LM_Q) + 7) / 8;
             const size_t osm4 = (size_t)LM_Q * 257 * 4;
             const dim3 grid4((unsigned)(nmb4 * nqt4 * 8));
             PairGroupArgs pg0{};
-            if (pg) pg0 = *pg;
+            if (a.pg) pg0 = *a.pg;
             PairGroupArgs pgn{};
             if (mfma != 2)      // 2: pass 0 already ran as extra workgroups of the probe-pick launch (pq_lut_pass0_blocks)
                 hipLaunchKernelGGL(k_pq_lut_mfma<0>, grid4, dim3(256), 0, st, Q32, ldq, codebooks, M, Mpad, nq, mnmx, lut8, transposed,
                                    lut32_out, probe_dis0, nprobe, (PQQParam*)nullptr, pgn);
             hipLaunchKernelGGL(k_pq_lut_mfma<1>, dim3(grid4.x + (unsigned)pg0.nb), dim3(256), osm4, st, Q32, ldq, codebooks, M, Mpad, nq, mnmx, lut8, transposed,
-                               lut32_out, probe_dis0, nprobe, (PQQParam*)qparam, pg0);
+                               lut32_out, probe_dis0, nprobe, qparam, pg0);
             return;
         }
-        if (phase != 2) {
+        if (phase != PQ_LUT_QPARAM) {
             hipLaunchKernelGGL(k_pq_lut_tiled<0>, grid, dim3(256), 0, st, Q32, ldq, codebooks, M, Mpad, nq, mnmx, errb, lut8, transposed, (float*)nullptr);
             hipLaunchKernelGGL(k_pq_lut_tiled<1>, grid, dim3(256), osm, st, Q32, ldq, codebooks, M, Mpad, nq, mnmx, errb, lut8, transposed, lut32_out);
         }
-        if (phase != 1)
-            hipLaunchKernelGGL(k_pq_qparam, dim3((unsigned)nq), dim3(64), 0, st, nq, M, Mpad, mnmx, errb, probe_dis0, nprobe,
-                               (PQQParam*)qparam);
+        if (phase != PQ_LUT_TABLES)
+            hipLaunchKernelGGL(k_pq_qparam, dim3((unsigned)nq), dim3(64), 0, st, nq, M, Mpad, mnmx, errb, probe_dis0, nprobe, qparam);
         return;
     }
     const size_t lds = pq_lut8_fused_lds(M, Mpad, dsub);
     auto kern = dsub == 8 ? k_pq_lut8f<8> : k_pq_lut8f<0>;
     static DevOnce once8, once0;
     (dsub == 8 ? once8 : once0).once([&] { hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); });
-    hipLaunchKernelGGL(kern, dim3((unsigned)nq), dim3(256), lds, st, Q32, ldq, codebooks, dsub, M, Mpad, probe_dis0, nprobe,
-                       lut8, (PQQParam*)qparam, transposed, lut32_out);
+    hipLaunchKernelGGL(kern, dim3((unsigned)nq), dim3(256), lds, st, Q32, ldq, codebooks, dsub, M, Mpad, probe_dis0, nprobe, lut8, qparam, transposed, lut32_out);
 }
 
 // LDS byte offset (code * 4) of byte K of w in ONE instruction: the SDWA form of v_lshlrev selects the
@@ -1071,7 +1056,7 @@ static int launch_pq_scan8_t(const PQScan8Args& A, hipStream_t st) {
     hipLaunchKernelGGL((k_pq_scan8<NCH, VPL, VAR, FILTER>), grid, dim3(1024), shm, st, A);
     return 0;
 }
-template <int NCH, bool FILTER = false>
+template <int NCH, bool FILTER>
 static int launch_pq_scan8_v(const PQScan8Args& A, int vpl, hipStream_t st) {
     switch (vpl) {
         case 16: return launch_pq_scan8_t<NCH, 16, 0, FILTER>(A, st);
@@ -1081,57 +1066,30 @@ static int launch_pq_scan8_v(const PQScan8Args& A, int vpl, hipStream_t st) {
         default: return launch_pq_scan8_t<NCH, 1, 0, FILTER>(A, st);
     }
 }
-// returns 0 on launch, -1 if this (M, layout) has no fast-scan kernel
-int launch_pq_scan8(const PQScanArgs& a, const uint8_t* lut8, const void* qparam, const int32_t* pairs_sorted,
-                    const int32_t* pair_off, const int32_t* group_off, const int32_t* total_groups,
-                    const int32_t* item_off, const int32_t* total_items, int nlist, int64_t max_items, int vpl,
-                    hipStream_t st) {
-    if (a.CB != 16 || max_items <= 0 || max_items > 0x7fffff00 || a.M * 255 >= 65536) return -1;
-    PQScan8Args A;
-    A.b = a; A.lut8 = lut8; A.qp = (const PQQParam*)qparam;
-    A.pairs_sorted = pairs_sorted; A.pair_off = pair_off; A.group_off = group_off; A.total_groups = total_groups;
-    A.item_off = item_off; A.total_items = total_items;
-    A.nlist = nlist; A.max_items = (int)max_items;
-    A.tau_key = nullptr; A.tau_stride = 0; A.cand = nullptr; A.cand_cnt = nullptr; A.cand_cap = 0; A.prune = 0; A.excl = nullptr; A.pace = 0; A.qitems = nullptr; A.qitems_tmax = 0;
+template <bool FILTER>
+static int launch_pq_scan8_m(const PQScan8Args& A, int vpl, hipStream_t st) {
+    switch (A.b.Mpad / 16) {
+        case 1: return launch_pq_scan8_v<1, FILTER>(A, vpl, st);
+        case 2: return launch_pq_scan8_v<2, FILTER>(A, vpl, st);
+        case 3: return launch_pq_scan8_v<3, FILTER>(A, vpl, st);
+        case 4: return launch_pq_scan8_v<4, FILTER>(A, vpl, st);
+        case 6: return launch_pq_scan8_v<6, FILTER>(A, vpl, st);
+        case 8: return launch_pq_scan8_v<8, FILTER>(A, vpl, st);
+        default: return -1;
+    }
+}
+// returns 0 on launch, -1 if this (M, layout) has no fast-scan kernel; filtered iff A.tau_key is set (rsx_internal.h)
+int launch_pq_scan8(const PQScan8Args& A, int vpl, hipStream_t st) {
+    const PQScanArgs& a = A.b;
+    if (a.CB != 16 || A.max_items <= 0 || a.M * 255 >= 65536) return -1;
 #ifdef RSX_MEASURE     // cost-split variants (wrong results on purpose): tools/ builds only, not even instantiated in librsx.so
-    if (a.Mpad == 96 && vpl == 8) {
+    if (!A.tau_key && a.Mpad == 96 && vpl == 8) {
         static const int var = measure_env("RSX_SCAN8_VARIANT", 0);
         if (var == 1) return launch_pq_scan8_t<6, 8, 1>(A, st);
         if (var == 2) return launch_pq_scan8_t<6, 8, 2>(A, st);
     }
 #endif
-    switch (a.Mpad / 16) {
-        case 1: return launch_pq_scan8_v<1>(A, vpl, st);
-        case 2: return launch_pq_scan8_v<2>(A, vpl, st);
-        case 3: return launch_pq_scan8_v<3>(A, vpl, st);
-        case 4: return launch_pq_scan8_v<4>(A, vpl, st);
-        case 6: return launch_pq_scan8_v<6>(A, vpl, st);
-        case 8: return launch_pq_scan8_v<8>(A, vpl, st);
-        default: return -1;
-    }
-}
-
-int launch_pq_scan8_filter(const PQScanArgs& a, const uint8_t* lut8, const void* qparam, const int32_t* pairs_sorted,
-                           const int32_t* pair_off, const int32_t* group_off, const int32_t* total_groups,
-                           const int32_t* item_off, const int32_t* total_items, int nlist, int64_t max_items, int vpl,
-                           const uint64_t* tau_key, int64_t tau_stride, uint64_t* cand, unsigned long long* cand_cnt,
-                           int cand_cap, hipStream_t st) {
-    if (a.CB != 16 || max_items <= 0 || max_items > 0x7fffff00 || a.M * 255 >= 65536) return -1;
-    PQScan8Args A;
-    A.b = a; A.lut8 = lut8; A.qp = (const PQQParam*)qparam;
-    A.pairs_sorted = pairs_sorted; A.pair_off = pair_off; A.group_off = group_off; A.total_groups = total_groups;
-    A.item_off = item_off; A.total_items = total_items;
-    A.nlist = nlist; A.max_items = (int)max_items;
-    A.tau_key = tau_key; A.tau_stride = tau_stride; A.cand = cand; A.cand_cnt = cand_cnt; A.cand_cap = cand_cap; A.prune = 0; A.excl = nullptr; A.pace = 0; A.qitems = nullptr; A.qitems_tmax = 0;
-    switch (a.Mpad / 16) {
-        case 1: return launch_pq_scan8_v<1, true>(A, vpl, st);
-        case 2: return launch_pq_scan8_v<2, true>(A, vpl, st);
-        case 3: return launch_pq_scan8_v<3, true>(A, vpl, st);
-        case 4: return launch_pq_scan8_v<4, true>(A, vpl, st);
-        case 6: return launch_pq_scan8_v<6, true>(A, vpl, st);
-        case 8: return launch_pq_scan8_v<8, true>(A, vpl, st);
-        default: return -1;
-    }
+    return !A.tau_key ? launch_pq_scan8_m<false>(A, vpl, st) : launch_pq_scan8_m<true>(A, vpl, st);
 }
 
 // ---------------------------------------------------------------------------------------

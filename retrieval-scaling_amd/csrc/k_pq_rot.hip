@@ -1663,27 +1663,18 @@ static int launch_pq_scan_sl4_t(const PQScan8Args& A, int vpl, void* desc_ws, in
 }
 
 // returns 0 on launch, -1 if this M has no rotated kernel.  tau_key == null: unfiltered (every score to a.temp).
-int launch_pq_scan_rot(const PQScanArgs& a, const uint8_t* lut8t, const void* qparam, const int32_t* pairs_sorted,
-                       const int32_t* pair_off, const int32_t* group_off, const int32_t* total_groups,
-                       const int32_t* item_off, const int32_t* total_items, int nlist, int64_t max_items, int vpl,
-                       const uint64_t* tau_key, int64_t tau_stride, uint64_t* cand, unsigned long long* cand_cnt,
-                       int cand_cap, void* item_ws, int log_cap, int prune, int pace, const uint16_t* excl, int32_t* qitems,
-                       int qitems_tmax, hipStream_t st, int q8, PQTileSet tiles) {
-    if (!pq_rot_family(a.CB) || !item_ws || log_cap <= 0 || !pq_rot_applies(a.M) || a.M != a.Mpad || max_items <= 0 || max_items > 0x7fffff00) return -1;
-    if (a.CB == PQ_SLICED && (!tau_key || !pq_sliced_applies(a.M))) return -1;      // the sliced layout has the filtered 8-query scan only
+int launch_pq_scan_rot(const PQScan8Args& A0, const PQRotLaunch& r, hipStream_t st) {
+    const PQScanArgs& a = A0.b;
+    const int vpl = r.vpl, log_cap = r.log_cap, q8 = r.q8; void* item_ws = r.item_ws;
+    if (!pq_rot_family(a.CB) || !item_ws || log_cap <= 0 || !pq_rot_applies(a.M) || a.M != a.Mpad || A0.max_items <= 0) return -1;
+    if (a.CB == PQ_SLICED && (!A0.tau_key || !pq_sliced_applies(a.M))) return -1;      // the sliced layout has the filtered 8-query scan only
     // k_pq_scan_sl8 reaches the batch's tables through one buffer descriptor: 32-bit offsets, at most 4 GiB = 174 762 queries at M = 96
     // (DESIGN.md §5); the caller reports a larger batch as unsupported
     if (a.CB == PQ_SLICED && q8 && (a.nq <= 0 || a.nq * 256 * a.M > 0xffffffffll)) return -1;
-    PQScan8Args A;
-    A.b = a; A.lut8 = lut8t; A.qp = (const PQQParam*)qparam;
-    A.pairs_sorted = pairs_sorted; A.pair_off = pair_off; A.group_off = group_off; A.total_groups = total_groups;
-    A.item_off = item_off; A.total_items = total_items;
-    A.nlist = nlist; A.max_items = (int)max_items;
-    A.tau_key = tau_key; A.tau_stride = tau_stride; A.cand = cand; A.cand_cnt = cand_cnt; A.cand_cap = cand_cap;
-    A.prune = prune; A.pace = pace; A.excl = excl; A.qitems = qitems; A.qitems_tmax = qitems_tmax;
-    A.tile_j0 = tiles.j0; A.tile_mul = tiles.mul; A.tile_mod = tiles.mod; A.tile_rows = 1024 * vpl;
+    PQScan8Args A = A0;
+    A.tile_rows = 1024 * vpl;
     const int bpw = 4 * vpl;   // tile = 16 waves x bpw blocks x 16 vectors = 1024 vpl vectors, as k_pq_scan8's
-    const bool f = tau_key != nullptr;
+    const bool f = A.tau_key != nullptr;
     if (a.CB == PQ_SLICED) return q8 ? launch_pq_scan_sl8_t<3, SL8_NB, SL8_RD>(A, vpl, item_ws, log_cap, st) : launch_pq_scan_sl4_t<3>(A, vpl, item_ws, log_cap, st);
     switch (a.M) {
         case 16: return f ? launch_pq_scan_rot16(A, vpl, item_ws, log_cap, st) : launch_pq_scan_rot_t<0, 0, false, 1>(A, vpl, item_ws, log_cap, st);   // 64-vector blocks

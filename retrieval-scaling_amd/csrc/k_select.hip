@@ -1331,16 +1331,14 @@ __global__ __launch_bounds__(1024) void k_group_pairs_1wg(const int32_t* probe_l
     }
 }
 
-void launch_group_pairs(const int32_t* probe_list, int64_t npairs, int nlist, int group_size, int32_t* cnt,
-                        int32_t* cursor, int32_t* pair_off, int32_t* group_off, int32_t* total_groups,
-                        int32_t* pairs_sorted, const int64_t* list_len, int tile_rows, int32_t* item_off,
-                        int32_t* total_items, int nprobe, int jmin, int jmax, int tile_cap, hipStream_t st) {
+void launch_group_pairs(const PairGroupArgs& g, int32_t* cnt, int32_t* cursor, int nprobe, int jmax, hipStream_t st) {
+    const int nlist = g.nlist; const int64_t npairs = g.npairs;
     if (nlist <= GP1_MAX_LISTS && npairs <= 8192) {   // larger batches: the multi-launch form is parallel and faster (32 k pairs: 45 vs 65 us)
         size_t shm = ((size_t)nlist + 64) * 4;
         if (shm > 48 * 1024) hipFuncSetAttribute((const void*)k_group_pairs_1wg, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm);
-        hipLaunchKernelGGL(k_group_pairs_1wg, dim3(1), dim3(1024), shm, st, probe_list, (int)npairs, nlist, group_size, pair_off,
-                           group_off, total_groups, pairs_sorted, list_len, tile_rows, item_off, total_items, nprobe, jmin, jmax,
-                           tile_cap);
+        hipLaunchKernelGGL(k_group_pairs_1wg, dim3(1), dim3(1024), shm, st, g.probe_list, g.npairs, nlist, g.G, g.pair_off,
+                           g.group_off, g.total_groups, g.pairs_sorted, g.list_len, g.tile_rows, g.item_off, g.total_items, nprobe, 0, jmax,
+                           g.tile_cap);
         return;
     }
     if (cursor == cnt + (nlist + 1)) {      // the callers lay the two arrays end to end: one launch
@@ -1349,11 +1347,11 @@ void launch_group_pairs(const int32_t* probe_list, int64_t npairs, int nlist, in
         hipLaunchKernelGGL(k_zero_i32, dim3((nlist + 255) / 256), dim3(256), 0, st, cnt, nlist);
         hipLaunchKernelGGL(k_zero_i32, dim3((nlist + 255) / 256), dim3(256), 0, st, cursor, nlist);
     }
-    hipLaunchKernelGGL(k_pair_hist, dim3((unsigned)((npairs + 255) / 256)), dim3(256), 0, st, probe_list, npairs, nprobe, jmin, jmax, cnt);
-    hipLaunchKernelGGL(k_pair_scan, dim3(1), dim3(1024), 0, st, cnt, nlist, group_size, pair_off, group_off, total_groups,
-                       list_len, tile_rows, tile_cap, item_off, total_items);
-    hipLaunchKernelGGL(k_pair_scatter, dim3((unsigned)((npairs + 255) / 256)), dim3(256), 0, st, probe_list, npairs,
-                       nprobe, jmin, jmax, pair_off, cursor, pairs_sorted);
+    hipLaunchKernelGGL(k_pair_hist, dim3((unsigned)((npairs + 255) / 256)), dim3(256), 0, st, g.probe_list, npairs, nprobe, 0, jmax, cnt);
+    hipLaunchKernelGGL(k_pair_scan, dim3(1), dim3(1024), 0, st, cnt, nlist, g.G, g.pair_off, g.group_off, g.total_groups,
+                       g.list_len, g.tile_rows, g.tile_cap, g.item_off, g.total_items);
+    hipLaunchKernelGGL(k_pair_scatter, dim3((unsigned)((npairs + 255) / 256)), dim3(256), 0, st, g.probe_list, npairs,
+                       nprobe, 0, jmax, g.pair_off, cursor, g.pairs_sorted);
 }
 
 // ---------------------------------------------------------------------------------------

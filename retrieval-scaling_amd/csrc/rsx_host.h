@@ -191,7 +191,6 @@ struct rsx_index {
     float sq_vdmax = 0.0f;                        // the largest vdiff_j
     unsigned int sq_bn2 = 0;                      // the largest sum_j (code_j - 128)^2 of a row ever stored (with max_norm2).  Like max_norm2 of the
                                                   // row kinds, both survive rsx_reset: maxima over everything EVER stored — conservative for the certificate
-    float sq_cmax = 0.0f; uint64_t sq_cmax_gen = ~0ull;   // >= the largest centroid norm, of centroid set sq_cmax_gen (by_residual certificate term)
     DevBuf w_sqhi, w_sqlo, w_sqc;                 // per-batch query factors (k_sq_query_factors)
     bool trained = false;
     int64_t ntotal = 0;
@@ -213,7 +212,8 @@ struct rsx_index {
     DevBuf d_centroids, d_codebooks;
     DevBuf cent16;            // fp16 copy of the centroids, [round_up(nlist, 128)][ld] zero padded: the fast coarse quantiser's operand (built on demand)
     uint64_t cent_gen = 0, cent16_gen = 0;   // set_centroids counts; the copy belongs to cent16_gen
-    float cent_cmax = 0.0f;   // >= the largest centroid norm (with the copy)
+    float cent_cmax = 0.0f; uint64_t cent_cmax_gen = ~0ull;   // >= the largest centroid norm, of centroid set cent_cmax_gen (api_search.hip: cent_cmax; the fast
+                                                              // coarse quantiser's bound and the by_residual scalar quantiser's certificate term)
     int coarse_fast = 1;      // coarse quantiser: fp16 MFMA scores + exact re-score of the candidates (k_coarse_pick), 0 = the exact GEMM for all lists
 
     // storage.  PQ: slab layout bytes.  Flat/IVFFlat: rows of ld elements (fp16 or fp32).

@@ -143,7 +143,7 @@ __host__ __device__ inline int64_t pq_code_addr(int64_t row, int m, int Mpad, in
 __host__ __device__ inline bool pq_rot_applies(int M) { return M == 16 || (M % 32 == 0 && M >= 32 && M <= 128); }
 __host__ __device__ inline bool pq_sliced_applies(int M) { return M == 96; }      // the M whose 8-query table (M * 2 KiB) exceeds the LDS
 __host__ __device__ inline bool pq_rot_family(int CB) { return CB == 0 || CB == PQ_SLICED; }
-// 8-bit table layouts (launch_pq_lut8 `transposed`): 0 = [q][m][code] (granule scans), 1 = [q][code][m] (rotated layout: a code's row feeds
+// 8-bit table layouts (PQLutArgs::transposed): 0 = [q][m][code] (granule scans), 1 = [q][code][m] (rotated layout: a code's row feeds
 // the table image), 2 = [q][slice m >> 5][code][m & 31] (sliced layout: the 8 KiB table of one (query, slice) is contiguous — the scan
 // re-stages single slices, and a [code][m] table would hand it a third of every cache line it touches)
 __host__ __device__ inline int64_t pq_lut8_index(int64_t q, int c, int m, int Mpad, int mode) {
@@ -298,39 +298,38 @@ struct PQScanArgs {
 int launch_pq_scan(const PQScanArgs& a, hipStream_t st);  // returns 0, or -1 if the LDS request cannot be met
 // IVF-PQ, METRIC_L2: per-(query, list) table of squared sub-vector distances built in LDS, exact scan, scores = -distance (k_pq_rot.hip)
 int launch_pq_scan_l2(const PQScanArgs& a, const float* Q32, int ldq, const float* centroids, const float* codebooks, int d, int dsub, hipStream_t st);
-// list-major two-queries-per-LDS-read scan; pairs grouped by list in groups of 2 (launch_group_pairs)
-int launch_pq_scan2(const PQScanArgs& a, const int32_t* pairs_sorted, const int32_t* pair_off, const int32_t* group_off,
-                    const int32_t* total_groups, const int32_t* item_off, const int32_t* total_items, int nlist,
-                    int64_t max_items, int vpl, hipStream_t st);
+// list-major two-queries-per-LDS-read scan (k_pq_scan2); pairs grouped by list in groups of 2 (launch_group_pairs)
+struct PQScan2Args {
+    PQScanArgs b;
+    const int32_t* pairs_sorted; const int32_t* pair_off; const int32_t* group_off; const int32_t* total_groups;
+    const int32_t* item_off; const int32_t* total_items;   // work items = (list, tile, group), list-major
+    int nlist; int max_items;
+};
+int launch_pq_scan2(const PQScan2Args& A, int vpl, hipStream_t st);   // returns 0 on launch, -1 if this (M, layout) has no v2 kernel or max_items <= 0
 // 8-bit table fast scan (4 queries per LDS read) — approximate scores, certified by k_finalize
-// lut32 null -> fused form: the fp32 table is built in LDS from Q32 [nq, ldq] and the codebooks (needs
-// pq_lut8_fused_lds(M, Mpad, dsub) <= 160 KiB); otherwise quantises the given fp32 tables.
 struct PairGroupArgs;
 size_t pq_lut8_fused_lds(int M, int Mpad, int dsub);
-void launch_pq_lut8(const float* lut32, const float* Q32, int ldq, const float* codebooks, int dsub, int64_t nq, int M,
-                    int Mpad, const float* probe_dis0, int nprobe, uint8_t* lut8,
-                    void* qparam /* [nq] {scale, bias, eps, pad} */,
-                    void* ws /* pq_lut8_tiled_ws(nq, Mpad) bytes -> tiled build (dsub 8), or null */,
-                    int transposed /* pq_lut8_index: 0: lut8 [nq][Mpad][256]; 1: [nq][256][Mpad] (rotated-layout scans); 2: [nq][Mpad/32][256][32] (sliced) */, hipStream_t st,
-                    int metric /* rsx_metric; 1 = L2 (IndexPQ only: Q32 is the residual to a zero centroid): negated squared-distance tables by the
-                                  VALU builders only (tiled when ws is given and dsub = 8, else per query), whatever phase / mfma say */,
-                    int phase = 0 /* tiled build only: 1 = the tables (independent of the probe selection), 2 = the per-query parameters */,
-                    float* lut32_out = nullptr /* fused forms only: also store the fp32 tables [nq][Mpad][256] (k_pq_final_tab reads them) */,
-                    int mfma = 0 /* tiled build, phase 0: the matrix-core form (k_pq_lut_mfma: tables and per-query parameters in two launches; 2: its
-                                    first pass already ran in the probe-pick launch) */,
-                    const struct PairGroupArgs* pg = nullptr /* matrix-core form: also group the (query, probe) pairs by list (extra workgroups) */);
+enum { PQ_LUT_WHOLE = 0, PQ_LUT_TABLES = 1, PQ_LUT_QPARAM = 2 };     // PQLutArgs::phase
+struct PQLutArgs {
+    const float* lut32;        // null -> fused form: the fp32 table is built in LDS from Q32 [nq, ldq] and the codebooks (needs
+                               // pq_lut8_fused_lds(M, Mpad, dsub) <= 160 KiB); otherwise quantises the given fp32 tables
+    const float* Q32; int ldq; const float* codebooks; int dsub; int64_t nq; int M; int Mpad;
+    const float* probe_dis0; int nprobe;
+    uint8_t* lut8;
+    void* qparam;              // [nq] {scale, bias, eps, pad}
+    void* ws;                  // pq_lut8_tiled_ws(nq, Mpad) bytes -> tiled build (dsub 8), or null
+    int transposed;            // pq_lut8_index: 0: lut8 [nq][Mpad][256]; 1: [nq][256][Mpad] (rotated-layout scans); 2: [nq][Mpad/32][256][32] (sliced)
+    int metric;                // rsx_metric; 1 = L2 (IndexPQ only: Q32 is the residual to a zero centroid): negated squared-distance tables by the
+                               // VALU builders only (tiled when ws is given and dsub = 8, else per query), whatever phase / mfma say
+    int phase;                 // tiled build only: PQ_LUT_TABLES = the tables (independent of the probe selection), PQ_LUT_QPARAM = the per-query parameters
+    float* lut32_out;          // fused forms only: also store the fp32 tables [nq][Mpad][256] (k_pq_final_tab reads them)
+    int mfma;                  // tiled build, phase 0: the matrix-core form (k_pq_lut_mfma: tables and per-query parameters in two launches; 2: its
+                               // first pass already ran in the probe-pick launch)
+    const PairGroupArgs* pg;   // matrix-core form: also group the (query, probe) pairs by list (extra workgroups)
+};
+void launch_pq_lut8(const PQLutArgs& a, hipStream_t st);
 size_t pq_lut8_tiled_ws(int64_t nq, int Mpad);
 int pq_lut_pass0_blocks(int64_t nq, int Mpad);      // workgroups of pass 0 of the matrix-core form (mfma = 2: they already ran elsewhere)
-int launch_pq_scan8(const PQScanArgs& a, const uint8_t* lut8, const void* qparam, const int32_t* pairs_sorted,
-                    const int32_t* pair_off, const int32_t* group_off, const int32_t* total_groups,
-                    const int32_t* item_off, const int32_t* total_items, int nlist, int64_t max_items, int vpl,
-                    hipStream_t st);
-// filtered variant: instead of storing every score, append keys > tau_key[q] to cand[q][..cap) (count in cand_cnt[q])
-int launch_pq_scan8_filter(const PQScanArgs& a, const uint8_t* lut8, const void* qparam, const int32_t* pairs_sorted,
-                           const int32_t* pair_off, const int32_t* group_off, const int32_t* total_groups,
-                           const int32_t* item_off, const int32_t* total_items, int nlist, int64_t max_items, int vpl,
-                           const uint64_t* tau_key, int64_t tau_stride, uint64_t* cand, unsigned long long* cand_cnt,
-                           int cand_cap, hipStream_t st);
 // shared by the list-major IVF-PQ scans (k_pq.hip, k_pq_rot.hip)
 struct PQQParam { float scale, bias, eps, pad; };   // pad: the largest integer table sum this query's u8 table can produce
 struct PQScan8Args {
@@ -352,9 +351,11 @@ struct PQScan8Args {
     // list's tile count, tile_mul coprime to it: consecutive numbers are spread over the whole list and the stages' sets are disjoint.
     // The item then describes its tile as a list of its own (base row, length <= tile_rows, tile 0, candidate offset): the scans' 32-bit byte
     // offsets stay inside the tile.
-    int tile_j0 = 0, tile_mul = 0, tile_mod = 0, tile_rows = 0;
+    int tile_j0, tile_mul, tile_mod, tile_rows;       // tile_rows: set by launch_pq_scan_rot (1024 vpl)
 };
-struct PQTileSet { int j0 = 0, mul = 0, mod = 0; };
+// returns 0 on launch, -1 if this (M, layout) has no fast-scan kernel or max_items <= 0; filtered (keys > tau_key[q] appended to cand[q][..cap),
+// count in cand_cnt[q], instead of every score stored) iff A.tau_key is set
+int launch_pq_scan8(const PQScan8Args& A, int vpl, hipStream_t st);
 
 // Work-item decode shared by the list-major scans.  Items are ordered (list, tile, group) so that the
 // query groups of one list-tile (same codes) are adjacent; XCD c takes the contiguous item range
@@ -378,15 +379,16 @@ __device__ inline bool pq_decode_item(const int32_t* item_off, const int32_t* gr
     return true;
 }
 
-// rotated-layout (CB = 0) scans: k_pq_rot.hip.  lut8 is TRANSPOSED there: [nq][256][M] (see launch_pq_lut8's `transposed`)
-int launch_pq_scan_rot(const PQScanArgs& a, const uint8_t* lut8t, const void* qparam, const int32_t* pairs_sorted,
-                       const int32_t* pair_off, const int32_t* group_off, const int32_t* total_groups,
-                       const int32_t* item_off, const int32_t* total_items, int nlist, int64_t max_items, int vpl,
-                       const uint64_t* tau_key, int64_t tau_stride, uint64_t* cand, unsigned long long* cand_cnt,
-                       int cand_cap, void* item_ws /* pq_scan_rot_ws(max_items, log_cap, pq_scan_rot_max_wgs(M)) bytes */, int log_cap, int prune, int pace,
-                       const uint16_t* excl, int32_t* qitems /* non-null: fill it and leave the runs for k_pq_gather_select */,
-                       int qitems_tmax, hipStream_t st, int q8 = 0 /* filtered M = 64: eight queries per work item (pq_scan_rot_ngq) */,
-                       PQTileSet tiles = PQTileSet() /* mod > 0: the launch covers that set of tiles (PQScan8Args::tile_mod) */);
+// rotated-layout (CB = 0) scans: k_pq_rot.hip.  lut8 is TRANSPOSED there: [nq][256][M] (see PQLutArgs::transposed)
+struct PQRotLaunch {
+    int vpl;
+    void* item_ws;     // pq_scan_rot_ws(max_items, log_cap, pq_scan_rot_max_wgs(M)) bytes
+    int log_cap;
+    int q8;            // filtered M = 64: eight queries per work item (pq_scan_rot_ngq)
+};
+// returns 0 on launch, -1 if this M has no rotated kernel.  A.tau_key == null: unfiltered (every score to A.b.temp); A.qitems non-null: fill
+// it and leave the runs for k_pq_gather_select; A.tile_mod > 0: the launch covers that set of tiles
+int launch_pq_scan_rot(const PQScan8Args& A, const PQRotLaunch& r, hipStream_t st);
 // Survivors of the filtered scan (round 4): every (persistent workgroup, wave, query slot) appends to its own LOG of log_cap keys;
 // an 8-byte descriptor per (item, wave, slot) = {index of the run's first key in the log pool, keys stored | bit 31: keys were
 // dropped because the log was full} lets the gather / compaction kernels find an item's runs.
@@ -564,11 +566,6 @@ void launch_coarse_approx(const __half* Q16, int64_t nq_pad, const __half* C16, 
 void launch_coarse_pick(const CoarsePickArgs& a, int64_t nq, hipStream_t st);
 void launch_probe_setup(const uint64_t* probe_keys, int KPp, int64_t nq, int nprobe, const int64_t* list_len,
                         int pad_to, int32_t* probe_list, float* probe_dis0, int64_t* seg_start, hipStream_t st);
-// tile_rows > 0: also build the (list, tile, group) work-item table: item_off[nlist+1], total_items
-void launch_group_pairs(const int32_t* probe_list, int64_t npairs, int nlist, int group_size, int32_t* cnt,
-                        int32_t* cursor, int32_t* pair_off, int32_t* group_off, int32_t* total_groups,
-                        int32_t* pairs_sorted, const int64_t* list_len, int tile_rows, int32_t* item_off,
-                        int32_t* total_items, int nprobe, int jmin, int jmax, int tile_cap, hipStream_t st);
 // The same grouping as EXTRA WORKGROUPS of another launch (round 6): the four launches above are ~24 us of launch floors and round trips in
 // front of the scan for a few microseconds of work.  Blocks 0 .. nb - 1 of the host kernel (k_pq_lut_mfma<1>: it follows the probe
 // selection in stream order and has LDS to spare) each own nlist / nb consecutive lists: histogram of their lists over ALL pairs in LDS,
@@ -582,6 +579,9 @@ struct PairGroupArgs {
     int npairs, nlist, G, tile_rows, tile_cap, nb;
     uint32_t epoch;
 };
+// The grouping in launches of its own, of the pairs with probe rank < jmax (flags / nb / epoch unused).  cnt, cursor: [nlist + 1] scratch each.
+// tile_rows > 0: also build the (list, tile, group) work-item table: item_off[nlist+1], total_items
+void launch_group_pairs(const PairGroupArgs& g, int32_t* cnt, int32_t* cursor, int nprobe, int jmax, hipStream_t st);
 #define PG_BLOCKS 32
 #define PG_MAX_LPB 2048                 // lists per block the LDS histogram holds (nlist <= 65536 with 32 blocks)
 #define PG_MAX_PAIRS 131072             // every block reads all pairs twice
