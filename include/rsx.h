@@ -247,7 +247,7 @@ int rsx_get(rsx_index_t* h, const char* key, int64_t* out);
  * scan + selection launches), "lut_tiled" (IVFPQ fast scan, dsub = 8: 1 = 8-bit tables built by
  * codebook-slice tiles shared by 32 queries [default], 0 = one workgroup per query), "flat_filter" (Flat: 1 = one filtered GEMM launch after the first chunk [default], 0 = score buffer
  * per chunk), "pq_flat_first" / "pq_flat_growth" / "pq_flat_max_stages" (IndexPQ staged scan: rows of the first stage, 0 =
- * default; percent by which each stage outgrows the one before, 0 = default 300; most stages, 0 = default 12), "profile" (1 = record stage timings with HIP
+ * default; percent by which each stage outgrows the one before, 0 = default 300; most stages, 0 = default 12), "range_cand_cap" (rsx_range_search: keys a query's candidate row holds in the first scan, 0 = default 65536), "profile" (1 = record stage timings with HIP
  * events on the library's stream; 2 = additionally count the vectors each search scanned). */
 /* Build-time knob (IVF indexes, before the first add): "add_list_mod" = N, "add_list_rem" = r make this handle a LIST
  * shard of an N-way multi-GPU index: rsx_add assigns every vector of the stream (sequential ids keep counting all
@@ -315,6 +315,39 @@ int rsx_search_prepass_sel(rsx_index_t* h, int64_t nq, const void* q, int dtype,
  * kc > 4096 (RSX_ERR_UNSUPPORTED), k < 1 or k > kc (RSX_ERR_INVALID).  rsx_get_timing: "refine_calls", "refine_candidates" (nq * kc,
  * summed) and, with "profile" = 1, "refine_ms" (HIP events around the call's launches). */
 int rsx_refine(rsx_index_t* flat, int64_t nq, const void* q, int dtype, int kc, const int64_t* labels, int k, float* D, int64_t* I);
+
+/* ---- range search (FAISS Index::range_search) -------------------------------------- */
+
+/* faiss RangeSearchResult: the library-owned answer of one rsx_range_search, whose size is known only after the scan.  It lives in
+ * DEVICE memory (on the handle's device) when the queries were a device pointer, else in host memory; it stays valid until
+ * rsx_range_result_destroy and does not depend on the handle. */
+typedef struct rsx_range_result rsx_range_result_t;
+
+/* Index::range_search(n, x, radius, result) of IndexFlat / IndexFlatIP / IndexFlatL2 and IndexIVFFlat (sequential and explicit ids):
+ * every stored vector within the radius of every query.  The reference has no call of it (its thresholds are applied after a top-k
+ * search, src/search.py:519-527); FAISS's GPU indexes do not offer it.  DESIGN.md section 7g.
+ *   membership  inner product: score > radius;  L2: squared distance < radius — strict, in fp32, on the canonical exact value (fp64
+ *               accumulation of the exact products, rounded once: what rsx_search returns for that row).  IVF-Flat compares the rows
+ *               of the query's nprobe probed lists, the probes rsx_search would take; nprobe_override > 0 replaces the handle's nprobe
+ *               for this call (ignored by Flat), 0 keeps it.  A query with a NaN or infinite component owns nothing.
+ *   order       inside a query best first, equal values by id ascending (FAISS leaves the order open).
+ *   exactness   every result is exact — there is no uncertified outcome: the scans' fixed per-query threshold admits every member
+ *               (the proven bound of the fp16 scans plus rounding margins), an exact re-score decides.  A query with more candidates
+ *               than a first-pass row holds ("range_cand_cap" keys, default 65536, rounded up to a power of two) is scanned again
+ *               with a row sized from its count, in groups that fit "temp_budget_mb"; a row that cannot fit ends the call with
+ *               RSX_ERR_OOM and leaves the handle usable.
+ * nq = 0 gives lims = [0]; an empty index all-zero lims.  RSX_ERR_INVALID: a non-finite radius, an open two-call search.
+ * RSX_ERR_UNSUPPORTED, the handle untouched: IVF-PQ, IndexPQ and IndexIVFScalarQuantizer handles, sharded handles, an IVF-Flat
+ * handle whose rows had to be widened to fp32 (no filtered list scan).  rsx_get_timing: "range_candidates", "range_results",
+ * "range_overflow_queries" (summed over the calls) and, with "profile" > 0, "range_ms" / "range_backend_ms" (HIP events). */
+int rsx_range_search(rsx_index_t* h, int64_t nq, const void* q, int dtype, float radius, int nprobe_override, rsx_range_result_t** out);
+/* The fields of a RangeSearchResult (any out pointer may be NULL): nq; total = lims[nq]; on_device (1: lims / D / I are device pointers);
+ * lims int64 [nq + 1] with lims[0] = 0 (FAISS: size_t) — query i owns D[lims[i] .. lims[i + 1]) float32 (RangeSearchResult::distances)
+ * and I[..] int64 (RangeSearchResult::labels).  D and I are NULL when total = 0. */
+int rsx_range_result_get(const rsx_range_result_t* r, int64_t* nq, int64_t* total, int* on_device, const int64_t** lims, const float** D,
+                         const int64_t** I);
+/* delete of a RangeSearchResult; NULL is accepted */
+int rsx_range_result_destroy(rsx_range_result_t* r);
 
 /* ---- removal (FAISS Index::remove_ids) --------------------------------------------- */
 

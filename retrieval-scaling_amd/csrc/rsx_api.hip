@@ -3,6 +3,7 @@
 // CPU search path.
 #include <atomic>
 #include "rsx_host.h"
+#include "rsx_range.h"
 
 thread_local std::string g_err;
 
@@ -67,7 +68,7 @@ static int search_prepass_common(rsx_index_t* h, int64_t nq, const void* q, int 
 extern "C" {
 
 const char* rsx_last_error(void) { return g_err.c_str(); }
-int rsx_version(void) { return 1005; }     // 1001: filtered search (rsx_selector_*, rsx_search_sel, rsx_search_prepass_sel); 1002: rsx_remove_ids; 1003: rsx_pq_create; 1004: rsx_refine; 1005: rsx_ivfsq_create
+int rsx_version(void) { return 1006; }     // 1001: filtered search (rsx_selector_*, rsx_search_sel, rsx_search_prepass_sel); 1002: rsx_remove_ids; 1003: rsx_pq_create; 1004: rsx_refine; 1005: rsx_ivfsq_create; 1006: rsx_range_search, rsx_range_result_get, rsx_range_result_destroy
 
 int rsx_device_count(int* n) {
     return guarded([&] {
@@ -382,6 +383,42 @@ int rsx_refine(rsx_index_t* h, int64_t nq, const void* q, int dtype, int kc, con
     });
 }
 
+int rsx_range_search(rsx_index_t* h, int64_t nq, const void* q, int dtype, float radius, int nprobe_override, rsx_range_result_t** out) {
+    return guarded([&] {
+        if (!h || !out) RSX_THROW(RSX_ERR_INVALID, "range_search: null pointer");
+        *out = nullptr;
+        refuse_while_two_call(h, "range_search");
+        if (dtype != RSX_F32 && dtype != RSX_F16) RSX_THROW(RSX_ERR_INVALID, "range_search: bad dtype %d", dtype);
+        if (nprobe_override < 0) RSX_THROW(RSX_ERR_INVALID, "range_search: nprobe override must be positive or 0 (got %d)", nprobe_override);
+        if (is_sharded(h)) RSX_THROW(RSX_ERR_UNSUPPORTED, "range_search: not available on a sharded handle in this build");
+        if (public_kind(h) != RSX_KIND_FLAT && public_kind(h) != RSX_KIND_IVFFLAT)
+            RSX_THROW(RSX_ERR_UNSUPPORTED, "range_search: available on Flat and IVF-Flat handles only in this build (this handle's kind is %d)", public_kind(h));
+        use_device(h);
+        SelScope sc(h, nullptr, h->kind == KIND_IVFFLAT ? nprobe_override : 0);
+        *out = range_impl(h, nq, q, dtype, radius);
+    });
+}
+int rsx_range_result_get(const rsx_range_result_t* r, int64_t* nq, int64_t* total, int* on_device, const int64_t** lims, const float** D, const int64_t** I) {
+    return guarded([&] {
+        if (!r) RSX_THROW(RSX_ERR_INVALID, "range_result_get: null result");
+        if (nq) *nq = r->nq;
+        if (total) *total = r->total;
+        if (on_device) *on_device = r->on_device;
+        if (lims) *lims = r->on_device ? r->d_lims->as<int64_t>() : r->h_lims.data();
+        if (D) *D = r->on_device ? (r->d_D ? r->d_D->as<float>() : nullptr) : r->h_D.data();
+        if (I) *I = r->on_device ? (r->d_I ? r->d_I->as<int64_t>() : nullptr) : r->h_I.data();
+    });
+}
+int rsx_range_result_destroy(rsx_range_result_t* r) {
+    return guarded([&] {
+        if (!r) return;
+        int prev = -1;
+        if (r->on_device && hipGetDevice(&prev) == hipSuccess && prev != r->device) (void)hipSetDevice(r->device); else prev = -1;
+        delete r;
+        if (prev >= 0) (void)hipSetDevice(prev);      // the caller's current device is left as it was
+    });
+}
+
 int rsx_remove_ids(rsx_index_t* h, const rsx_selector_t* sel, int64_t* nremoved) {
     return guarded([&] {
         if (!h || !sel || !nremoved) RSX_THROW(RSX_ERR_INVALID, "null pointer");
@@ -609,6 +646,7 @@ int rsx_set_param(rsx_index_t* h, const char* key, double value) {
         else if (s == "ivf_overflow_max") h->ivf_overflow_max = std::max(0, (int)value);
         else if (s == "flat_stages") h->flat_stages = std::max(0, (int)value);
         else if (s == "flat_cert") h->flat_cert = (int)value;
+        else if (s == "range_cand_cap") h->range_cand_cap = std::max(0, (int)value);
         else if (s == "profile") { h->profile = (int)value; h->timing.clear(); }
         else if (s == "temp_budget_mb") h->temp_budget = (int64_t)value << 20;
         else RSX_THROW(RSX_ERR_INVALID, "unknown parameter '%s'", key);

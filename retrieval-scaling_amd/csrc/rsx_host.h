@@ -3,6 +3,7 @@
 //   api_build.hip    HBM layout management, add / train, list import / export, persistence
 //   api_search.hip   the search drivers (search_batch = one internal batch, search_impl = one rsx_search call)
 //   api_refine.hip   rsx_refine: exact re-ranking of candidate labels against a Flat row store (k_refine.hip)
+//   api_range.hip    rsx_range_search: every neighbour within a radius, Flat and IVF-Flat (k_range.hip; declarations in rsx_range.h)
 //   api_sharded.hip  the single-process multi-GPU handle
 //   api_remove.hip   rsx_remove_ids: the removal plan and compaction (k_remove.hip) on a handle and on the shards of one
 //   rsx_api.hip      the extern "C" entry points
@@ -274,12 +275,14 @@ struct rsx_index {
     int ivf_filter = 1;   // IVF-Flat: candidates filtered inside the list scan (0 = full score rows + select)
     int ivf_pre_lists = 0;   // IVF-Flat threshold sample at large K': closest lists sampled (0 = 2)
     int ivf_pre_mult = 4;    // ... and rows of each per K'
+    int range_cand_cap = 0;  // range search: keys a query's candidate row holds in the first scan (0 = 65536; rounded up to a power of two); queries with more are scanned again with rows sized from their counts
     int profile = 0;
     int64_t temp_budget = (int64_t)16 << 30;
 
     // workspace
     DevBuf w_q32, w_q16, w_coarse, w_keys1, w_probekeys, w_probelist, w_dis0, w_segstart, w_temp, w_lut, w_lutws, w_pgflags, w_state,
-        w_D, w_I, w_qin, w_pairs, w_flag, w_x, w_partial, w_assign, w_dest, w_idsin, w_misc, w_lut8, w_qparam, w_uncertain, w_fbq, w_fbD, w_fbI, w_cand, w_candcnt, w_itemdesc, w_tau, w_excl, w_state2, w_addcnt, w_addstart, w_qitems, w_tiews, w_stagedir, w_rlabels, w_rflag;
+        w_D, w_I, w_qin, w_pairs, w_flag, w_x, w_partial, w_assign, w_dest, w_idsin, w_misc, w_lut8, w_qparam, w_uncertain, w_fbq, w_fbD, w_fbI, w_cand, w_candcnt, w_itemdesc, w_tau, w_excl, w_state2, w_addcnt, w_addstart, w_qitems, w_tiews, w_stagedir, w_rlabels, w_rflag,
+        w_rg_cnt, w_rg_nmem, w_rg_lims, w_rg_kptr;      // range search: per-row candidate counts, member counts, the batch's lims, the rows' key pointers
     std::vector<int32_t> stage_host;      // IndexPQ staged scan: host image of w_stagedir (the stages' item tables), alive while the copy runs
     std::map<std::string, double> timing;
 

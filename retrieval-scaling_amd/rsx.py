@@ -12,6 +12,7 @@ written against `faiss`:
     faiss.IndexPQ(d,M,nbits,METRIC_IP)    contriever/src/index.py:19     rsx.IndexPQ(...)
     faiss.IndexRefineFlat(base)           (factory "...,RFlat")          rsx.IndexRefineFlat(base)
     index.train / add / search / nprobe / ntotal / is_trained            same
+    index.range_search(x, radius)         (faiss.Index verb; Flat, IVF-Flat) same, lims as int64
     faiss.read_index / write_index                                        rsx.read_index / write_index
     StandardGpuResources / GpuClonerOptions / index_cpu_to_gpu / index_gpu_to_cpu
         (ivf_flat.py:155-163: CUDA-only training clone)                   identity shims — the index
@@ -47,6 +48,7 @@ ABI_SYMBOLS = [
     "rsx_selector_create", "rsx_selector_destroy", "rsx_selector_is_member", "rsx_search_sel", "rsx_search_prepass_sel",
     "rsx_remove_ids", "rsx_refine",
     "rsx_ivfsq_create", "rsx_set_sq_trained", "rsx_get_sq_trained",
+    "rsx_range_search", "rsx_range_result_get", "rsx_range_result_destroy",
 ]
 
 
@@ -494,6 +496,55 @@ class Index:
         call(D.ctypes.data_as(ctypes.c_void_p), I.ctypes.data_as(ctypes.c_void_p))
         return D, I
 
+    def range_search(self, x, radius, *, params=None):
+        """faiss.Index.range_search(x, radius) -> (lims, D, I): every stored vector with score > radius (inner product) or squared
+        distance < radius (L2) — strict, on the exact fp32 value `search` returns for that row; IVF-Flat over the rows of the nprobe
+        probed lists.  lims int64 [n + 1] with lims[0] = 0: query i owns D[lims[i]:lims[i+1]] (float32) and I[lims[i]:lims[i+1]] (int64),
+        best first, equal values by id ascending.  FAISS returns lims as uint64; int64 here, so that CUDA tensors can carry it.
+        numpy in -> numpy out, CUDA tensor in -> CUDA tensors out.  IndexFlat* and IndexIVFFlat only (rsx_range_search); params:
+        SearchParameters / SearchParametersIVF without a selector (nprobe replaces index.nprobe for the call)."""
+        if not isinstance(self, (IndexFlat, IndexIVFFlat)):
+            raise RuntimeError(f"range_search: not available on {type(self).__name__} in this build (IndexFlat* and IndexIVFFlat only)")
+        nprobe = 0
+        if params is not None:
+            sel, nprobe, _ = _resolve_params(params, isinstance(self, _IndexIVF))
+            if sel is not None:
+                raise RuntimeError("range_search: a params object that carries a selector is not supported in this build")
+        keep, p, n, dt, on_dev = _as_matrix(x, self.d, "range_search")
+        _sync_producer(keep, on_dev)
+        r = ctypes.c_void_p()
+        _check(lib().rsx_range_search(self._h, ctypes.c_int64(n), p, dt, ctypes.c_float(float(radius)), int(nprobe), ctypes.byref(r)))
+        try:
+            total, dev = ctypes.c_int64(0), ctypes.c_int(0)
+            pl, pD, pI = ctypes.c_void_p(), ctypes.c_void_p(), ctypes.c_void_p()
+            _check(lib().rsx_range_result_get(r, None, ctypes.byref(total), ctypes.byref(dev), ctypes.byref(pl), ctypes.byref(pD), ctypes.byref(pI)))
+            total = total.value
+            if dev.value:      # the result lives in device memory: cloned into tensors before it is destroyed
+                import torch
+
+                def take(ptr, count, typestr, dtype):
+                    if count == 0 or not ptr.value:
+                        return torch.empty((0,), dtype=dtype, device=keep.device)
+
+                    class _View:      # the library's memory through the CUDA array interface
+                        __cuda_array_interface__ = {"shape": (count,), "typestr": typestr, "data": (ptr.value, False), "version": 2}
+                    return torch.as_tensor(_View(), device=keep.device).clone()
+                out = take(pl, n + 1, "<i8", torch.int64), take(pD, total, "<f4", torch.float32), take(pI, total, "<i8", torch.int64)
+                torch.cuda.current_stream(keep.device).synchronize()
+                return out if on_dev else tuple(a.cpu().numpy() for a in out)
+
+            def take(ptr, count, ctype, dtype):
+                if count == 0 or not ptr.value:
+                    return np.empty((0,), dtype=dtype)
+                return np.ctypeslib.as_array(ctypes.cast(ptr, ctypes.POINTER(ctype)), shape=(count,)).astype(dtype, copy=True)
+            out = take(pl, n + 1, ctypes.c_int64, np.int64), take(pD, total, ctypes.c_float, np.float32), take(pI, total, ctypes.c_int64, np.int64)
+            if on_dev:         # a host result for CUDA-tensor queries (an empty batch has no device pointer to tell by): tensors on the queries' device
+                import torch
+                return tuple(torch.as_tensor(a).to(keep.device) for a in out)
+            return out
+        finally:
+            lib().rsx_range_result_destroy(r)
+
     def search_prepass(self, x, k, params=None):
         """First half of a two-call search (rsx_search_prepass): CUDA-tensor queries in -> a CUDA int64 tensor VIEW of the nq
         threshold keys (or None when this search has none).  The keys are unsigned 64-bit integers: flip the sign bit
@@ -840,6 +891,9 @@ class IndexRefineFlat:
 
     def remove_ids(self, x):
         raise RuntimeError("IndexRefineFlat: remove_ids not implemented for this type of index (FAISS's IndexRefine has none)")
+
+    def range_search(self, x, radius, *, params=None):
+        raise RuntimeError("IndexRefineFlat: range_search is not available in this build (IndexFlat* and IndexIVFFlat only)")
 
     def search(self, x, k, *, params=None):
         """-> (D float32 [n,k], I int64 [n,k]); numpy in -> numpy out, CUDA tensor in -> CUDA tensors out.  The queries are uploaded
