@@ -228,7 +228,7 @@ int rsx_merge_packed(int nshards, int64_t nq, int k, int metric, const int64_t* 
 /* ---- introspection / knobs --------------------------------------------------------- */
 
 /* Integer properties: "ntotal", "nlist", "d", "is_trained", "nprobe", "M", "nbits", "kind",
- * "metric", "storage_dtype", "code_size", "qtype" / "by_residual" (IVFSQ), "device", "max_k", "pq_layout" (IVFPQ: 1 = rotated code layout), "nshards"
+ * "metric", "storage_dtype", "code_size", "qtype" / "by_residual" (IVFSQ), "device", "max_k", "pq_layout" (IVFPQ: 1 = rotated code layout), "direct_map_type" (rsx_direct_map_type the handle holds now), "nshards"
  * (0 = single-device handle), "hbm_bytes", "explicit_ids" (1 = a Flat handle that stores caller ids, or any handle one of whose
  * rsx_add calls since the last rsx_reset carried ids).
  * (index.ntotal / index.is_trained — ivf_flat.py:171; ivf_pq.py:175) */
@@ -315,6 +315,48 @@ int rsx_search_prepass_sel(rsx_index_t* h, int64_t nq, const void* q, int dtype,
  * kc > 4096 (RSX_ERR_UNSUPPORTED), k < 1 or k > kc (RSX_ERR_INVALID).  rsx_get_timing: "refine_calls", "refine_candidates" (nq * kc,
  * summed) and, with "profile" = 1, "refine_ms" (HIP events around the call's launches). */
 int rsx_refine(rsx_index_t* flat, int64_t nq, const void* q, int dtype, int kc, const int64_t* labels, int k, float* D, int64_t* I);
+
+/* ---- stored vectors by id (FAISS Index::reconstruct*) ------------------------------- */
+
+/* DirectMap::Type of FAISS 1.8.0 (invlists/DirectMap.h): the map from a stored id to its storage row. */
+enum rsx_direct_map_type { RSX_DM_NOMAP = 0, RSX_DM_ARRAY = 1, RSX_DM_HASHTABLE = 2 };
+
+/* IndexIVF::make_direct_map(new_maintain_direct_map) / IndexIVF::set_direct_map_type(type) -> DirectMap::set_type: build the map
+ * at once (type 1 or 2) or release it (type 0).
+ *   RSX_DM_ARRAY      int64 map[ntotal], 8 B per vector: taken when every stored id lies in [0, ntotal) once (sequential ids in any
+ *                     list order, a permutation given through rsx_add's ids); otherwise the build falls back to the hash table
+ *                     (FAISS throws instead);
+ *   RSX_DM_HASHTABLE  open addressing over (id, row) slots of 16 B, capacity the power of two >= 2 ntotal: 32 - 64 B per vector.
+ * The type asked for is kept for later builds; rsx_get "direct_map_type" tells what the handle holds now (0 = nothing).
+ * DIFFERENCE FROM FAISS: IndexIVF::reconstruct throws before make_direct_map; here the first rsx_reconstruct_batch builds the map
+ * (Array where the ids allow it), so this call is an optimisation of WHEN, never a requirement.  The map is derived data, counted in
+ * rsx_get "workspace_bytes": rsx_add, rsx_add_list, rsx_remove_ids, rsx_reset, rsx_reserve_lists and every re-layout RELEASE it
+ * (FAISS maintains it across add), the next lookup builds it again.  The build checks hipMemGetInfo first: without
+ * room it fails with RSX_ERR_OOM and the handle stays usable.  An id stored more than once resolves to its copy in the LOWEST
+ * storage row: the first in (list number, in-list offset) order.  A Flat handle of sequential ids and an IndexPQ handle need no
+ * map (the key is the row): the call succeeds and "direct_map_type" stays 0.  rsx_get_timing: "direct_map_builds",
+ * "direct_map_ms" (host wall time).  Refused: sharded handles (RSX_ERR_UNSUPPORTED), an unknown type (RSX_ERR_INVALID). */
+int rsx_make_direct_map(rsx_index_t* h, int type);
+
+/* Index::reconstruct_batch(n, keys, recons) — and with it Index::reconstruct (n = 1), Index::reconstruct_n (keys i0 .. i0 + n - 1) and
+ * the gather of Index::search_and_reconstruct (keys = the labels of a search, fill_negative = 1).  The reference serves the same need
+ * from host RAM: get_embs(indices) / get_knn_scores(query_emb, indices) index a resident self.embs array
+ * (src/indicies/ivf_flat.py:109-123, ivf_pq.py:112-123, flat.py:90); here the vectors come from what the index keeps in HBM.
+ *   keys int64 [n]: ids, the labels rsx_search returns, in any order, repeats allowed;  out float32 [n, d];  keys and out are HOST or
+ *   DEVICE pointers, each on its own.  out[i] is the vector the index STORES for keys[i] — what an exact search scores against:
+ *     Flat, IVF-Flat   the stored row (fp16 rows widened, which is exact; fp32 rows as they are);
+ *     IVF-PQ           x^_j = fl32(c_list[j] + codebook[m][code_m][t]), j = m dsub + t (IndexIVFPQ::reconstruct_from_offset): the
+ *                      DECODED vector, not the one that was added;
+ *     IndexPQ          the codebook entries alone, nothing added (ProductQuantizer::decode); a key is the position of the vector;
+ *     IVF-SQ           the decoded code, with by_residual the list's centroid added and the sum rounded once (rsx_ivfsq_create's x^).
+ *   fill_negative != 0: a key < 0 (the padding label of a search) gives a row whose every bit is set (FAISS: memset(-1); reads as NaN).
+ * A key that is not stored (and a key < 0 without fill_negative) is never dereferenced: the call returns RSX_ERR_INVALID once its work
+ * has finished, the message names the first such key, out is unspecified and the handle stays usable (DirectMap::get throws as well).
+ * n = 0 succeeds and touches nothing.  One k_reconstruct launch (one wave per key) per 64 MiB of host output, or per call for device
+ * output, on the handle's stream; the call may directly follow the rsx_search that produced the keys.  The id -> row map is built by
+ * the first call that needs it (rsx_make_direct_map).  rsx_get_timing: "reconstruct_calls", "reconstruct_keys".
+ * Refused with the handle untouched: sharded handles (RSX_ERR_UNSUPPORTED), n < 0, a null pointer with n > 0 (RSX_ERR_INVALID). */
+int rsx_reconstruct_batch(rsx_index_t* h, int64_t n, const int64_t* keys, int fill_negative, float* out);
 
 /* ---- range search (FAISS Index::range_search) -------------------------------------- */
 

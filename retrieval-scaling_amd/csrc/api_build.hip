@@ -23,7 +23,8 @@ int64_t workspace_bytes(const rsx_index* h) {
                             &h->w_temp, &h->w_lut, &h->w_lutws, &h->w_state, &h->w_D, &h->w_I, &h->w_qin, &h->w_pairs, &h->w_flag, &h->w_x,
                             &h->w_partial, &h->w_assign, &h->w_dest, &h->w_idsin, &h->w_misc, &h->w_lut8, &h->w_qparam, &h->w_uncertain,
                             &h->w_fbq, &h->w_fbD, &h->w_fbI, &h->w_cand, &h->w_candcnt, &h->w_itemdesc, &h->w_tau, &h->w_excl, &h->w_state2, &h->w_addcnt, &h->w_addstart, &h->w_qitems, &h->w_tiews, &h->w_stagedir, &h->w_rlabels, &h->w_sqhi, &h->w_sqlo, &h->w_sqc, &h->sh_D, &h->sh_I, &h->sh_q,
-                            &h->sh_oD, &h->sh_oI, &h->sel_mask, &h->sel_dev, &h->codes_plain /* derived from the payload on demand, dropped by the next add */};
+                            &h->sh_oD, &h->sh_oI, &h->sel_mask, &h->sel_dev, &h->codes_plain /* derived from the payload on demand, dropped by the next add */,
+                            &h->dmap /* the direct map: derived on demand, released by every mutation (api_reconstruct.hip) */, &h->dmap_ws, &h->w_rkeys, &h->w_rout};
     int64_t t = 0;
     for (const DevBuf* b : bufs) t += (int64_t)b->bytes;
     return t;
@@ -31,6 +32,7 @@ int64_t workspace_bytes(const rsx_index* h) {
 
 void upload_dir(rsx_index* h) {
     h->dir_gen++;       // list lengths changed: the memoised host-side bounds below are stale
+    release_direct_map(h);      // ... and so is the id -> row map: the next lookup builds it again
     size_t nb = (size_t)h->nlist * sizeof(int64_t);
     h->d_base.ensure(nb);
     h->d_len.ensure(nb);
@@ -49,6 +51,7 @@ void ensure_capacity(rsx_index* h, const std::vector<int64_t>& need, bool exact)
     bool need_norms = (h->metric == RSX_METRIC_L2) && h->kind != KIND_IVFPQ;
     if (!grow && h->data.p && (!need_ids || h->ids.p) && (!need_norms || h->norms.p)) return;
 
+    release_direct_map(h);      // a re-layout holds two copies of the payload: the map's memory goes back before the allocation
     // Amortised growth: a re-layout moves the whole index, so when ANY list overflows EVERY list gets
     // headroom proportional to its current need (2x for PQ codes, 1.5x for raw rows); the number of
     // re-layouts is then logarithmic in the final size instead of one per add batch.

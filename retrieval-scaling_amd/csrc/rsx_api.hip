@@ -68,7 +68,7 @@ static int search_prepass_common(rsx_index_t* h, int64_t nq, const void* q, int 
 extern "C" {
 
 const char* rsx_last_error(void) { return g_err.c_str(); }
-int rsx_version(void) { return 1006; }     // 1001: filtered search (rsx_selector_*, rsx_search_sel, rsx_search_prepass_sel); 1002: rsx_remove_ids; 1003: rsx_pq_create; 1004: rsx_refine; 1005: rsx_ivfsq_create; 1006: rsx_range_search, rsx_range_result_get, rsx_range_result_destroy
+int rsx_version(void) { return 1007; }     // 1007: rsx_make_direct_map, rsx_reconstruct_batch; 1001: filtered search (rsx_selector_*, rsx_search_sel, rsx_search_prepass_sel); 1002: rsx_remove_ids; 1003: rsx_pq_create; 1004: rsx_refine; 1005: rsx_ivfsq_create; 1006: rsx_range_search, rsx_range_result_get, rsx_range_result_destroy
 
 int rsx_device_count(int* n) {
     return guarded([&] {
@@ -383,6 +383,27 @@ int rsx_refine(rsx_index_t* h, int64_t nq, const void* q, int dtype, int kc, con
     });
 }
 
+int rsx_make_direct_map(rsx_index_t* h, int type) {
+    return guarded([&] {
+        if (!h) RSX_THROW(RSX_ERR_INVALID, "make_direct_map: null pointer");
+        refuse_while_two_call(h, "make_direct_map");
+        if (is_sharded(h)) RSX_THROW(RSX_ERR_UNSUPPORTED, "make_direct_map: not available on a sharded handle (the rows are split over the shards)");
+        use_device(h);
+        make_direct_map_impl(h, type);
+    });
+}
+int rsx_reconstruct_batch(rsx_index_t* h, int64_t n, const int64_t* keys, int fill_negative, float* out) {
+    return guarded([&] {
+        if (!h) RSX_THROW(RSX_ERR_INVALID, "reconstruct_batch: null pointer");
+        refuse_while_two_call(h, "reconstruct_batch");
+        if (is_sharded(h)) RSX_THROW(RSX_ERR_UNSUPPORTED, "reconstruct_batch: not available on a sharded handle (the rows are split over the shards)");
+        if (n < 0) RSX_THROW(RSX_ERR_INVALID, "reconstruct_batch: n = %lld", (long long)n);
+        if (n > 0 && (!keys || !out)) RSX_THROW(RSX_ERR_INVALID, "reconstruct_batch: null pointer with n = %lld", (long long)n);
+        use_device(h);
+        reconstruct_impl(h, n, keys, fill_negative, out);
+    });
+}
+
 int rsx_range_search(rsx_index_t* h, int64_t nq, const void* q, int dtype, float radius, int nprobe_override, rsx_range_result_t** out) {
     return guarded([&] {
         if (!h || !out) RSX_THROW(RSX_ERR_INVALID, "range_search: null pointer");
@@ -550,6 +571,7 @@ int rsx_get(rsx_index_t* h, const char* key, int64_t* out) {
         if (!h || !key || !out) RSX_THROW(RSX_ERR_INVALID, "null pointer");
         std::string s(key);
         if (s == "nshards") { *out = (int64_t)h->shards.size(); return; }
+        if (s == "direct_map_type") { *out = (!is_sharded(h) && h->dmap_type != 0 && h->dmap_gen == h->dir_gen) ? h->dmap_type : 0; return; }
         if (s == "explicit_ids") { *out = (h->ids_given || (h->kind == KIND_FLAT && h->custom_ids)) ? 1 : 0; return; }
         if (is_sharded(h)) {
             if (s == "ntotal") { *out = h->ntotal; return; }

@@ -4,6 +4,7 @@
 //   api_search.hip   the search drivers (search_batch = one internal batch, search_impl = one rsx_search call)
 //   api_refine.hip   rsx_refine: exact re-ranking of candidate labels against a Flat row store (k_refine.hip)
 //   api_range.hip    rsx_range_search: every neighbour within a radius, Flat and IVF-Flat (k_range.hip; declarations in rsx_range.h)
+//   api_reconstruct.hip  rsx_reconstruct_batch / rsx_make_direct_map: stored vectors by id (k_reconstruct.hip; rsx_reconstruct.h)
 //   api_sharded.hip  the single-process multi-GPU handle
 //   api_remove.hip   rsx_remove_ids: the removal plan and compaction (k_remove.hip) on a handle and on the shards of one
 //   rsx_api.hip      the extern "C" entry points
@@ -293,6 +294,15 @@ struct rsx_index {
     uint64_t sel_mask_serial = 0, sel_mask_gen = 0;
     const void* sel_mask_of = nullptr;
 
+    // direct map (rsx_reconstruct_batch): id -> storage row, derived from the list directory and the ids.  dmap holds
+    // dmap_n int64 rows (Array) or dmap_n (id, row) slots (Hashtable, dmap_n a power of two); it belongs to directory generation
+    // dmap_gen and is RELEASED by upload_dir / ensure_capacity, i.e. by every mutation (api_reconstruct.hip: release_direct_map)
+    DevBuf dmap, dmap_ws, w_rkeys, w_rout;
+    int dmap_type = 0;        // what dmap holds: 0 = nothing, 1 = Array, 2 = Hashtable (rsx_get "direct_map_type")
+    int dmap_pref = 1;        // what the next build makes: 1 = Array where the ids allow it, else Hashtable; 2 = Hashtable
+    int64_t dmap_n = 0;
+    uint64_t dmap_gen = ~0ull;
+
     // Flat / IVF-Flat: largest |x|^2 ever added (certificate of the MFMA scan); device copy is the running atomic max
     float max_norm2 = 0.0f;
     DevBuf d_maxnorm;
@@ -383,6 +393,9 @@ void sharded_save(rsx_index* h, const char* path);
 void destroy_handle(rsx_index* h);
 rsx_index* sharded_load(const char* path, int ndev, const int* devices);
 int64_t remove_impl(rsx_index* h, const rsx_selector* s);
+void release_direct_map(rsx_index* h);
+void make_direct_map_impl(rsx_index* h, int type);
+void reconstruct_impl(rsx_index* h, int64_t n, const int64_t* keys, int fill_negative, float* out);
 int64_t sharded_remove(rsx_index* h, const rsx_selector* s);
 
 // k_remove.hip: the removal kernels (mask: k_sel_mask, bit s = slot s is removed; slots of the moves are uint32: < 2^32 storage rows)

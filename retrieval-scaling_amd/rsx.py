@@ -11,6 +11,8 @@ written against `faiss`:
     faiss.IndexIVFPQ(q,d,nlist,M,nbits,METRIC_IP)      ivf_pq.py:147     rsx.IndexIVFPQ(...)
     faiss.IndexPQ(d,M,nbits,METRIC_IP)    contriever/src/index.py:19     rsx.IndexPQ(...)
     faiss.IndexRefineFlat(base)           (factory "...,RFlat")          rsx.IndexRefineFlat(base)
+    index.reconstruct / reconstruct_batch / reconstruct_n / search_and_reconstruct / make_direct_map
+        (faiss.Index verbs; the reference's get_embs(indices))            same, decoded on the GPU
     index.train / add / search / nprobe / ntotal / is_trained            same
     index.range_search(x, radius)         (faiss.Index verb; Flat, IVF-Flat) same, lims as int64
     faiss.read_index / write_index                                        rsx.read_index / write_index
@@ -49,6 +51,7 @@ ABI_SYMBOLS = [
     "rsx_remove_ids", "rsx_refine",
     "rsx_ivfsq_create", "rsx_set_sq_trained", "rsx_get_sq_trained",
     "rsx_range_search", "rsx_range_result_get", "rsx_range_result_destroy",
+    "rsx_make_direct_map", "rsx_reconstruct_batch",
 ]
 
 
@@ -607,10 +610,82 @@ class Index:
         _check(lib().rsx_get_list_sizes(self._h, out.ctypes.data_as(ctypes.c_void_p)))
         return out
 
-    def reconstruct_n(self, i0, n):
-        assert self._get("kind") == 0, "reconstruct_n is implemented for Flat and PQ indexes"
-        payload, _ = self.get_list(0)
-        return payload[i0:i0 + n]
+    # -- stored vectors by id (rsx_reconstruct_batch)
+    def _reconstruct_keys(self, keys, fill_negative):
+        """keys: int64, numpy (-> numpy float32 [n, d]) or a CUDA tensor (-> CUDA tensor); any shape, read flattened."""
+        if _is_torch(keys) and keys.is_cuda:
+            import torch
+            k = keys.to(torch.int64).contiguous().reshape(-1)
+            out = torch.empty((k.numel(), self.d), dtype=torch.float32, device=k.device)
+            _sync_producer(k, True)
+            _check(lib().rsx_reconstruct_batch(self._h, ctypes.c_int64(k.numel()), ctypes.c_void_p(k.data_ptr()) if k.numel() else None,
+                                               int(fill_negative), ctypes.c_void_p(out.data_ptr()) if k.numel() else None))
+            return out
+        back = _is_torch(keys)
+        k = np.ascontiguousarray(keys.numpy() if back else keys, dtype=np.int64).reshape(-1)
+        out = np.empty((len(k), self.d), dtype=np.float32)
+        _check(lib().rsx_reconstruct_batch(self._h, ctypes.c_int64(len(k)), k.ctypes.data_as(ctypes.c_void_p) if len(k) else None,
+                                           int(fill_negative), out.ctypes.data_as(ctypes.c_void_p) if len(k) else None))
+        if back:
+            import torch
+            return torch.from_numpy(out)
+        return out
+
+    def reconstruct_batch(self, keys):
+        """faiss.Index.reconstruct_batch(keys) -> float32 [n, d]: the vector the index STORES for every key (an id, the label `search`
+        returns), in the order of the keys; keys may repeat.  Flat / IVF-Flat: the stored row; IVF-PQ: centroid + codebook entries
+        (the decoded vector, not the one that was added); IndexPQ: the codebook entries; IVF-SQ: the decoded code (+ centroid with
+        by_residual).  numpy keys -> numpy out, a CUDA int64 tensor -> a CUDA tensor.  A key that is not stored raises (the message
+        names the first one).  Unlike FAISS's IndexIVF no make_direct_map() is needed first: the first lookup builds the map."""
+        return self._reconstruct_keys(keys, False)
+
+    def reconstruct(self, key):
+        """faiss.Index.reconstruct(key) -> float32 [d]."""
+        return self._reconstruct_keys(np.array([int(key)], dtype=np.int64), False)[0]
+
+    def reconstruct_n(self, i0=0, n=None):
+        """faiss.Index.reconstruct_n(i0, n) = reconstruct_batch(arange(i0, i0 + n)); n None: up to ntotal."""
+        n = self.ntotal - int(i0) if n is None else int(n)
+        assert n >= 0, "reconstruct_n: n must not be negative"
+        return self._reconstruct_keys(np.arange(int(i0), int(i0) + n, dtype=np.int64), False)
+
+    def search_and_reconstruct(self, x, k, *, params=None):
+        """faiss.Index.search_and_reconstruct(x, k) -> (D, I, R float32 [n, k, d]): D, I exactly what search(x, k, params=params)
+        returns, R[i, j] = reconstruct(I[i, j]); where I[i, j] = -1 every bit of R[i, j] is set (FAISS's memset(-1); reads as NaN).
+        The labels stay on the device between the search and the gather.  numpy in -> numpy out, CUDA tensor in -> CUDA tensors out."""
+        import torch
+        on_dev = _is_torch(x) and x.is_cuda
+        if on_dev:
+            xq = x
+        else:
+            xh = x if _is_torch(x) else np.asarray(x)
+            if not _is_torch(xh) and xh.dtype not in (np.float32, np.float16):
+                xh = xh.astype(np.float32)
+            xq = torch.as_tensor(xh).to(f"cuda:{self._get('device')}")
+        D, I = self.search(xq, k, params=params)
+        R = self._reconstruct_keys(I, True).reshape(I.shape[0], I.shape[1], self.d)
+        if on_dev:
+            return D, I, R
+        return D.cpu().numpy(), I.cpu().numpy(), R.cpu().numpy()
+
+    def make_direct_map(self, new_maintain_direct_map=True):
+        """faiss.IndexIVF.make_direct_map: True builds the id -> row map now (Array where every id lies in [0, ntotal) once, else
+        Hashtable), False releases it.  Never required: the first reconstruct builds it; every add / remove_ids / reset releases it."""
+        _check(lib().rsx_make_direct_map(self._h, DirectMap.Array if new_maintain_direct_map else DirectMap.NoMap))
+
+    def set_direct_map_type(self, type):
+        """faiss.IndexIVF.set_direct_map_type(DirectMap.NoMap | Array | Hashtable) (rsx_make_direct_map)."""
+        _check(lib().rsx_make_direct_map(self._h, int(type)))
+
+    @property
+    def direct_map_type(self):
+        """What the handle holds now: DirectMap.NoMap (also: a Flat / IndexPQ handle, whose keys are rows), Array or Hashtable."""
+        return self._get("direct_map_type")
+
+
+class DirectMap:
+    """faiss.DirectMap.Type: the map from a stored id to its storage row (rsx_direct_map_type)."""
+    NoMap, Array, Hashtable = 0, 1, 2
 
 
 class IndexFlat(Index):
@@ -800,15 +875,11 @@ class IndexPQ(Index):
                                       ids.ctypes.data_as(ctypes.c_void_p)))
 
     def reconstruct_n(self, i0=0, n=None):
-        """Decoded vectors float32 [n, d] of the stored codes i0 .. i0 + n - 1 (host arithmetic on the exported codes)."""
-        codes, _ = self.get_list(0)
-        codes = codes[i0:] if n is None else codes[i0:i0 + n]
-        cb = self.get_codebooks()
-        dsub = self.d // self.M
-        out = np.empty((len(codes), self.d), dtype=np.float32)
-        for m in range(self.M):
-            out[:, m * dsub:(m + 1) * dsub] = cb[m][codes[:, m]]
-        return out
+        """Decoded vectors float32 [n, d] of the stored codes i0 .. i0 + n - 1, clipped to ntotal (a slice, as before): the codebook
+        entries alone, gathered on the GPU (rsx_reconstruct_batch)."""
+        i0 = int(i0)
+        hi = self.ntotal if n is None else min(self.ntotal, i0 + int(n))
+        return self._reconstruct_keys(np.arange(i0, max(i0, hi), dtype=np.int64), False)
 
 
 class IndexRefineSearchParameters(SearchParameters):
@@ -894,6 +965,36 @@ class IndexRefineFlat:
 
     def range_search(self, x, radius, *, params=None):
         raise RuntimeError("IndexRefineFlat: range_search is not available in this build (IndexFlat* and IndexIVFFlat only)")
+
+    # faiss.IndexRefine::reconstruct: refine_index's row
+    def reconstruct(self, key):
+        return self.refine_index.reconstruct(key)
+
+    def reconstruct_batch(self, keys):
+        return self.refine_index.reconstruct_batch(keys)
+
+    def reconstruct_n(self, i0=0, n=None):
+        return self.refine_index.reconstruct_n(i0, n)
+
+    def make_direct_map(self, new_maintain_direct_map=True):
+        self.refine_index.make_direct_map(new_maintain_direct_map)
+
+    def search_and_reconstruct(self, x, k, *, params=None):
+        """-> (D, I, R): this index's search, then refine_index's rows of the labels (all-ones words where a label is -1)."""
+        on_dev = _is_torch(x) and x.is_cuda
+        if on_dev:
+            xq = x
+        else:
+            import torch
+            xh = x if _is_torch(x) else np.asarray(x)
+            if not _is_torch(xh) and xh.dtype not in (np.float32, np.float16):
+                xh = xh.astype(np.float32)
+            xq = torch.as_tensor(xh).to(f"cuda:{self.refine_index._get('device')}")
+        D, I = self.search(xq, k, params=params)
+        R = self.refine_index._reconstruct_keys(I, True).reshape(I.shape[0], I.shape[1], self.d)
+        if on_dev:
+            return D, I, R
+        return D.cpu().numpy(), I.cpu().numpy(), R.cpu().numpy()
 
     def search(self, x, k, *, params=None):
         """-> (D float32 [n,k], I int64 [n,k]); numpy in -> numpy out, CUDA tensor in -> CUDA tensors out.  The queries are uploaded

@@ -169,7 +169,19 @@ class BackendBase:
     def get_embs(self, indices=None, shard_id=None):
         if shard_id is not None:
             return self.load_embeds(shard_id)
-        raise AttributeError("get_embs(indices=...) needs resident embeddings, which no backend keeps")
+        if indices is None:
+            raise ValueError("get_embs needs indices or shard_id")
+        # the reference indexes a resident self.embs array (ivf_flat.py:109-117, ivf_pq.py:112-117, flat.py:90); here the vectors
+        # come from what the index stores in HBM (rsx_reconstruct_batch): the raw rows for Flat / IVF-Flat, the DECODED vectors
+        # for IVF-PQ
+        indices = np.asarray(indices, dtype=np.int64)
+        d = self.index.d
+        return self.index.reconstruct_batch(indices.ravel()).reshape(*indices.shape, d)
+
+    def get_knn_scores(self, query_emb, indices):
+        """reference ivf_pq.py:119-123 / ivf_flat.py:119-123: minus the Euclidean distance of every query to its retrieved vectors."""
+        embs = self.get_embs(indices)     # [batch_size, k, dimension]
+        return -np.sqrt(np.sum((np.expand_dims(query_emb, 1) - embs) ** 2, -1))     # [batch_size, k]
 
     # ---- id -> passage (reference flat.py:115-136).  The reference resolves every retrieved id through two Python
     # containers (index_id_to_db_id list, {shard: {chunk: [file, offset]}} dict of dicts) and opens the passage file once
