@@ -1,5 +1,5 @@
 // api_refine.hip — rsx_refine's host driver: exact re-ranking of candidate labels against a Flat handle's row store (k_refine.hip).
-#include "rsx_host.h"
+#include "rsx_stages.h"
 #include "k_rescore.h"
 
 // rsx_refine on a Flat handle of sequential ids: the labels ARE the storage rows.  One k_refine launch per internal batch; queries, labels
@@ -15,17 +15,13 @@ void refine_impl(rsx_index* h, int64_t nq, const void* q, int dtype, int kc, con
     h->w_rflag.host_mapped = true;
     h->w_rflag.ensure(sizeof(int));
     *h->w_rflag.as<int>() = 0;          // (no kernel of this handle is in flight: every call ends with a synchronisation of its stream)
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;
-    if (h->profile > 0) { (void)hipEventCreate(&ev0); (void)hipEventCreate(&ev1); (void)hipEventRecord(ev0, h->st); }
+    StreamTimer t_all(h->profile > 0, h->st);
+    t_all.start();
     const int64_t qb = std::max(1, h->query_batch);
     for (int64_t q0 = 0; q0 < nq; q0 += qb) {
         const int64_t nb = std::min(qb, nq - q0);
         const void* dq = (const char*)q + (size_t)q0 * d * esz;
-        if (!q_dev) {
-            h->w_qin.ensure((size_t)nb * d * esz);
-            HIPCHECK(hipMemcpyAsync(h->w_qin.p, dq, (size_t)nb * d * esz, hipMemcpyHostToDevice, h->st));
-            dq = h->w_qin.p;
-        }
+        if (!q_dev) dq = stage_rows(h, h->w_qin, dq, nb, d, dtype);
         const int64_t* dl = labels + q0 * kc;
         if (!l_dev) {
             h->w_rlabels.ensure((size_t)nb * kc * 8);
@@ -51,14 +47,10 @@ void refine_impl(rsx_index* h, int64_t nq, const void* q, int dtype, int kc, con
         }
         if (!q_dev || !l_dev || !o_dev) HIPCHECK(hipStreamSynchronize(h->st));     // the staging buffers serve the next batch
     }
-    if (ev0) (void)hipEventRecord(ev1, h->st);
+    t_all.stop();
     HIPCHECK(hipStreamSynchronize(h->st));
     HIPCHECK(hipGetLastError());
-    if (ev0) {
-        float ms = 0; (void)hipEventElapsedTime(&ms, ev0, ev1);
-        h->timing["refine_ms"] += ms;
-        (void)hipEventDestroy(ev0); (void)hipEventDestroy(ev1);
-    }
+    if (h->profile > 0) h->timing["refine_ms"] += t_all.ms();
     h->timing["refine_calls"] += 1.0;
     h->timing["refine_candidates"] += (double)nq * kc;
     if (*h->w_rflag.as<int>() != 0)

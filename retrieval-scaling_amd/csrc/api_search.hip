@@ -1,8 +1,9 @@
 // api_search.hip — the search drivers: search_batch (one internal batch: coarse quantiser, probe selection, table build, threshold
-// pre-pass, scan, selection, exact re-rank, certificate fallbacks) and search_impl (one rsx_search call).  Shared declarations: rsx_host.h.
+// pre-pass, scan, selection, exact re-rank, certificate fallbacks) and search_impl (one rsx_search call).  Shared declarations: rsx_host.h;
+// the stages that range_search runs as well: rsx_stages.h.
 #include <chrono>
 #include <cstring>
-#include "rsx_host.h"
+#include "rsx_stages.h"
 
 // ---------------------------------------------------------------------------------------
 // search
@@ -58,83 +59,6 @@ static void sel_apply_flat(rsx_index* h, float* temp, int64_t tstride, int64_t n
     SelApplyArgs sa{};
     sa.temp = temp; sa.tstride = tstride; sa.nq = nq; sa.mask = h->sel_mask.as<uint32_t>(); sa.flat_n = n; sa.slot0 = slot0;
     launch_sel_apply(sa, h->st);
-}
-
-// top-k of `nrows` rows of fp32 scores (row r valid length: row_n or n_uniform) into state [nrows, KP]
-static void select_rows(rsx_index* h, const float* scores, int64_t row_stride, const int64_t* row_n, int64_t row_n_stride,
-                        int64_t n_max, uint32_t idx_base, int64_t nrows, int KP, int BUF, int k, uint64_t* state,
-                        bool merge_state, unsigned long long* threshold_only_cnt = nullptr) {
-    int64_t seg_len = std::max<int64_t>(4096, (int64_t)8 * BUF);
-    seg_len = round_up(seg_len, 256);
-    if (KP >= 1024 && n_max <= 131072) seg_len = round_up(n_max, 256);     // one segment: the radix selection (launch_select)
-    int nseg = (int)std::max<int64_t>(1, (n_max + seg_len - 1) / seg_len);
-    SelectArgs a{};
-    a.in = scores; a.in_is_keys = 0; a.row_stride = row_stride;
-    a.row_n = row_n; a.row_n_stride = row_n_stride; a.n_uniform = n_max;
-    a.seg_len = seg_len; a.nseg = nseg; a.idx_base = idx_base;
-    a.nrows = nrows; a.KP = KP; a.BUF = BUF; a.k = k;
-    if (nseg == 1) {
-        a.init = merge_state ? state : nullptr;
-        a.out = state; a.out_row_stride = KP;
-        if (threshold_only_cnt) { a.keep_last = 1; a.zero_cnt = threshold_only_cnt; }
-        launch_select(a, h->st);
-        return;
-    }
-    h->w_keys1.ensure((size_t)nrows * nseg * KP * 8);
-    a.init = nullptr; a.out = h->w_keys1.as<uint64_t>(); a.out_row_stride = (int64_t)nseg * KP;
-    if (nseg >= 4 && !merge_state) {
-        // Phase A: segment 0 of every row (for IVF: the head of the closest list) alone; its k-th key is a
-        // lower bound of the row's final k-th best, so (phase B) the other segments start from that
-        // threshold and append almost nothing — no LDS sorts on the bulk of the row.
-        SelectArgs a0 = a; a0.nseg = 1; a0.seg_base = 0;
-        launch_select(a0, h->st);
-        a.seg_base = 1;
-        a.tau_ptr = h->w_keys1.as<uint64_t>() + (k - 1); a.tau_stride = (int64_t)nseg * KP;
-        launch_select(a, h->st);
-    } else {
-        launch_select(a, h->st);
-    }
-    SelectArgs b{};
-    b.in = h->w_keys1.p; b.in_is_keys = 1; b.row_stride = (int64_t)nseg * KP;
-    b.row_n = nullptr; b.n_uniform = (int64_t)nseg * KP;
-    b.seg_len = round_up((int64_t)nseg * KP, 256); b.nseg = 1; b.idx_base = 0;
-    b.init = merge_state ? state : nullptr;
-    b.out = state; b.out_row_stride = KP;
-    b.nrows = nrows; b.KP = KP; b.BUF = BUF; b.k = k;
-    if (threshold_only_cnt) { b.keep_last = 1; b.zero_cnt = threshold_only_cnt; }
-    launch_select(b, h->st);
-}
-
-// Upper bound on the number of (list, tile, group) work items of a list-major scan without a host round
-// trip: sum_l ceil(cnt_l/G)*tiles_l <= (nq * TQ)/G + sum_l tiles_l, TQ = tiles of the nprobe longest lists.
-// (sum, max) of the nprobe largest values of ceil(len / unit) * scale over the lists (unit > 0), memoised per directory
-// generation.  tag distinguishes the callers' (unit, scale) families.
-static std::pair<int64_t, int64_t> top_probe_sum(rsx_index* h, int nprobe, int unit, int scale) {
-    const auto key = std::make_tuple(nprobe, unit, scale);
-    auto it = h->bound_cache.find(key);
-    if (it != h->bound_cache.end() && it->second.first == h->dir_gen) return it->second.second;
-    std::vector<int64_t> t((size_t)h->nlist);
-    for (int l = 0; l < h->nlist; l++) t[(size_t)l] = (h->h_len[(size_t)l] + unit - 1) / unit * scale;
-    const int np = std::min(nprobe, h->nlist);
-    std::partial_sort(t.begin(), t.begin() + np, t.end(), std::greater<int64_t>());
-    int64_t s = 0;
-    for (int j = 0; j < np; j++) s += t[(size_t)j];
-    const std::pair<int64_t, int64_t> r(s, np > 0 ? t[0] : 0);
-    h->bound_cache[key] = std::make_pair(h->dir_gen, r);
-    return r;
-}
-static int64_t max_scan_items(rsx_index* h, int64_t nq, int nprobe, int G, int tile_rows) {
-    const auto key = std::make_tuple(-1, tile_rows, 0);       // all tiles of all lists
-    int64_t all;
-    auto it = h->bound_cache.find(key);
-    if (it != h->bound_cache.end() && it->second.first == h->dir_gen) all = it->second.second.first;
-    else {
-        all = 0;
-        for (int l = 0; l < h->nlist; l++) all += (h->h_len[(size_t)l] + tile_rows - 1) / tile_rows;
-        h->bound_cache[key] = std::make_pair(h->dir_gen, std::make_pair(all, (int64_t)0));
-    }
-    const int64_t tq = top_probe_sum(h, nprobe, tile_rows, 1).first;
-    return (nq * tq + G - 1) / G + all + 8;
 }
 
 // ---------------------------------------------------------------------------------------
@@ -243,31 +167,6 @@ static void merge_key_rows(rsx_index* h, const void* keys, const unsigned long l
     b.nrows = nrows; b.KP = KP; b.BUF = BUF; b.k = KP; b.row_filter = row_filter;
     launch_select(b, h->st);
 }
-// what a list-major scan reads of a grouping: the pairs sorted by list, the per-list offsets, the (list, tile, group) work items
-struct PairView {
-    const int32_t *pairs_sorted, *pair_off, *group_off, *total_groups, *item_off, *total_items; int nlist;
-};
-// the (query, probe) pairs of a batch grouped by list (launch_group_pairs), carved out of h->w_pairs
-struct PairArea {
-    rsx_index* h; int64_t npairs; int nlist, nprobe;
-    int32_t *pairs_sorted, *cnt, *cursor, *pair_off, *group_off, *item_off, *total_groups, *total_items;
-    PairArea(rsx_index* hh, int64_t nq, int np, int nl) : h(hh), npairs(nq * np), nlist(nl), nprobe(np) {
-        h->w_pairs.ensure((size_t)(npairs + 5 * (size_t)(nlist + 1) + 8) * 4);
-        pairs_sorted = h->w_pairs.as<int32_t>(); cnt = pairs_sorted + npairs; cursor = cnt + (nlist + 1); pair_off = cursor + (nlist + 1);
-        group_off = pair_off + (nlist + 1); item_off = group_off + (nlist + 1); total_groups = item_off + (nlist + 1); total_items = total_groups + 1;
-    }
-    // groups of G probing queries; tile_rows > 0: also the (list, tile, group) work items (at most tile_cap tiles per list, 0 = all)
-    PairGroupArgs args(int G, int tile_rows, int tile_cap) const {
-        PairGroupArgs g{};
-        g.probe_list = h->w_probelist.as<int32_t>(); g.pair_off = pair_off; g.group_off = group_off; g.total_groups = total_groups; g.pairs_sorted = pairs_sorted;
-        if (tile_rows) { g.list_len = h->d_len.as<int64_t>(); g.item_off = item_off; g.total_items = total_items; }
-        g.npairs = (int)npairs; g.nlist = nlist; g.G = G; g.tile_rows = tile_rows; g.tile_cap = tile_cap;
-        return g;
-    }
-    // ... over the probe ranks [0, jmax), in launches of its own
-    void group(int G, int tile_rows, int jmax, int tile_cap, hipStream_t st) const { launch_group_pairs(args(G, tile_rows, tile_cap), cnt, cursor, nprobe, jmax, st); }
-    PairView view() const { return PairView{pairs_sorted, pair_off, group_off, total_groups, item_off, total_items, nlist}; }
-};
 // what one batch's stages leave for the later ones
 struct BatchResult {
     bool filtered = false;         // in-kernel candidate filtering: candidate rows instead of score rows
@@ -353,18 +252,14 @@ static void rerun_uncertified(rsx_index* h, int64_t nq, const void* dq, int dtyp
 // queries: fp32 copy (exact re-rank, coarse quantiser, LUT) [nq, ld]; fp16 copy for the scans
 static void convert_queries(rsx_index* h, const BatchPlan& P, const void* dq, int dtype, StageTimer& tm) {
     const int64_t nq = P.nq; const int d = h->d, ld = h->ld;
-    h->w_q32.ensure((size_t)nq * ld * 4);
-    if (h->kind == KIND_IVFPQ && P.coarse_fast) {
-        if (!P.q16_direct) {
+    if (h->kind != KIND_IVFPQ) convert_scan_queries(h, dq, dtype, nq, P.nq_pad);
+    else {
+        h->w_q32.ensure((size_t)nq * ld * 4);
+        if (!P.coarse_fast) launch_convert_to_f32(dq, dtype == RSX_F16, d, nq, d, h->w_q32.as<float>(), ld, h->st);
+        else if (!P.q16_direct) {
             h->w_q16.ensure((size_t)round_up(nq, 128) * ld * 2);
             launch_convert_to_f32_f16(dq, dtype == RSX_F16, d, nq, d, h->w_q32.as<float>(), h->w_q16.as<__half>(), ld, round_up(nq, 128), h->st);
         }
-    } else
-        launch_convert_to_f32(dq, dtype == RSX_F16, d, nq, d, h->w_q32.as<float>(), ld, h->st);
-    if (h->kind != KIND_IVFPQ) {
-        h->w_q16.ensure((size_t)P.nq_pad * ld * 2); h->w_flag.ensure(sizeof(int));
-        HIPCHECK(hipMemsetAsync(h->w_flag.p, 0, sizeof(int), h->st));
-        launch_convert_to_f16(dq, dtype == RSX_F16, nq, d, h->w_q16.as<__half>(), ld, P.nq_pad, h->w_flag.as<int>(), h->st);
     }
     h->w_state.ensure((size_t)nq * P.KP * 8);
     if (!P.q16_direct) tm.mark("convert");       // (nothing was launched for it otherwise: the widening rides in the coarse GEMM)
@@ -405,14 +300,6 @@ static void fork_side_tables(rsx_index* h, const BatchPlan& P) {
     launch_pq_lut8(la, h->st2);
     HIPCHECK(hipEventRecord(h->ev_lut, h->st2));
 }
-// >= the largest centroid norm (the fast coarse quantiser's bound; certificate term of a by_residual scalar-quantiser index), once per centroid set
-static float cent_cmax(rsx_index* h) {
-    if (h->cent_cmax_gen == h->cent_gen) return h->cent_cmax;
-    double mx = 0.0;
-    for (int l = 0; l < h->nlist; l++) { double n2 = 0.0; for (int t = 0; t < h->d; t++) { const double v = h->h_centroids[(size_t)l * h->d + t]; n2 += v * v; } mx = std::max(mx, n2); }
-    h->cent_cmax = (float)(std::sqrt(mx) * 1.000001); h->cent_cmax_gen = h->cent_gen;
-    return h->cent_cmax;
-}
 // the stored rows of a KIND_IVFSQ index, as the exact re-scores decode them
 static SqRows sq_rows(rsx_index* h) {
     return SqRows{h->data.as<uint8_t>(), h->d_sq.as<float>(), h->by_residual ? h->d_centroids.as<float>() : nullptr, h->d_base.as<int64_t>(), h->nlist};
@@ -430,18 +317,11 @@ static FinalizeArgs finalize_args(rsx_index* h, const BatchPlan& P, float* dD, i
         // (only where the certificate runs: with flat_cert = 0 there is no second pass, and the uncertified mode keeps re-ranking all
         //  K' candidates as it always did: ADVICE r5)
         fa.KPv = std::min(P.KP, P.k + std::max(8, P.k / 16));
-        // |approx - exact| of the fp16-MFMA scan for ANY stored vector (Cauchy-Schwarz on the per-element errors):
-        //   fp32 accumulation of d exact products       (d + 2) 2^-24 |q| |x|
-        //   fp32 rows rounded to fp16 inside the scan   2^-11 |q| |x|        (fp16 storage is lossless)
-        //   fp32 queries rounded to fp16                2^-11 |q| |x|        (only when the batch held such a value: device flag)
-        //   L2: the ranking score adds -|x|^2/2 (fp32)  (d + 4) 2^-24 |x|^2  (folded into the absolute term)
-        const float u24 = 5.9604645e-8f, u11 = 4.8828125e-4f;
-        const float xmax = sqrtf(h->max_norm2) * 1.0000002f;
+        // |approx - exact| of the fp16-MFMA scan for any stored vector: scan_cert_bound (derived there)
+        const ScanBound sb = scan_cert_bound(h);
         h->w_uncertain.ensure((size_t)P.nq * 8);
-        fa.uncertain = h->w_uncertain.as<int32_t>(); fa.cert_xmax = xmax;
-        fa.cert_rel = ((float)d + 2.0f) * u24 * 1.01f + (h->storage_f16 ? 0.0f : u11 * 1.002f);
-        fa.cert_rel_qlossy = u11 * 1.002f + u11 * u11; fa.cert_qflag = h->w_flag.as<int>();
-        fa.cert_abs = sqrtf((float)d) * u24 + (h->metric == RSX_METRIC_L2 ? ((float)d + 4.0f) * u24 * xmax : 0.0f);
+        fa.uncertain = h->w_uncertain.as<int32_t>(); fa.cert_qflag = h->w_flag.as<int>();
+        fa.cert_rel = sb.rel; fa.cert_rel_qlossy = sb.rel_qlossy; fa.cert_xmax = sb.xmax; fa.cert_abs = sb.abs;
     }
     if (h->kind == KIND_IVFSQ) {
         fa.sq = sq_rows(h);
@@ -602,9 +482,9 @@ static void flat_scan(rsx_index* h, const BatchPlan& P, FinalizeArgs& fa, StageT
 // flags behind w_uncertain's certificate words that rerun_uncertified merges)
 static void coarse_quantiser(rsx_index* h, const BatchPlan& P, const void* dq, int dtype, StageTimer& tm) {
     const int64_t nq = P.nq; const int d = h->d, ld = h->ld, nlist = h->nlist, nprobe = P.nprobe;
-    const int nlp = (int)round_up(nlist, 4);   // row stride of the coarse scores: 16-byte aligned rows for k_select
-    h->w_probelist.ensure((size_t)nq * nprobe * 4); h->w_dis0.ensure((size_t)nq * nprobe * 4); h->w_segstart.ensure((size_t)nq * (nprobe + 1) * 8);
     if (P.coarse_fast) {
+        const int nlp = (int)round_up(nlist, 4);   // row stride of the coarse scores: 16-byte aligned rows for k_select
+        h->w_probelist.ensure((size_t)nq * nprobe * 4); h->w_dis0.ensure((size_t)nq * nprobe * 4); h->w_segstart.ensure((size_t)nq * (nprobe + 1) * 8);
         const int64_t nqp = h->kind == KIND_IVFPQ ? round_up(nq, 128) : P.nq_pad;
         const int64_t nl128 = round_up(nlist, 128);
         if (h->cent16_gen != h->cent_gen || !h->cent16.p) {       // the centroids' fp16 copy, once per centroid set
@@ -630,17 +510,7 @@ static void coarse_quantiser(rsx_index* h, const BatchPlan& P, const void* dq, i
                                   pq_lut_pass0_blocks(nq, h->Mpad)};
         }
         launch_coarse_pick(cp, nq, h->st);
-    } else {
-        h->w_coarse.ensure((size_t)nq * nlp * 4);
-        launch_gemm_exact_scores(h->w_q32.p, 0, nq, ld, h->d_centroids.as<float>(), nlist, d, h->w_coarse.as<float>(), nlp, h->st);
-        tm.mark("coarse");
-        const int KPp = std::max(16, pow2ceil(nprobe)), BUFp = std::max(2 * KPp, 256);
-        h->w_probekeys.ensure((size_t)nq * KPp * 8);
-        select_rows(h, h->w_coarse.as<float>(), nlp, nullptr, 0, nlist, 0, nq, KPp, BUFp, nprobe, h->w_probekeys.as<uint64_t>(), false);
-        // probe set-up
-        launch_probe_setup(h->w_probekeys.as<uint64_t>(), KPp, nq, nprobe, h->d_len.as<int64_t>(), P.pad_to,
-                           h->w_probelist.as<int32_t>(), h->w_dis0.as<float>(), h->w_segstart.as<int64_t>(), h->st);
-    }
+    } else { coarse_exact_scores(h, nq); tm.mark("coarse"); coarse_exact_probes(h, nq, nprobe, P.pad_to); }
     if (P.side_lut) HIPCHECK(hipEventRecord(h->ev_probe, h->st));
     tm.mark("select_probe");
 }
@@ -1145,40 +1015,14 @@ static bool ivf_flat_filtered(rsx_index* h, const BatchPlan& P, BatchResult& R, 
     a.tau_key = nullptr; a.cand = nullptr; a.cand_cnt = nullptr; a.cand_cap = 0;
     return filtered;
 }
-// what the list scans of IVF-Flat and IVF-SQ share: lists, grouping, probes, score rows, the group bound, the L2 bias; each adds its rows and queries
-static ListScanArgs list_scan_args(rsx_index* h, const BatchPlan& P, const PairArea& pr) {
-    const int64_t npairs = pr.npairs;
-    ListScanArgs a{};
-    a.ld = h->ld;
-    a.bias = h->metric == RSX_METRIC_L2 ? h->w_misc.as<float>() : nullptr;
-    a.list_base = h->d_base.as<int64_t>(); a.list_len = h->d_len.as<int64_t>();
-    a.pairs_sorted = pr.pairs_sorted; a.pair_off = pr.pair_off; a.group_off = pr.group_off; a.total_groups = pr.total_groups;
-    a.probe_list = h->w_probelist.as<int32_t>(); a.seg_start = h->w_segstart.as<int64_t>();
-    a.nlist = pr.nlist; a.nprobe = pr.nprobe; a.flat_mode = 0; a.nq = (int)P.nq;
-    a.temp = h->w_temp.as<float>(); a.tstride = P.tmax;
-    a.max_groups = (int)std::min<int64_t>(npairs, npairs / 16 + std::min<int64_t>(pr.nlist, npairs));
-    return a;
-}
 // group (query, probe) pairs by list, then list-major MFMA scan
 static void ivf_flat_scan(rsx_index* h, const BatchPlan& P, BatchResult& R, StageTimer& tm) {
     const int64_t nq = P.nq, npairs = nq * P.nprobe; const int nlist = h->nlist, nprobe = P.nprobe, ld = h->ld;
     const PairArea pr(h, nq, nprobe, nlist);
-    // probing queries per group of the LDS-DMA list scans.  A group passes over its list's rows once, so the larger the group the fewer
-    // passes: 16 (k_list_scan2<_, 1>: two workgroups per CU), 64 (the 8-wave form, queries in LDS) or 128 (k_list_scan3, queries in
-    // registers: d = 384 / 512 / 768 / 1024).  Round 5, 20M x 768, inner product, batch 1024 (profiles/r05_ivfflat_wide.md): at 8 probing queries per
-    // list on average 16 wins (5.47 ms against 5.59 with 64), at 16 already 64 does (nlist 2048 / nprobe 32: 5.08 against 5.95;
-    // nlist 4096 / nprobe 64: 6.93 against 8.53), at 32 64 beats 128 (5.20 against 5.61: no list needs a second pass yet, and the
-    // 8-wave form has no barrier), at 64 and more 128 wins (6.04 against 7.23; nlist 1024 / nprobe 128: 10.6 against 11.4).  The
-    // 32-query form lost everywhere and is only reachable through the parameter.
+    // probing queries per group of the LDS-DMA list scans (list_scan_qtiles; "scan_chunk" takes the batch to the older scan: groups of 16)
     int ls_qt = 1;
-    if (h->scan_chunk <= 0 && h->ivf_qtiles != 0 && list_scan2_chunk_rows(h->storage_f16, ld) > 0) {
-        const int64_t qpl = npairs / std::max(1, nlist);
-        const bool ls3 = list_scan3_applies(h->storage_f16, ld, h->metric == RSX_METRIC_L2) != 0;      // 128 queries per group, held in registers (k_list_scan3)
-        ls_qt = h->ivf_qtiles > 1 ? h->ivf_qtiles : (qpl >= 48 && ls3 ? 8 : qpl >= 12 ? 4 : 1);
-        if (ls_qt == 8 && !ls3) ls_qt = 4;
-        if (ls_qt != 8) ls_qt = std::min(ls_qt == 3 ? 2 : ls_qt, list_scan2_max_qtiles(ld));
-        if (ls_qt != 2 && ls_qt != 4 && ls_qt != 8) ls_qt = 1;
-    }
+    if (h->scan_chunk <= 0 && list_scan2_chunk_rows(h->storage_f16, ld) > 0)
+        ls_qt = list_scan_qtiles(h, npairs, list_scan3_applies(h->storage_f16, ld, h->metric == RSX_METRIC_L2) != 0);
     // (list, chunk, group) work items in list-major order for the LDS-DMA scan's XCD-aware 1-D grid (round 4): the groups of a
     // list chunk run on one XCD at the same moment and its rows cross HBM once — at nlist 2048 / nprobe 128 half of the lists
     // are probed by more than 64 queries, i.e. by two groups, which used to land on different XCDs (two fetches)
@@ -1187,7 +1031,7 @@ static void ivf_flat_scan(rsx_index* h, const BatchPlan& P, BatchResult& R, Stag
     const int item_rows = (h->scan_chunk <= 0 && ls2_rows > 0) ? (ls_wide ? 2 * ls2_rows : ls2_rows) : 0;
     pr.group(16 * ls_qt, item_rows, nprobe, 0, h->st);
     tm.mark("group");
-    ListScanArgs a = list_scan_args(h, P, pr);
+    ListScanArgs a = list_scan_args(h, P.nq, P.tmax, pr);
     a.Q16 = h->w_q16.as<__half>(); a.X = h->data.p; a.x_f16 = h->storage_f16;
     int64_t chunk_rows = h->scan_chunk > 0 ? round_up(h->scan_chunk, 64) : 2048;
     int64_t want = 2048;  // work items
@@ -1232,7 +1076,7 @@ static void ivf_sq_scan(rsx_index* h, const BatchPlan& P, BatchResult& R, StageT
     const int base_rows = sq_list_scan_chunk_rows(1), item_rows = sq_list_scan_chunk_rows(ls_qt);
     pr.group(16 * ls_qt, item_rows, nprobe, 0, h->st);
     tm.mark("group");
-    ListScanArgs a = list_scan_args(h, P, pr);
+    ListScanArgs a = list_scan_args(h, P.nq, P.tmax, pr);
     a.sq_codes = h->data.as<uint8_t>(); a.sq_qhi = h->w_sqhi.as<__half>(); a.sq_qlo = h->w_sqlo.as<__half>(); a.sq_qc = h->w_sqc.as<float>();
     a.sq_dis0 = h->by_residual ? h->w_dis0.as<float>() : nullptr;
     a.chunk_rows = base_rows; a.qtiles = ls_qt;
@@ -1402,12 +1246,6 @@ static void search_batch(rsx_index* h, int64_t nq, const void* dq, int dtype, in
     if (P.fast || P.certify) rerun_uncertified(h, nq, dq, dtype, k, dD, dI, (size_t)P.tmax * 4, P.coarse_fast, pq_second_chance(h, P, R, fa));
 }
 
-// L2 ranking bias  -|x|^2/2  from the stored squared norms
-__global__ void k_bias_from_norms(const float* norms, float* bias, int64_t n) {
-    int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n) bias[i] = -0.5f * norms[i];
-}
-
 // The slot mask of h->sel over the handle's storage (k_sel_mask), rebuilt only when the selector or the index state changed: every
 // add / add_list / reset / re-layout bumps dir_gen (upload_dir), and a re-layout also moves the storage.
 static void ensure_sel_mask(rsx_index* h) {
@@ -1452,12 +1290,7 @@ void search_impl(rsx_index* h, int64_t nq, const void* q, int dtype, int k, floa
         HIPCHECK(hipMemcpy(I, hi.data(), hi.size() * 8, o_dev ? hipMemcpyHostToDevice : hipMemcpyHostToHost));
         return;
     }
-    if (h->metric == RSX_METRIC_L2 && h->kind != KIND_IVFPQ) {
-        int64_t rows = h->total_cap;
-        h->w_misc.ensure((size_t)rows * 4);
-        hipLaunchKernelGGL(k_bias_from_norms, dim3((unsigned)((rows + 255) / 256)), dim3(256), 0, h->st, h->norms.as<float>(),
-                           h->w_misc.as<float>(), rows);
-    }
+    if (h->metric == RSX_METRIC_L2 && h->kind != KIND_IVFPQ) l2_bias_rows(h);
     if (h->sel) ensure_sel_mask(h);
     // batch size: bounded by the knob and by the score-buffer budget (the plan's row sizes depend on neither nq nor the query buffer)
     int64_t qb = std::max(1, h->query_batch);

@@ -106,6 +106,15 @@ void launch_fill_f32(float* p, int64_t n, float v, hipStream_t st) {
     int blocks = (int)((n + 255) / 256); if (blocks > 4096) blocks = 4096;
     hipLaunchKernelGGL(k_fill_f32, dim3(blocks), dim3(256), 0, st, p, n, v);
 }
+// L2 ranking bias  -|x|^2/2  from the stored squared norms
+__global__ void k_bias_from_norms(const float* norms, float* bias, int64_t n) {
+    int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n) bias[i] = -0.5f * norms[i];
+}
+void launch_bias_from_norms(const float* norms, float* bias, int64_t n, hipStream_t st) {
+    if (n <= 0) return;
+    hipLaunchKernelGGL(k_bias_from_norms, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, norms, bias, n);
+}
 
 // ---------------------------------------------------------------------------------------
 // Synthetic Gaussian mixture — bit-identical to oracle/rsx_oracle.c orc_synth_* (integer hash,

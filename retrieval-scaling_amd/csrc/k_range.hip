@@ -5,7 +5,7 @@
 //                    of 4096 keys, the strides beyond a tile through global memory)
 //   k_range_lims     exclusive scan of the member counts
 //   k_range_emit / k_range_ties   D and I at lims[q]; runs of equal scores reordered by id where ids are not the scan's indices
-//   k_range_compact / k_range_gather_rows / k_range_bias   what the second pass of overflowed queries and the L2 scans need
+//   k_range_compact / k_range_gather_rows   what the second pass of overflowed queries needs
 #include "rsx_range.h"
 #include "k_rescore.h"
 
@@ -13,7 +13,7 @@ namespace rsx {
 
 // ---------------------------------------------------------------------------------------
 // The threshold.  The scans rank a stored vector x by r = <q, x> (inner product) or r = <q, x> - |x|^2 / 2 (L2: |q - x|^2 = |q|^2 - 2 r) and
-// compute r~ with |r~ - r| <= eps = rel |q| xmax + cert_abs (|q| + xmax) (api_search.hip: finalize_args; k_finalize forms the same
+// compute r~ with |r~ - r| <= eps = rel |q| xmax + cert_abs (|q| + xmax) (api_stages.hip: scan_cert_bound; k_finalize forms the same
 // expression, and so does this kernel, in fp32 with qn >= |q|).  Membership is decided on the canonical value c = fl32(v), v the fp64 sum:
 //   inner product:  c > radius.  Rounding to nearest is monotone and radius is an fp32 number, so c > radius implies v > radius; v differs
 //                   from the real <q, x> by the fp64 accumulation, at most d 2^-53 |q| |x|.  On top of that one fp32 rounding of the score
@@ -57,15 +57,6 @@ __global__ __launch_bounds__(256) void k_range_tau(RangeTauArgs a) {
 void launch_range_tau(const RangeTauArgs& a, hipStream_t st) {
     if (a.nq <= 0) return;
     hipLaunchKernelGGL(k_range_tau, dim3((unsigned)((a.nq + 3) / 4)), dim3(256), 0, st, a);
-}
-
-__global__ void k_range_bias(const float* norms, float* bias, int64_t n) {
-    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n) bias[i] = -0.5f * norms[i];
-}
-void launch_range_bias(const float* norms, float* bias, int64_t n, hipStream_t st) {
-    if (n <= 0) return;
-    hipLaunchKernelGGL(k_range_bias, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, norms, bias, n);
 }
 
 __device__ inline int range_pow2ceil(int n) { int p = 1; while (p < n) p <<= 1; return p; }

@@ -2,6 +2,7 @@
 // (struct rsx_index = the opaque rsx_index_t of include/rsx.h) and the prototypes of the host functions that cross files.
 //   api_build.hip    HBM layout management, add / train, list import / export, persistence
 //   api_search.hip   the search drivers (search_batch = one internal batch, search_impl = one rsx_search call)
+//   api_stages.hip   the batch stages that search and range_search share (declarations in rsx_stages.h)
 //   api_refine.hip   rsx_refine: exact re-ranking of candidate labels against a Flat row store (k_refine.hip)
 //   api_range.hip    rsx_range_search: every neighbour within a radius, Flat and IVF-Flat (k_range.hip; declarations in rsx_range.h)
 //   api_reconstruct.hip  rsx_reconstruct_batch / rsx_make_direct_map: stored vectors by id (k_reconstruct.hip; rsx_reconstruct.h)
@@ -133,6 +134,7 @@ static inline bool is_device_ptr(const void* p) {
 
 static inline int64_t round_up(int64_t x, int64_t a) { return (x + a - 1) / a * a; }
 static inline int pow2ceil(int x) { int p = 1; while (p < x) p <<= 1; return p; }
+static inline int64_t pow2ceil64(int64_t x) { int64_t p = 1; while (p < x) p <<= 1; return p; }
 
 // ---------------------------------------------------------------------------------------
 // deterministic host RNG shared with the training spec (splitmix64 Fisher-Yates)

@@ -200,6 +200,7 @@ void launch_residuals(const float* x, int64_t n, int d, const float* centroids, 
 void launch_fill_u64(uint64_t* p, int64_t n, uint64_t v, hipStream_t st);
 void launch_keep_last_u64(uint64_t* p, int64_t rows, int len, hipStream_t st);   // zero all but the last key of each row
 void launch_fill_f32(float* p, int64_t n, float v, hipStream_t st);
+void launch_bias_from_norms(const float* norms, float* bias, int64_t n, hipStream_t st);      // L2 ranking bias -|x|^2 / 2 of every storage row
 void launch_synth_vectors(int d, int ncentres, uint32_t seed_c, uint32_t seed_x, float sigma, int64_t i0,
                           int64_t n, __half* out, hipStream_t st);
 void launch_synth_queries(int d, int ncentres, uint32_t seed_c, uint32_t seed_x, float sigma, int64_t nbase,

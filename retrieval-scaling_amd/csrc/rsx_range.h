@@ -1,7 +1,7 @@
 // rsx_range.h — range search (faiss Index::range_search): the launch interface of k_range.hip, the library-owned result
 // object behind rsx_range_result_t (include/rsx.h) and the host driver's entry (api_range.hip).
 #pragma once
-#include "rsx_host.h"
+#include "rsx_stages.h"
 
 namespace rsx {
 
@@ -10,12 +10,11 @@ namespace rsx {
 struct RangeTauArgs {
     const float* Q32; int ldq; int d; int64_t nq;
     int metric; float radius;
-    float cert_rel, cert_rel_qlossy, cert_xmax, cert_abs; const int* cert_qflag;     // the scan's error bound, as FinalizeArgs carries it
+    float cert_rel, cert_rel_qlossy, cert_xmax, cert_abs; const int* cert_qflag;     // the scan's error bound (scan_cert_bound), as FinalizeArgs carries it
     uint64_t* tau;                       // [nq] out
     unsigned long long* cand_cnt;        // [nq * CCS] out: zeroed
 };
 void launch_range_tau(const RangeTauArgs& a, hipStream_t st);
-void launch_range_bias(const float* norms, float* bias, int64_t n, hipStream_t st);      // L2 ranking bias -|x|^2 / 2 of every storage row
 
 // Candidate rows of one scan: row r holds rcnt[r] keys (approximate score, index) in cand[r * cap ..); the row belongs to query
 // qsel[r] of the batch (null: r).  cap is a power of two.

@@ -17,6 +17,9 @@ FLAT_RADII = {0: (125.0, 97.0, 8.0), 1: (0.99, 54.0, 226.0)}
 IVF = dict(d=64, n=60000, nq=203, nlist=40, ncent=16)
 IVF_RADII = {0: (75.0, 50.0), 1: (20.0, 40.0)}       # (about ten results per query, thousands per query)
 IVF768_RADII = {0: 740.0, 1: 380.0}
+# many lists: nlist = 12 800 is the smallest at which the coarse selection (16 keys kept, segments of 4096 scores) has four segments and
+# takes its two-phase form; the centroids are further rows of the vectors' mixture, so most lists stay empty
+WIDE = dict(d=32, n=60000, nq=70, nlist=12800, ncent=16, nprobe=6)
 # fp32 storage (test_gpu_range.py: fp32_case): no oracle score lies within 8 ulp of these (tests/test_range_host.py checks it)
 FP32_RADII = {0: 97.0, 1: 54.0}
 
@@ -95,9 +98,23 @@ def ivf_inputs():
 
 
 @functools.lru_cache(maxsize=None)
+def wide_inputs():
+    orc = _orc()
+    c = Case()
+    c.__dict__.update(WIDE)
+    c.x = orc.synth_vectors(c.d, c.ncent, util.SEED_C, util.SEED_X, 0.5, 0, c.n)
+    c.q = orc.synth_queries(c.d, c.ncent, util.SEED_C, util.SEED_X, 0.5, c.n, util.SEED_Q, 0.1, 0, c.nq)
+    c.x32, c.q32 = c.x.astype(F32), c.q.astype(F32)
+    c.cen = orc.synth_vectors(c.d, c.ncent, util.SEED_C, util.SEED_X, 0.5, c.n, c.nlist).astype(F32)
+    c.assign, _ = orc.assign_ip(c.cen, c.x32)
+    c.sizes = np.bincount(c.assign, minlength=c.nlist)
+    return c
+
+
+@functools.lru_cache(maxsize=None)
 def ivf_full(name, metric, nprobe, explicit_ids=False):
-    """name "ivf": the case above; "D": sq_ref's d = 768 set (n 20 000, nlist 32, 200 queries)"""
-    c = ivf_inputs() if name == "ivf" else sq_ref.inputs("D")
+    """name "ivf": the case above; "wide": the many-lists case; "D": sq_ref's d = 768 set (n 20 000, nlist 32, 200 queries)"""
+    c = ivf_inputs() if name == "ivf" else wide_inputs() if name == "wide" else sq_ref.inputs("D")
     orc = _orc()
     ids = 7 * np.arange(c.n, dtype=np.int64) + 1000003 if explicit_ids else np.arange(c.n, dtype=np.int64)
     lm = orc.ListMajor(c.assign, ids, c.x32, c.nlist)
@@ -112,7 +129,7 @@ def ivf_expected(name, metric, nprobe, radius, explicit_ids=False):
 
 # ------------------------------------------------------------------------------------------ the threshold, restated
 def scan_bound(d, metric, max_norm2, storage_f16):
-    """(rel, rel_qlossy, xmax, abs) of the fp16 scans' error bound (api_range.hip: scan_bound), fp32 as the library forms them"""
+    """(rel, rel_qlossy, xmax, abs) of the fp16 scans' error bound (api_stages.hip: scan_cert_bound), fp32 as the library forms them"""
     u24, u11 = F32(5.9604645e-8), F32(4.8828125e-4)
     xmax = F32(np.sqrt(F32(max_norm2))) * F32(1.0000002)
     rel = (F32(d) + F32(2)) * u24 * F32(1.01) + (F32(0) if storage_f16 else u11 * F32(1.002))

@@ -175,6 +175,37 @@ def test_ivf_d768_takes_a_filtered_form(gpu, metric):
     both_paths(ix, c.q, radius, want, f"IVF-Flat d 768 metric {metric}")
 
 
+@pytest.mark.parametrize("metric", [0, 1])
+def test_ivf_two_phase_probe_selection(gpu, metric):
+    """nlist = 12 800: the coarse selection runs over four segments of centroid scores, i.e. in its two-phase form (select_rows, nseg >= 4);
+    the probes, and with them the result, must be the oracle's.  Radius: the median over the queries of the 20th best oracle score."""
+    c = rr.wide_inputs()
+    ix = gpu.IndexIVFFlat(None, c.d, c.nlist, metric, device=0)
+    ix.set_centroids(c.cen)
+    ix.add(c.x)
+    ix.nprobe = c.nprobe
+    D, _ = rr.ivf_full("wide", metric, c.nprobe)
+    radius = float(np.median(D[:, 19]))
+    want = rr.ivf_expected("wide", metric, c.nprobe, radius)
+    counts = np.diff(want[0])
+    print(f"metric {metric}: radius {radius}, results per query median {np.median(counts)} max {counts.max()}, non-empty lists {(c.sizes > 0).sum()}")
+    assert 0 < np.median(counts) < 5000
+    both_paths(ix, c.q, radius, want, f"IVF-Flat nlist {c.nlist} metric {metric}")
+
+
+@pytest.mark.parametrize("qtiles", [2, 3, 8, 9])
+def test_ivf_forced_group_sizes(ivf_ix, qtiles):
+    """"ivf_qtiles" 2 and 3 ask for groups of 32 probing queries, 8 and 9 for more than the filtered scans have: 64"""
+    c = rr.ivf_inputs()
+    ix, radius = ivf_ix[0], rr.IVF_RADII[0][0]
+    ix.nprobe = 6
+    ix.set_param("ivf_qtiles", qtiles)
+    try:
+        both_paths(ix, c.q, radius, rr.ivf_expected("ivf", 0, 6, radius, True), f"IVF-Flat ivf_qtiles {qtiles}")
+    finally:
+        ix.set_param("ivf_qtiles", 1)
+
+
 # ------------------------------------------------------------------------------------------ ties and edges
 @pytest.mark.parametrize("kind", ["flat", "ivf"])
 def test_ties_come_back_in_id_order(gpu, kind):
