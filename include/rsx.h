@@ -358,6 +358,29 @@ int rsx_make_direct_map(rsx_index_t* h, int type);
  * Refused with the handle untouched: sharded handles (RSX_ERR_UNSUPPORTED), n < 0, a null pointer with n > 0 (RSX_ERR_INVALID). */
 int rsx_reconstruct_batch(rsx_index_t* h, int64_t n, const int64_t* keys, int fill_negative, float* out);
 
+/* ---- vector transforms (FAISS VectorTransform / LinearTransform) --------------------- */
+
+/* faiss.LinearTransform and its subclasses (RandomRotationMatrix, PCAMatrix, OPQMatrix) as the library sees them: a matrix A
+ * float32 [d_out, d_in] row-major and an optional bias b [d_out] on one device, applied on the GPU (k_vt_apply).
+ * The reference has no transform; FAISS applies it on the CPU in front of an index (IndexPreTransform; factory "OPQ96,..." / "PCA256,..."). */
+typedef struct rsx_vt rsx_vt_t;
+
+int rsx_vt_create(int device, int d_in, int d_out, rsx_vt_t** out);
+/* A [d_out, d_in] and b [d_out] or NULL (no bias): HOST float32 arrays, copied; replaces what an earlier call set.  Uploads A, its
+ * transposed copy (the reverse transform's operand) and b. */
+int rsx_vt_set(rsx_vt_t* vt, const float* A, const float* b_or_null);
+/* reverse = 0, LinearTransform::apply:  x [n, d_in] (dtype RSX_F32 or RSX_F16) -> y float32 [n, d_out],
+ *     y_j = fl32(s_j + b_j),  s_j = fmaf(x[t], A[j][t], s) for t = 0 .. d_in - 1 from +0  (fp16 widened exactly; no bias: y_j = s_j);
+ * reverse != 0, LinearTransform::transform_transpose (the inverse of an orthonormal A; the caller checks that):  x [n, d_out] ->
+ * y float32 [n, d_in],  y_t = fmaf(fl32(x[j] - b_j), A[j][t], s) for j = 0 .. d_out - 1 from +0.
+ * Both are one sequential fp32 chain per output, bit for bit reproducible (f32-input MFMA).  x and y are HOST or DEVICE pointers, each
+ * on its own; a host operand is staged through at most 64 MiB of device memory per chunk.  Runs on the handle's own stream and
+ * returns when the work is complete; device inputs must be complete when the call is made.  n = 0 succeeds and touches nothing.
+ * RSX_ERR_NOT_TRAINED before rsx_vt_set; RSX_ERR_INVALID: n < 0, a bad dtype, a null pointer with n > 0. */
+int rsx_vt_apply(rsx_vt_t* vt, int64_t n, const void* x, int dtype, float* y, int reverse);
+/* NULL is accepted */
+int rsx_vt_destroy(rsx_vt_t* vt);
+
 /* ---- range search (FAISS Index::range_search) -------------------------------------- */
 
 /* faiss RangeSearchResult: the library-owned answer of one rsx_range_search, whose size is known only after the scan.  It lives in

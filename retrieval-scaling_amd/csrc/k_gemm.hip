@@ -20,46 +20,16 @@
 //                 the group's queries held in LDS (v_mfma_f32_16x16x32_f16).  HBM-bound by design:
 //                 a list is read once per batch for all queries that probe it.
 #include "rsx_internal.h"
+#include "k_gemm_tile.h"
 
 namespace rsx {
 
-typedef float floatx16 __attribute__((ext_vector_type(16)));
 typedef float floatx4 __attribute__((ext_vector_type(4)));
 typedef _Float16 half8 __attribute__((ext_vector_type(8)));
 
 // =======================================================================================
 // exact f32 GEMM
 // =======================================================================================
-template <bool XF16>
-__device__ inline void load16_f32(const void* X, int64_t row, int ldx, int t0, int d, bool vec_ok, float* out) {
-    if (XF16) {
-        const __half* p = (const __half*)X + row * ldx + t0;
-        if (vec_ok && t0 + 16 <= d) {
-            uint4 u0 = *reinterpret_cast<const uint4*>(p);
-            uint4 u1 = *reinterpret_cast<const uint4*>(p + 8);
-            const __half* h0 = reinterpret_cast<const __half*>(&u0);
-            const __half* h1 = reinterpret_cast<const __half*>(&u1);
-#pragma unroll
-            for (int e = 0; e < 8; e++) { out[e] = __half2float(h0[e]); out[8 + e] = __half2float(h1[e]); }
-        } else {
-#pragma unroll
-            for (int e = 0; e < 16; e++) out[e] = (t0 + e < d) ? __half2float(p[e]) : 0.0f;
-        }
-    } else {
-        const float* p = (const float*)X + row * ldx + t0;
-        if (vec_ok && t0 + 16 <= d) {
-#pragma unroll
-            for (int e = 0; e < 4; e++) {
-                float4 f = *reinterpret_cast<const float4*>(p + 4 * e);
-                out[4 * e] = f.x; out[4 * e + 1] = f.y; out[4 * e + 2] = f.z; out[4 * e + 3] = f.w;
-            }
-        } else {
-#pragma unroll
-            for (int e = 0; e < 16; e++) out[e] = (t0 + e < d) ? p[e] : 0.0f;
-        }
-    }
-}
-
 template <bool XF16, bool ARGMAX>
 __global__ __launch_bounds__(256) void k_gemm_exact(const void* X, int64_t n, int ldx, int x_vec_ok, const float* C,
                                                     int nc, int d, int c_vec_ok, float* S, int64_t lds_,
@@ -155,8 +125,6 @@ __global__ void k_argmax_reduce(const uint64_t* partial, int64_t n, int npart, i
     assign[i] = b ? (int32_t)key_idx(b) : 0;
     if (best) best[i] = b ? key_score(b) : -__builtin_inff();
 }
-
-static inline int aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
 
 // The same scores for a handful of rows (single-query / small-batch latency path): the 128 x 128 MFMA tile would run
 // nc / 128 workgroups with 127 idle rows each, and a thread walking its own centroid row has one cache line in flight.

@@ -68,7 +68,7 @@ static int search_prepass_common(rsx_index_t* h, int64_t nq, const void* q, int 
 extern "C" {
 
 const char* rsx_last_error(void) { return g_err.c_str(); }
-int rsx_version(void) { return 1007; }     // 1007: rsx_make_direct_map, rsx_reconstruct_batch; 1001: filtered search (rsx_selector_*, rsx_search_sel, rsx_search_prepass_sel); 1002: rsx_remove_ids; 1003: rsx_pq_create; 1004: rsx_refine; 1005: rsx_ivfsq_create; 1006: rsx_range_search, rsx_range_result_get, rsx_range_result_destroy
+int rsx_version(void) { return 1008; }     // 1008: rsx_vt_create, rsx_vt_set, rsx_vt_apply, rsx_vt_destroy (api_vt.hip); 1007: rsx_make_direct_map, rsx_reconstruct_batch; 1001: filtered search (rsx_selector_*, rsx_search_sel, rsx_search_prepass_sel); 1002: rsx_remove_ids; 1003: rsx_pq_create; 1004: rsx_refine; 1005: rsx_ivfsq_create; 1006: rsx_range_search, rsx_range_result_get, rsx_range_result_destroy
 
 int rsx_device_count(int* n) {
     return guarded([&] {

@@ -6,6 +6,7 @@
 //   api_refine.hip   rsx_refine: exact re-ranking of candidate labels against a Flat row store (k_refine.hip)
 //   api_range.hip    rsx_range_search: every neighbour within a radius, Flat and IVF-Flat (k_range.hip; declarations in rsx_range.h)
 //   api_reconstruct.hip  rsx_reconstruct_batch / rsx_make_direct_map: stored vectors by id (k_reconstruct.hip; rsx_reconstruct.h)
+//   api_vt.hip       rsx_vt_*: the linear vector transform handle and its entry points (k_vt.hip)
 //   api_sharded.hip  the single-process multi-GPU handle
 //   api_remove.hip   rsx_remove_ids: the removal plan and compaction (k_remove.hip) on a handle and on the shards of one
 //   rsx_api.hip      the extern "C" entry points

@@ -237,6 +237,13 @@ void launch_gemm_exact_scores(const void* X, int x_f16, int64_t n, int ldx, cons
 // assign[i] = argmax_c <X_i, C_c> (first maximum).  partial: workspace [n, 2*ceil(nc/128)] u64.
 void launch_gemm_exact_argmax(const void* X, int x_f16, int64_t n, int ldx, const float* C, int nc, int d,
                               uint64_t* partial, int32_t* assign, float* best, hipStream_t st);
+// k_vt.hip
+// Y[i, j] = fl32(<X'_i, C_j> + badd[j]) as one sequential fp32 fmaf chain over t = 0..d-1 (f32-input MFMA), X'[t] = fl32(X[t] - bsub[t]).
+// X: [n, d] f32 or f16;  C: [nc, d] f32;  bsub [d] / badd [nc] or null;  Y: [n, nc] f32.
+void launch_vt_apply(const void* X, int x_f16, int64_t n, int d, const float* bsub, const float* C, int nc, const float* badd, float* Y,
+                     hipStream_t st);
+// At [cols, rows] = A [rows, cols] transposed
+void launch_vt_transpose(const float* A, int rows, int cols, float* At, hipStream_t st);
 // Flat scan: temp[q, v] = <Q_q, X_v> (fp16 MFMA, fp32 accumulate) for v in [v0, v0+nv).
 // Q16: [nq_pad(128), ld] f16; X: [., ld] f16|f32 storage (ld multiple of 64); bias: per-row or null.
 void launch_flat_gemm(const __half* Q16, int nq_pad, const void* X, int x_f16, int64_t v0, int64_t nv,

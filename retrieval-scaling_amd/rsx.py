@@ -16,6 +16,8 @@ written against `faiss`:
     index.train / add / search / nprobe / ntotal / is_trained            same
     index.range_search(x, radius)         (faiss.Index verb; Flat, IVF-Flat) same, lims as int64
     faiss.read_index / write_index                                        rsx.read_index / write_index
+    faiss.VectorTransform / LinearTransform / RandomRotationMatrix / PCAMatrix / OPQMatrix, IndexPreTransform,
+        index_factory, extract_index_ivf, downcast_index  (factory "OPQ96,IVF4096,PQ96")   same names (module rsx_vt, re-exported here)
     StandardGpuResources / GpuClonerOptions / index_cpu_to_gpu / index_gpu_to_cpu
         (ivf_flat.py:155-163: CUDA-only training clone)                   identity shims — the index
                                                                           already lives on the GPU
@@ -52,6 +54,7 @@ ABI_SYMBOLS = [
     "rsx_ivfsq_create", "rsx_set_sq_trained", "rsx_get_sq_trained",
     "rsx_range_search", "rsx_range_result_get", "rsx_range_result_destroy",
     "rsx_make_direct_map", "rsx_reconstruct_batch",
+    "rsx_vt_create", "rsx_vt_set", "rsx_vt_apply", "rsx_vt_destroy",
 ]
 
 
@@ -1056,6 +1059,12 @@ def write_index(index, path):
     file is called — the reference's mirrors keep its `index_*.faiss` names).  RSX_INDEX_FORMAT=faiss writes a FAISS-format file
     through rsx_faiss_io instead, for hand-over to a real faiss.read_index (written from upstream knowledge of the format,
     unverified against a FAISS-produced file: DESIGN.md)."""
+    if getattr(index, "_is_pretransform", False):
+        if os.environ.get("RSX_INDEX_FORMAT", "").lower() == "faiss":
+            raise RuntimeError("write_index: an IndexPreTransform has no FAISS-format writer in this build (RSX_INDEX_FORMAT=faiss; FAISS's IxPT / VTrs "
+                               "records); unset it to write the native RSXT manifest")
+        from rsx_vt import _write_pretransform
+        return _write_pretransform(index, os.fspath(path))
     if os.environ.get("RSX_INDEX_FORMAT", "").lower() == "faiss" and index.nshards == 0:
         if isinstance(index, IndexIVFScalarQuantizer):
             raise RuntimeError("write_index: an IndexIVFScalarQuantizer (kind 4) has no FAISS-format writer in this build (RSX_INDEX_FORMAT=faiss); "
@@ -1107,7 +1116,7 @@ def _read_refine(path, device):
 
 def read_index(path, device=None, devices=None):
     """faiss.read_index(path): loads an RSX1 container (RSXS: the manifest of a sharded index, one shard per device; RSXR: the
-    manifest of an IndexRefineFlat, one device only), or a FAISS-format file via rsx_faiss_io.
+    manifest of an IndexRefineFlat, RSXT: the manifest of an IndexPreTransform, one device only), or a FAISS-format file via rsx_faiss_io.
 
     A multi-device request (devices=[...] / "all", cfg.datastore.index.devices, RSX_DEVICES) on a file written from ONE
     index — RSX1 or FAISS — RE-SHARDS it while loading: every inverted list / row block is cut over the devices as it
@@ -1130,6 +1139,13 @@ def read_index(path, device=None, devices=None):
         raise RuntimeError(f"{path}: an IndexRefineFlat cannot be loaded onto several devices (no sharded form)")
     if magic == _REFINE_MAGIC:
         return _read_refine(path, device)
+    if magic in (b"RSXT", b"IxPT") and multi:
+        raise RuntimeError(f"{path}: an IndexPreTransform cannot be loaded onto several devices (no sharded form)")
+    if magic == b"RSXT":
+        from rsx_vt import _read_pretransform
+        return _read_pretransform(path, device)
+    if magic == b"IxPT":
+        raise RuntimeError(f"{path}: a FAISS-format IndexPreTransform (IxPT) has no reader in this build; write it with rsx.write_index (RSXT)")
     if magic != b"RSX1":
         from rsx_faiss_io import read_faiss_index
         return read_faiss_index(path, device=device, devices=devs if multi else None)
@@ -1247,3 +1263,14 @@ def index_cpu_to_gpu(res, device, index, co=None):
 
 def index_gpu_to_cpu(index):
     return index
+
+
+# ------------------------------------------------------------------------------------------
+# vector transforms, IndexPreTransform, index_factory: module rsx_vt, written against the names above and re-exported here on first use
+# (PEP 562), so that either module can be imported first
+# ------------------------------------------------------------------------------------------
+def __getattr__(name):
+    import rsx_vt
+    if name in rsx_vt.__all__:
+        return getattr(rsx_vt, name)
+    raise AttributeError(f"module 'rsx' has no attribute {name!r}")
