@@ -244,8 +244,8 @@ int rsx_get(rsx_index_t* h, const char* key, int64_t* out);
  * pre-pass, default 2048, 0 = one scan tile), "pq_tau_anchor" (filtered fast scan, four-query pre-pass: 1 = the threshold is anchored on the
  * exact scores of the sample's k best rows [default], 0 = the approximate k-th best minus 2 eps alone; read per search), "ivf_filter" (IVF-Flat: candidates filtered inside the list scan: 1 = when
  * the score rows of the batch would exceed ~2 GB [default], 2 = always, 0 = never = full score rows), "pq_prepass_fused" (filtered fast scan: 1 = threshold pre-pass in one launch [default], 0 = grouping +
- * scan + selection launches), "lut_tiled" (IVFPQ fast scan, dsub = 8: 1 = 8-bit tables built by
- * codebook-slice tiles shared by 32 queries [default], 0 = one workgroup per query), "flat_filter" (Flat: 1 = one filtered GEMM launch after the first chunk [default], 0 = score buffer
+ * scan + selection launches), "lut_tiled" (IVFPQ fast scan, dsub = 8: non-zero = 8-bit tables built by
+ * tiles that share codebook slices among queries [default 2; inner product: on the matrix cores, IndexPQ L2: VALU tiles], 0 = one workgroup per query), "flat_filter" (Flat: 1 = one filtered GEMM launch after the first chunk [default], 0 = score buffer
  * per chunk), "pq_flat_first" / "pq_flat_growth" / "pq_flat_max_stages" (IndexPQ staged scan: rows of the first stage, 0 =
  * default; percent by which each stage outgrows the one before, 0 = default 300; most stages, 0 = default 12), "range_cand_cap" (rsx_range_search: keys a query's candidate row holds in the first scan, 0 = default 65536), "profile" (1 = record stage timings with HIP
  * events on the library's stream; 2 = additionally count the vectors each search scanned). */

@@ -3,11 +3,6 @@
 #include "rsx_host.h"
 
 void use_device(rsx_index* h) { HIPCHECK(hipSetDevice(h->device)); }
-void ensure_side_stream(rsx_index* h) {
-    if (h->st2) return;
-    HIPCHECK(hipStreamCreateWithFlags(&h->st2, hipStreamNonBlocking));
-    for (hipEvent_t* e : {&h->ev_fork, &h->ev_probe, &h->ev_lut, &h->ev_group}) HIPCHECK(hipEventCreateWithFlags(e, hipEventDisableTiming));
-}
 // A two-call search that is parked between rsx_search_prepass and rsx_search_scan owns the handle's workspaces (thresholds,
 // candidate rows, state): every other entry point refuses to touch the handle until rsx_search_scan has finished it.
 void refuse_while_two_call(const rsx_index* h, const char* what) {

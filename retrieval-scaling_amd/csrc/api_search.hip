@@ -71,7 +71,7 @@ struct BatchPlan {
     int KP, BUF;               // selection state: K' keys per query, the selection's buffer
     bool certify;              // Flat / IVF-Flat: the fp16 scans are certified and the uncertain queries re-run exactly
     bool coarse_fast, q16_direct;
-    bool pq_fused_lut, side_lut, tab_expected, lut_pass0_early;
+    bool pq_fused_lut, tab_expected, lut_pass0_early;
     bool sl_eight; int ngq;    // sliced layout: eight queries per gather; 4-query records per work item of the filtered scan
     // the in-scan candidate filters in effect: the knobs, all off for a filtered search (h->sel), which takes the routes whose scans write
     // complete score rows
@@ -109,10 +109,8 @@ static BatchPlan plan_batch(rsx_index* h, int64_t nq, const void* dq, int dtype,
                     coarse_pick_lds(h->nlist, h->d, P.nprobe) <= 150 * 1024;
     // ... whose fp16 operand is the caller's own batch when that is fp16, unpadded (d = ld) and whole tiles: the fp32 copy then rides in the
     // GEMM's launch (extra grid rows) instead of a conversion launch of its own
-    // (not with the side-stream table build: it reads the fp32 copy before the GEMM has run)
-    P.q16_direct = pq && P.coarse_fast && h->overlap == 0 && dtype == RSX_F16 && h->d == h->ld && nq % 128 == 0 && ((uintptr_t)dq & 15) == 0;
+    P.q16_direct = pq && P.coarse_fast && dtype == RSX_F16 && h->d == h->ld && nq % 128 == 0 && ((uintptr_t)dq & 15) == 0;
     P.pq_fused_lut = pq && P.fast && pq_lut8_fused_lds(h->M, h->Mpad, h->dsub) <= 160 * 1024 - 64;
-    P.side_lut = P.pq_fused_lut && !l2 && h->overlap != 0 && h->dsub == 8 && h->lut_tiled != 0 && nq >= 64;      // (the side-stream split is a tiled-builder form)
     // the finalize-from-the-row kernel (k_pq_final_tab) will serve this batch: let the table builder store the fp32 tables for it
     // (M KiB per query, 100 MB at M = 96 / batch 1024) instead of every query's workgroup re-deriving its table from the 786 KB codebook
     P.tab_expected = P.pq_fused_lut && P.rot && h->pq_final_tab != 0 && (h->pq_final_tab == 2 || P.KP >= 512 || h->dsub > 8) &&
@@ -121,7 +119,7 @@ static BatchPlan plan_batch(rsx_index* h, int64_t nq, const void* dq, int dtype,
     // re-derives inner-product entries from the codebook needs no second metric
     P.tab_expected = P.tab_expected || (P.fast && l2);
     // the matrix-core table build will serve this batch and the fast coarse quantiser runs: its first pass rides in the probe-pick launch
-    P.lut_pass0_early = P.coarse_fast && P.pq_fused_lut && !P.side_lut && h->dsub == 8 && h->lut_tiled >= 2 && h->metric == RSX_METRIC_INNER_PRODUCT &&
+    P.lut_pass0_early = P.coarse_fast && P.pq_fused_lut && h->dsub == 8 && h->lut_tiled != 0 && h->metric == RSX_METRIC_INNER_PRODUCT &&
                         h->pq_lut_early != 0;
     // sliced layout: eight queries per gather (two records per item) where lists are long and shared by several queries; a handful of
     // queries (about one per probed list) or short lists take the four-query single-pass scan (k_pq_scan_sl4).  pq_q8: 1 = choose,
@@ -277,11 +275,7 @@ static void check_supported(rsx_index* h, const BatchPlan& P) {
         RSX_THROW(RSX_ERR_UNSUPPORTED, "IndexPQ: %lld x %d bytes of codes are served by the staged scan and the exact scans of the rotated / sliced layouts only "
                   "(this search was routed elsewhere: M = %d, pq_layout, pq_fast / pq_filter / scan_kernel)", (long long)h->h_len[0], h->Mpad, h->M);
 }
-// Round 4 (overlap = 1, no longer the default): the 8-bit tables depend on the queries only — their build starts here on the side
-// stream and runs beside the coarse quantiser and the probe selection; the per-query parameters (k_pq_qparam: they need the coarse
-// scores) follow on the main stream once both have finished.  Round 6 measured the three cross-stream joins of a batch at ~12 us
-// each (profiles/r06_fixed_cost.md): the default is one stream, with the table build, the parameters and the pair grouping in two launches.
-// the table build's arguments; its two callers add what they differ in: probe_dis0 / nprobe, phase, mfma, pg
+// the table build's arguments; its caller adds probe_dis0 / nprobe, pass0_done, pg
 static PQLutArgs pq_lut_args(rsx_index* h, const BatchPlan& P, void* lut_ws) {
     PQLutArgs a{};
     a.lut32 = P.pq_fused_lut ? nullptr : h->w_lut.as<float>();
@@ -289,16 +283,6 @@ static PQLutArgs pq_lut_args(rsx_index* h, const BatchPlan& P, void* lut_ws) {
     a.lut8 = h->w_lut8.as<uint8_t>(); a.qparam = h->w_qparam.p; a.ws = lut_ws;
     a.transposed = P.sliced ? 2 : P.rot ? 1 : 0; a.metric = h->metric; a.lut32_out = lut32_out(h, P);
     return a;
-}
-static void fork_side_tables(rsx_index* h, const BatchPlan& P) {
-    ensure_side_stream(h);
-    h->w_lut8.ensure((size_t)P.nq * h->Mpad * 256); h->w_qparam.ensure((size_t)P.nq * 16); h->w_lutws.ensure(pq_lut8_tiled_ws(P.nq, h->Mpad));
-    HIPCHECK(hipEventRecord(h->ev_fork, h->st));
-    HIPCHECK(hipStreamWaitEvent(h->st2, h->ev_fork, 0));
-    PQLutArgs la = pq_lut_args(h, P, h->w_lutws.p);
-    la.phase = PQ_LUT_TABLES;
-    launch_pq_lut8(la, h->st2);
-    HIPCHECK(hipEventRecord(h->ev_lut, h->st2));
 }
 // the stored rows of a KIND_IVFSQ index, as the exact re-scores decode them
 static SqRows sq_rows(rsx_index* h) {
@@ -511,7 +495,6 @@ static void coarse_quantiser(rsx_index* h, const BatchPlan& P, const void* dq, i
         }
         launch_coarse_pick(cp, nq, h->st);
     } else { coarse_exact_scores(h, nq); tm.mark("coarse"); coarse_exact_probes(h, nq, nprobe, P.pad_to); }
-    if (P.side_lut) HIPCHECK(hipEventRecord(h->ev_probe, h->st));
     tm.mark("select_probe");
 }
 // profile >= 2: the vectors this batch scans
@@ -551,11 +534,9 @@ static void* rot_scan_ws(rsx_index* h, int k, int64_t items, int ngq, int& log_c
 }
 // the 8-bit tables + per-query parameters; pg: the (query, probe) pairs grouped by list in the same launch (matrix-core form only)
 static void build_pq_tables(rsx_index* h, const BatchPlan& P, void* lut_ws, const PairGroupArgs* pg, StageTimer& tm) {
-    if (P.side_lut) HIPCHECK(hipStreamWaitEvent(h->st, h->ev_lut, 0));     // the tables were built beside the probe selection
     PQLutArgs la = pq_lut_args(h, P, lut_ws);
     la.probe_dis0 = h->w_dis0.as<float>(); la.nprobe = P.nprobe;
-    la.phase = P.side_lut ? PQ_LUT_QPARAM : PQ_LUT_WHOLE;
-    la.mfma = (lut_ws && !P.side_lut && h->lut_tiled >= 2) ? (P.lut_pass0_early ? 2 : 1) : 0; la.pg = pg;
+    la.pass0_done = P.lut_pass0_early; la.pg = pg;
     launch_pq_lut8(la, h->st);
     tm.mark("lut8");
 }
@@ -638,7 +619,7 @@ static bool pq_prepass(rsx_index* h, const BatchPlan& P, BatchResult& R, const P
         h->w_excl.ensure((size_t)nq * 2);
         pa.cand = h->w_cand.as<uint64_t>(); pa.cand_cap = R.cand_cap; pa.tile_rows = g.tile_rows; pa.excl = h->w_excl.as<uint16_t>();
     }
-    const bool group_in_tables = !P.staged && lut_ws && !P.side_lut && h->lut_tiled >= 2 && h->pq_group_fused != 0 && pr.npairs <= PG_MAX_PAIRS &&
+    const bool group_in_tables = !P.staged && lut_ws && h->pq_group_fused != 0 && pr.npairs <= PG_MAX_PAIRS &&
                                  nlist <= PG_BLOCKS * PG_MAX_LPB;
     PairGroupArgs pg{};
     bool grouped = false;
@@ -651,12 +632,6 @@ static bool pq_prepass(rsx_index* h, const BatchPlan& P, BatchResult& R, const P
         grouped = true;
     }
     build_pq_tables(h, P, lut_ws, group_in_tables ? &pg : nullptr, tm);
-    if (P.side_lut && !P.staged) {       // the (list, tile, group) work items of the scan: built beside the pre-pass (they need the probes only)
-        HIPCHECK(hipStreamWaitEvent(h->st2, h->ev_probe, 0));
-        pr.group(4 * P.ngq, g.tile_rows, P.nprobe, 0, h->st2);
-        HIPCHECK(hipEventRecord(h->ev_group, h->st2));
-        grouped = true;
-    }
     // large k: the histogram form of the four-query pre-pass (any sample size, several lists; pq_prepass4 = 2 keeps k_pq_prepass)
     const bool pre4big = P.rot && !g.pre4 && h->pq_prepass4 == 1 && nq >= 64 && h->Mpad >= 32 && g.pre_rows <= 32768;
     if (g.pre4 && launch_pq_prepass4(pa, nq, h->st) == 0) {
@@ -715,9 +690,7 @@ static bool pq_filtered_scan(rsx_index* h, const BatchPlan& P, BatchResult& R, P
         // (a stage mark is an event record: ~5 us of stream time in profile mode — none for a stage that launched nothing)
         tm.mark("select0");
     }
-    if (grouped) { if (P.side_lut) HIPCHECK(hipStreamWaitEvent(h->st, h->ev_group, 0)); }
-    else pr.group(4 * P.ngq, g.tile_rows, nprobe, 0, h->st);
-    if (!(grouped && !P.side_lut)) tm.mark("group");
+    if (!grouped) { pr.group(4 * P.ngq, g.tile_rows, nprobe, 0, h->st); tm.mark("group"); }
     const int64_t mi = max_scan_items(h, nq, nprobe, 4 * P.ngq, g.tile_rows);
     int log_cap = 64;
     void* rws = P.rot ? rot_scan_ws(h, P.k, mi, P.ngq, log_cap) : nullptr;
@@ -1219,10 +1192,6 @@ static void search_batch(rsx_index* h, int64_t nq, const void* dq, int dtype, in
     convert_queries(h, P, dq, dtype, tm);
     if (P.tab_expected) h->w_lut.ensure((size_t)nq * h->Mpad * 256 * 4);      // (lut32_out)
     check_supported(h, P);
-    // whatever still throws behind the fork (an allocation) leaves through this guard: the side stream is drained before
-    // the caller can reuse or free the buffers its kernels read and write
-    struct SideJoin { rsx_index* h; bool armed = false; ~SideJoin() { if (armed && h->st2) (void)hipStreamSynchronize(h->st2); } } side_join{h};
-    if (P.side_lut) { fork_side_tables(h, P); side_join.armed = true; }
     FinalizeArgs fa = finalize_args(h, P, dD, dI);
     if (h->kind == KIND_FLAT) {
         flat_scan(h, P, fa, tm);
@@ -1241,7 +1210,6 @@ static void search_batch(rsx_index* h, int64_t nq, const void* dq, int dtype, in
     select_stage(h, P, R, tm);
     finalize_stage(h, P, R, fa, tm);
     tm.finish();
-    side_join.armed = false;      // st has waited on every side-stream event of this batch
     // (the re-run fills score rows: chunked by the budget; the fast coarse quantiser's flags are this batch's)
     if (P.fast || P.certify) rerun_uncertified(h, nq, dq, dtype, k, dD, dI, (size_t)P.tmax * 4, P.coarse_fast, pq_second_chance(h, P, R, fa));
 }

@@ -177,14 +177,7 @@ void launch_gemm_exact_scores(const void* X, int x_f16, int64_t n, int ldx, cons
         const int NQ = n == 1 ? 1 : n == 2 ? 2 : n <= 4 ? 4 : 8;
         const size_t shm = (size_t)(SS_ROWS * (d + 4) + NQ * d) * 4;
         auto kern = NQ == 1 ? k_scores_small<1> : NQ == 2 ? k_scores_small<2> : NQ == 4 ? k_scores_small<4> : k_scores_small<8>;
-        static DevSize big;
-        if (shm > 48 * 1024)
-            big.grow(shm, [&] {
-                (void)hipFuncSetAttribute((const void*)k_scores_small<1>, hipFuncAttributeMaxDynamicSharedMemorySize, 159 * 1024);
-                (void)hipFuncSetAttribute((const void*)k_scores_small<2>, hipFuncAttributeMaxDynamicSharedMemorySize, 159 * 1024);
-                (void)hipFuncSetAttribute((const void*)k_scores_small<4>, hipFuncAttributeMaxDynamicSharedMemorySize, 159 * 1024);
-                (void)hipFuncSetAttribute((const void*)k_scores_small<8>, hipFuncAttributeMaxDynamicSharedMemorySize, 159 * 1024);
-            });
+        lds_grant(kern, shm);
         hipLaunchKernelGGL(kern, dim3(g), dim3(256), shm, st, Xf, (int)n, ldx, C, nc, d, S, lds_);
         return;
     }
@@ -195,15 +188,13 @@ void launch_gemm_exact_scores(const void* X, int x_f16, int64_t n, int ldx, cons
     // workgroup fits a CU and the dispatcher has to spread a grid of ~#CUs workgroups over all CUs (profiles/r05_coarse_gemm.md)
     static const int spread_kib = measure_env("RSX_COARSE_SPREAD", 0);
     const size_t dyn = (size_t)spread_kib * 1024;
-    if (dyn > 0) {
-        static DevOnce once;
-        once.once([&] {
-            (void)hipFuncSetAttribute((const void*)k_gemm_exact<true, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)dyn);
-            (void)hipFuncSetAttribute((const void*)k_gemm_exact<false, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)dyn);
-        });
+    if (x_f16) {
+        lds_grant(k_gemm_exact<true, false>, dyn);
+        hipLaunchKernelGGL((k_gemm_exact<true, false>), grid, dim3(256), dyn, st, X, n, ldx, xv, C, nc, d, cv, S, lds_, (uint64_t*)nullptr, 0);
+    } else {
+        lds_grant(k_gemm_exact<false, false>, dyn);
+        hipLaunchKernelGGL((k_gemm_exact<false, false>), grid, dim3(256), dyn, st, X, n, ldx, xv, C, nc, d, cv, S, lds_, (uint64_t*)nullptr, 0);
     }
-    if (x_f16) hipLaunchKernelGGL((k_gemm_exact<true, false>), grid, dim3(256), dyn, st, X, n, ldx, xv, C, nc, d, cv, S, lds_, (uint64_t*)nullptr, 0);
-    else hipLaunchKernelGGL((k_gemm_exact<false, false>), grid, dim3(256), dyn, st, X, n, ldx, xv, C, nc, d, cv, S, lds_, (uint64_t*)nullptr, 0);
 }
 
 void launch_gemm_exact_argmax(const void* X, int x_f16, int64_t n, int ldx, const float* C, int nc, int d,
@@ -682,15 +673,6 @@ __global__ __launch_bounds__(512) void k_flat_gemm2(const __half* Q16, int nq_pa
 
 static const size_t FG2_SHM = 2 * FG2_STAGE + 2 * 256 * 8 + 2 * 256 * 4;
 static const size_t FG2_SHM_FILTER = FG2_SHM + 8 * FG2_QCAP * (8 + 2);
-template <bool FILTER>
-static bool fg2_ready() {
-    static DevOnce once;
-    static std::atomic<int> failed{0};
-    once.once([&] {
-        if (hipFuncSetAttribute((const void*)k_flat_gemm2<FILTER>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(FILTER ? FG2_SHM_FILTER : FG2_SHM)) != hipSuccess) failed = 1;
-    });
-    return !failed;
-}
 // the 256 x 256 LDS-DMA kernel needs fp16 storage, K a multiple of 64 and enough queries to fill its tile
 static bool fg2_applies(int nq_pad, int x_f16, int ld) {
     static const int off = measure_env("RSX_FLAT_GEMM_V1", 0);
@@ -717,7 +699,7 @@ void launch_flat_gemm(const __half* Q16, int nq_pad, const void* X, int x_f16, i
                       const float* bias, float* temp, int64_t tstride, hipStream_t st) {
     if (nv <= 0 || nq_pad <= 0) return;
     FlatFilterArgs F{};
-    if (fg2_applies(nq_pad, x_f16, ld) && fg2_ready<false>()) {
+    if (fg2_applies(nq_pad, x_f16, ld) && lds_grant(k_flat_gemm2<false>, FG2_SHM)) {
         dim3 g2((unsigned)(nq_pad / 256), (unsigned)((nv + 255) / 256));
         hipLaunchKernelGGL((k_flat_gemm2<false>), g2, dim3(512), FG2_SHM, st, Q16, nq_pad, (const __half*)X, v0, nv, ld, bias, temp, tstride, F);
         return;
@@ -734,7 +716,7 @@ void launch_flat_gemm_filter(const __half* Q16, int nq_pad, int nq, const void* 
     if (nv <= 0 || nq_pad <= 0) return;
     FlatFilterArgs F{};
     F.tau = tau; F.tau_stride = tau_stride; F.cand = cand; F.cand_cnt = cand_cnt; F.cand_cap = cand_cap;
-    if (fg2_applies(nq_pad, x_f16, ld) && fg2_ready<true>()) {
+    if (fg2_applies(nq_pad, x_f16, ld) && lds_grant(k_flat_gemm2<true>, FG2_SHM_FILTER)) {
         F.nq = nq; F.qt = nq_pad / 256; F.ntiles = (nv + 255) / 256;
         // persistent walking workgroups (see the kernel) once every slot has a few db tiles to walk; RSX_FG2_WALK=0: off (A/B)
         static const int walk_on = measure_env("RSX_FG2_WALK", 1);
@@ -1310,23 +1292,16 @@ void launch_list_scan(const ListScanArgs& a, hipStream_t st) {
 #ifdef RSX_MEASURE
             static const int d_env = measure_env("RSX_LS3_D", 0);
 #define LS3_VARIANT(DD) if (d_env == DD && a.ld == 768 && !a.bias) { \
-                (void)hipFuncSetAttribute((const void*)k_list_scan3<false, 12, false, DD>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); \
-                (void)hipFuncSetAttribute((const void*)k_list_scan3<true, 12, false, DD>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); \
                 const size_t shm = (size_t)DD * 16384 + 28 * 128 + 2 * 128 * 4; \
-                if (a.tau_key) hipLaunchKernelGGL((k_list_scan3<true, 12, false, DD>), grid, dim3(512), shm, st, a); \
-                else hipLaunchKernelGGL((k_list_scan3<false, 12, false, DD>), grid, dim3(512), shm, st, a); \
+                if (a.tau_key) { auto k = k_list_scan3<true, 12, false, DD>; lds_grant(k, shm); hipLaunchKernelGGL(k, grid, dim3(512), shm, st, a); } \
+                else { auto k = k_list_scan3<false, 12, false, DD>; lds_grant(k, shm); hipLaunchKernelGGL(k, grid, dim3(512), shm, st, a); } \
                 return; }
             LS3_VARIANT(3) LS3_VARIANT(6) LS3_VARIANT(8)
 #undef LS3_VARIANT
 #endif
 #define LS3_LAUNCH(KT_, B_) { \
-                static DevOnce once3; \
-                once3.once([&] { \
-                    (void)hipFuncSetAttribute((const void*)k_list_scan3<false, KT_, B_>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); \
-                    (void)hipFuncSetAttribute((const void*)k_list_scan3<true, KT_, B_>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); \
-                }); \
-                if (a.tau_key) hipLaunchKernelGGL((k_list_scan3<true, KT_, B_>), grid, dim3(512), shm3, st, a); \
-                else hipLaunchKernelGGL((k_list_scan3<false, KT_, B_>), grid, dim3(512), shm3, st, a); \
+                if (a.tau_key) { auto k = k_list_scan3<true, KT_, B_>; lds_grant(k, shm3); hipLaunchKernelGGL(k, grid, dim3(512), shm3, st, a); } \
+                else { auto k = k_list_scan3<false, KT_, B_>; lds_grant(k, shm3); hipLaunchKernelGGL(k, grid, dim3(512), shm3, st, a); } \
                 return; }
 #define LS3_BY_BIAS(KT_) { if (a.bias) LS3_LAUNCH(KT_, true) else LS3_LAUNCH(KT_, false) }
             switch (a.ld) {
@@ -1344,38 +1319,27 @@ void launch_list_scan(const ListScanArgs& a, hipStream_t st) {
         const bool wide = qt == 4 && a.chunk_rows == 2 * base_rows;        // 8 waves x 3 stages, 1024 rows per work item
         const int nw = wide ? 8 : 4, dd = wide ? 3 : LS2_D;
         size_t shm2 = (size_t)16 * qt * (a.ld + 8) * 2 + 28 * 16 * qt + (size_t)nw * dd * 2048;
-        static DevOnce once;
-        once.once([&] {
-            (void)hipFuncSetAttribute((const void*)k_list_scan2<false, 1, 4, LS2_D>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-            (void)hipFuncSetAttribute((const void*)k_list_scan2<true, 1, 4, LS2_D>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-            (void)hipFuncSetAttribute((const void*)k_list_scan2<false, 2, 4, LS2_D>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-            (void)hipFuncSetAttribute((const void*)k_list_scan2<true, 2, 4, LS2_D>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-            (void)hipFuncSetAttribute((const void*)k_list_scan2<false, 4, 4, LS2_D>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-            (void)hipFuncSetAttribute((const void*)k_list_scan2<true, 4, 4, LS2_D>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-            (void)hipFuncSetAttribute((const void*)k_list_scan2<false, 4, 8, 3>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-            (void)hipFuncSetAttribute((const void*)k_list_scan2<true, 4, 8, 3>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        });
         if (wide) {
-            if (a.tau_key) hipLaunchKernelGGL((k_list_scan2<true, 4, 8, 3>), grid, dim3(512), shm2, st, a);
-            else hipLaunchKernelGGL((k_list_scan2<false, 4, 8, 3>), grid, dim3(512), shm2, st, a);
+            if (a.tau_key) { auto k = k_list_scan2<true, 4, 8, 3>; lds_grant(k, shm2); hipLaunchKernelGGL(k, grid, dim3(512), shm2, st, a); }
+            else { auto k = k_list_scan2<false, 4, 8, 3>; lds_grant(k, shm2); hipLaunchKernelGGL(k, grid, dim3(512), shm2, st, a); }
         } else if (qt == 4) {
-            if (a.tau_key) hipLaunchKernelGGL((k_list_scan2<true, 4, 4, LS2_D>), grid, dim3(256), shm2, st, a);
-            else hipLaunchKernelGGL((k_list_scan2<false, 4, 4, LS2_D>), grid, dim3(256), shm2, st, a);
+            if (a.tau_key) { auto k = k_list_scan2<true, 4, 4, LS2_D>; lds_grant(k, shm2); hipLaunchKernelGGL(k, grid, dim3(256), shm2, st, a); }
+            else { auto k = k_list_scan2<false, 4, 4, LS2_D>; lds_grant(k, shm2); hipLaunchKernelGGL(k, grid, dim3(256), shm2, st, a); }
         } else if (qt == 2) {
-            if (a.tau_key) hipLaunchKernelGGL((k_list_scan2<true, 2, 4, LS2_D>), grid, dim3(256), shm2, st, a);
-            else hipLaunchKernelGGL((k_list_scan2<false, 2, 4, LS2_D>), grid, dim3(256), shm2, st, a);
+            if (a.tau_key) { auto k = k_list_scan2<true, 2, 4, LS2_D>; lds_grant(k, shm2); hipLaunchKernelGGL(k, grid, dim3(256), shm2, st, a); }
+            else { auto k = k_list_scan2<false, 2, 4, LS2_D>; lds_grant(k, shm2); hipLaunchKernelGGL(k, grid, dim3(256), shm2, st, a); }
         } else {
-            if (a.tau_key) hipLaunchKernelGGL((k_list_scan2<true, 1, 4, LS2_D>), grid, dim3(256), shm2, st, a);
-            else hipLaunchKernelGGL((k_list_scan2<false, 1, 4, LS2_D>), grid, dim3(256), shm2, st, a);
+            if (a.tau_key) { auto k = k_list_scan2<true, 1, 4, LS2_D>; lds_grant(k, shm2); hipLaunchKernelGGL(k, grid, dim3(256), shm2, st, a); }
+            else { auto k = k_list_scan2<false, 1, 4, LS2_D>; lds_grant(k, shm2); hipLaunchKernelGGL(k, grid, dim3(256), shm2, st, a); }
         }
         return;
     }
     size_t shm = (size_t)16 * (a.ld + 8) * 2 + 16 * sizeof(int64_t);
     if (a.x_f16) {
-        if (shm > 48 * 1024) hipFuncSetAttribute((const void*)k_list_scan<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm);
+        lds_grant(k_list_scan<true>, shm);
         hipLaunchKernelGGL(k_list_scan<true>, grid, dim3(256), shm, st, a);
     } else {
-        if (shm > 48 * 1024) hipFuncSetAttribute((const void*)k_list_scan<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm);
+        lds_grant(k_list_scan<false>, shm);
         hipLaunchKernelGGL(k_list_scan<false>, grid, dim3(256), shm, st, a);
     }
 }

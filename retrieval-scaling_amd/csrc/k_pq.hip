@@ -115,8 +115,7 @@ __global__ __launch_bounds__(1024) void k_pq_scan(PQScanArgs a) {
 
 template <int NCH>
 static int launch_pq_scan_t(const PQScanArgs& a, dim3 grid, size_t shm, hipStream_t st) {
-    if (hipFuncSetAttribute((const void*)k_pq_scan<NCH>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm) != hipSuccess)
-        return -1;
+    if (!lds_grant(k_pq_scan<NCH>, shm)) return -1;
     hipLaunchKernelGGL(k_pq_scan<NCH>, grid, dim3(1024), shm, st, a);
     return 0;
 }
@@ -249,8 +248,7 @@ template <int NCH, int VPL>
 static int launch_pq_scan2_t(const PQScan2Args& A, hipStream_t st) {
     constexpr int GPC = NCH < 3 ? NCH : 3;
     size_t shm = (size_t)GPC * 16 * 256 * sizeof(float2);
-    if (hipFuncSetAttribute((const void*)k_pq_scan2<NCH, VPL>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm) != hipSuccess)
-        return -1;
+    if (!lds_grant(k_pq_scan2<NCH, VPL>, shm)) return -1;
     dim3 grid((unsigned)((A.max_items + 7) & ~7));
     hipLaunchKernelGGL((k_pq_scan2<NCH, VPL>), grid, dim3(1024), shm, st, A);
     return 0;
@@ -445,7 +443,8 @@ __global__ __launch_bounds__(256) void k_pq_lut8f(const float* Q32, int ldq, con
     }
 }
 
-// Tiled form of the same table build for dsub = 8 (what k_pq_lut8f computes, bit for bit).  k_pq_lut8f reads the whole
+// Tiled form of the same table build for dsub = 8, METRIC_L2 (IndexPQ: the negated squared-distance entries k_pq_lut8f<8, true> computes,
+// bit for bit; inner product has the matrix-core form below).  k_pq_lut8f reads the whole
 // 786 KB codebook per query through one CU's L2 path (~47 GB/s): 4 rounds of ~30 us.  Here a workgroup takes the
 // codebook slice of LT_MB sub-quantisers (each wave two of them, 4 codewords per lane in registers) and streams
 // LT_QC queries past it, so the codebook is read LT_QC x less often; the global maximum range a query's quantisation
@@ -469,7 +468,7 @@ __device__ __forceinline__ float lut_coarsen(float u) {
 #ifndef LT_QC
 #define LT_QC 8      // queries per tile: 32 -> 8 quadruples the workgroups (1536 at batch 1024), measured 0.135 -> 0.100 ms for the build
 #endif
-template <int PASS, bool L2 = false>      // L2: the negated squared-distance entries of an L2 IndexPQ (see k_pq_lut8f)
+template <int PASS>
 __global__ __launch_bounds__(256) void k_pq_lut_tiled(const float* Q32, int ldq, const float* codebooks, int M, int Mpad,
                                                       int64_t nq, float* mnmx, float* errb, uint8_t* lut8, int transposed, float* lut32_out) {
     __shared__ float s_q[LT_QC * LT_MB * 8];     // the tile's query slices
@@ -527,15 +526,8 @@ __global__ __launch_bounds__(256) void k_pq_lut_tiled(const float* Q32, int ldq,
             float v[4];
 #pragma unroll
             for (int j = 0; j < 4; j++) {
-                float t = 0.0f;
-                if (L2) {
-                    const float q8[8] = {q0_, q1_, q2_, q3_, q4_, q5_, q6_, q7_}, cw8[8] = {cx[j].x, cx[j].y, cx[j].z, cx[j].w, cy[j].x, cy[j].y, cy[j].z, cy[j].w};
-                    t = -pq_l2_entry(q8, cw8, 8);
-                } else {
-                t = __fmaf_rn(q0_, cx[j].x, t); t = __fmaf_rn(q1_, cx[j].y, t); t = __fmaf_rn(q2_, cx[j].z, t); t = __fmaf_rn(q3_, cx[j].w, t);
-                t = __fmaf_rn(q4_, cy[j].x, t); t = __fmaf_rn(q5_, cy[j].y, t); t = __fmaf_rn(q6_, cy[j].z, t); t = __fmaf_rn(q7_, cy[j].w, t);
-                }
-                v[j] = t;
+                const float q8[8] = {q0_, q1_, q2_, q3_, q4_, q5_, q6_, q7_}, cw8[8] = {cx[j].x, cx[j].y, cx[j].z, cx[j].w, cy[j].x, cy[j].y, cy[j].z, cy[j].w};
+                v[j] = -pq_l2_entry(q8, cw8, 8);
             }
             if (PASS == 0) {
                 float mn = fminf(fminf(v[0], v[1]), fminf(v[2], v[3])), mx = fmaxf(fmaxf(v[0], v[1]), fmaxf(v[2], v[3]));
@@ -638,7 +630,7 @@ __global__ __launch_bounds__(64) void k_pq_qparam(int64_t nq, int M, int Mpad, c
 }
 
 // ---------------------------------------------------------------------------------------
-// The same tables on the matrix cores, in two launches instead of three (round 6; lut_tiled = 2).  The VALU form above costs 20 + 35 us
+// The same tables on the matrix cores, in two launches instead of three (round 6; lut_tiled non-zero).  The VALU form above costs 20 + 35 us
 // (+ 5 for the parameters) per 1024 queries for 0.4 GFLOP: 60-odd VALU instructions and 12 dependent ds_bpermute shuffles per (query,
 // sub-quantiser) and pass.  Here an entry is a column of a v_mfma_f32_32x32x2_f32 product — on gfx950 bit for bit the k-ordered fmaf
 // chain (k_gemm.hip), i.e. exactly the value the VALU form computes:
@@ -783,39 +775,30 @@ size_t pq_lut8_fused_lds(int M, int Mpad, int dsub) { return ((size_t)Mpad * 256
 
 void launch_pq_lut8(const PQLutArgs& a, hipStream_t st) {
     const float *lut32 = a.lut32, *Q32 = a.Q32, *codebooks = a.codebooks, *probe_dis0 = a.probe_dis0;
-    const int ldq = a.ldq, dsub = a.dsub, M = a.M, Mpad = a.Mpad, nprobe = a.nprobe, transposed = a.transposed, phase = a.phase, mfma = a.mfma;
+    const int ldq = a.ldq, dsub = a.dsub, M = a.M, Mpad = a.Mpad, nprobe = a.nprobe, transposed = a.transposed;
     const int64_t nq = a.nq;
     uint8_t* lut8 = a.lut8; PQQParam* qparam = (PQQParam*)a.qparam; float* lut32_out = a.lut32_out;
     if (nq <= 0) return;
-    // the tiled builds (codebook slices shared by 32 queries): their workspace, grid and output staging
+    const bool l2 = a.metric != 0;      // (rsx_metric, as FinalizeArgs::metric) a squared difference is no contraction, so never the matrix-core builder
+    // the tiled builds (codebook slices shared by several queries): their workspace
     const bool tiled = a.ws && dsub == 8;
     float* mnmx = reinterpret_cast<float*>(a.ws);
-    float* errb = tiled ? mnmx + (size_t)nq * Mpad * 2 : nullptr;
-    const int64_t nmb = (Mpad + LT_MB - 1) / LT_MB, nqt8 = (((nq + LT_QC - 1) / LT_QC) + 7) / 8;
-    const dim3 grid((unsigned)(nmb * nqt8 * 8));
-    const size_t osm = transposed ? (size_t)LT_QC * 256 * LT_MB : 0;
-    if (a.metric != 0) {      // L2 (rsx_metric, as FinalizeArgs::metric): a squared difference is no contraction, so never the matrix-core builder
-        if (tiled) {      // the VALU tiles (measured at M = 96, batch 1024: the per-query builder below takes 0.30 ms): two passes + the parameters
-            static DevOnce once_t;
-            if (osm) once_t.once([&] { hipFuncSetAttribute((const void*)k_pq_lut_tiled<1, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)osm); });
-            hipLaunchKernelGGL((k_pq_lut_tiled<0, true>), grid, dim3(256), 0, st, Q32, ldq, codebooks, M, Mpad, nq, mnmx, errb, lut8, transposed, (float*)nullptr);
-            hipLaunchKernelGGL((k_pq_lut_tiled<1, true>), grid, dim3(256), osm, st, Q32, ldq, codebooks, M, Mpad, nq, mnmx, errb, lut8, transposed, lut32_out);
-            hipLaunchKernelGGL(k_pq_qparam, dim3((unsigned)nq), dim3(64), 0, st, nq, M, Mpad, mnmx, errb, probe_dis0, nprobe, qparam);
-            return;
-        }
-        const size_t lds = pq_lut8_fused_lds(M, Mpad, dsub);
-        auto kern = dsub == 8 ? k_pq_lut8f<8, true> : k_pq_lut8f<0, true>;
-        static DevOnce once8, once0;
-        (dsub == 8 ? once8 : once0).once([&] { hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); });
-        hipLaunchKernelGGL(kern, dim3((unsigned)nq), dim3(256), lds, st, Q32, ldq, codebooks, dsub, M, Mpad, probe_dis0, nprobe, lut8, qparam, transposed, lut32_out);
-        return;
-    }
-    if (phase != PQ_LUT_WHOLE && !(tiled && !lut32)) return;     // only the tiled build splits into tables (1) + per-query parameters (2)
-    if (lut32) {
+    if (lut32 && !l2) {
         hipLaunchKernelGGL(k_pq_lut8, dim3((unsigned)nq), dim3(256), 0, st, lut32, M, Mpad, probe_dis0, nprobe, lut8, qparam, transposed);
         return;
     }
-    if (tiled) {
+    if (tiled && l2) {      // the VALU tiles (measured at M = 96, batch 1024: the per-query builder below takes 0.30 ms): two passes + the parameters
+        float* errb = mnmx + (size_t)nq * Mpad * 2;
+        const int64_t nmb = (Mpad + LT_MB - 1) / LT_MB, nqt8 = (((nq + LT_QC - 1) / LT_QC) + 7) / 8;
+        const dim3 grid((unsigned)(nmb * nqt8 * 8));
+        const size_t osm = transposed ? (size_t)LT_QC * 256 * LT_MB : 0;
+        hipLaunchKernelGGL(k_pq_lut_tiled<0>, grid, dim3(256), 0, st, Q32, ldq, codebooks, M, Mpad, nq, mnmx, errb, lut8, transposed, (float*)nullptr);
+        lds_grant(k_pq_lut_tiled<1>, osm);
+        hipLaunchKernelGGL(k_pq_lut_tiled<1>, grid, dim3(256), osm, st, Q32, ldq, codebooks, M, Mpad, nq, mnmx, errb, lut8, transposed, lut32_out);
+        hipLaunchKernelGGL(k_pq_qparam, dim3((unsigned)nq), dim3(64), 0, st, nq, M, Mpad, mnmx, errb, probe_dis0, nprobe, qparam);
+        return;
+    }
+    if (tiled) {      // matrix-core form: tables + per-query parameters in two launches
 #ifdef RSX_MEASURE
         static int lut_step = -1;
         if (lut_step < 0) {
@@ -825,34 +808,22 @@ void launch_pq_lut8(const PQLutArgs& a, hipStream_t st) {
             (void)hipMemcpyToSymbol(HIP_SYMBOL(g_lut_step), &lut_step, sizeof(int));
         }
 #endif
-        static DevOnce once;
-        if (osm) once.once([&] { hipFuncSetAttribute((const void*)k_pq_lut_tiled<1>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)osm); });
-        if (mfma && phase == PQ_LUT_WHOLE) {      // matrix-core form: tables + per-query parameters in two launches (needs the coarse scores: phase 0 only)
-            const int64_t nmb4 = (Mpad + LM_MB - 1) / LM_MB, nqt4 = (((nq + LM_Q - 1) / LM_Q) + 7) / 8;
-            const size_t osm4 = (size_t)LM_Q * 257 * 4;
-            const dim3 grid4((unsigned)(nmb4 * nqt4 * 8));
-            PairGroupArgs pg0{};
-            if (a.pg) pg0 = *a.pg;
-            PairGroupArgs pgn{};
-            if (mfma != 2)      // 2: pass 0 already ran as extra workgroups of the probe-pick launch (pq_lut_pass0_blocks)
-                hipLaunchKernelGGL(k_pq_lut_mfma<0>, grid4, dim3(256), 0, st, Q32, ldq, codebooks, M, Mpad, nq, mnmx, lut8, transposed,
-                                   lut32_out, probe_dis0, nprobe, (PQQParam*)nullptr, pgn);
-            hipLaunchKernelGGL(k_pq_lut_mfma<1>, dim3(grid4.x + (unsigned)pg0.nb), dim3(256), osm4, st, Q32, ldq, codebooks, M, Mpad, nq, mnmx, lut8, transposed,
-                               lut32_out, probe_dis0, nprobe, qparam, pg0);
-            return;
-        }
-        if (phase != PQ_LUT_QPARAM) {
-            hipLaunchKernelGGL(k_pq_lut_tiled<0>, grid, dim3(256), 0, st, Q32, ldq, codebooks, M, Mpad, nq, mnmx, errb, lut8, transposed, (float*)nullptr);
-            hipLaunchKernelGGL(k_pq_lut_tiled<1>, grid, dim3(256), osm, st, Q32, ldq, codebooks, M, Mpad, nq, mnmx, errb, lut8, transposed, lut32_out);
-        }
-        if (phase != PQ_LUT_TABLES)
-            hipLaunchKernelGGL(k_pq_qparam, dim3((unsigned)nq), dim3(64), 0, st, nq, M, Mpad, mnmx, errb, probe_dis0, nprobe, qparam);
+        const int64_t nmb4 = (Mpad + LM_MB - 1) / LM_MB, nqt4 = (((nq + LM_Q - 1) / LM_Q) + 7) / 8;
+        const size_t osm4 = (size_t)LM_Q * 257 * 4;
+        const dim3 grid4((unsigned)(nmb4 * nqt4 * 8));
+        PairGroupArgs pg0{};
+        if (a.pg) pg0 = *a.pg;
+        PairGroupArgs pgn{};
+        if (!a.pass0_done)      // (else pass 0 already ran as extra workgroups of the probe-pick launch, pq_lut_pass0_blocks)
+            hipLaunchKernelGGL(k_pq_lut_mfma<0>, grid4, dim3(256), 0, st, Q32, ldq, codebooks, M, Mpad, nq, mnmx, lut8, transposed,
+                               lut32_out, probe_dis0, nprobe, (PQQParam*)nullptr, pgn);
+        hipLaunchKernelGGL(k_pq_lut_mfma<1>, dim3(grid4.x + (unsigned)pg0.nb), dim3(256), osm4, st, Q32, ldq, codebooks, M, Mpad, nq, mnmx, lut8, transposed,
+                           lut32_out, probe_dis0, nprobe, qparam, pg0);
         return;
     }
     const size_t lds = pq_lut8_fused_lds(M, Mpad, dsub);
-    auto kern = dsub == 8 ? k_pq_lut8f<8> : k_pq_lut8f<0>;
-    static DevOnce once8, once0;
-    (dsub == 8 ? once8 : once0).once([&] { hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); });
+    auto kern = l2 ? (dsub == 8 ? k_pq_lut8f<8, true> : k_pq_lut8f<0, true>) : (dsub == 8 ? k_pq_lut8f<8> : k_pq_lut8f<0>);
+    lds_grant(kern, lds);
     hipLaunchKernelGGL(kern, dim3((unsigned)nq), dim3(256), lds, st, Q32, ldq, codebooks, dsub, M, Mpad, probe_dis0, nprobe, lut8, qparam, transposed, lut32_out);
 }
 
@@ -1050,8 +1021,7 @@ __global__ __launch_bounds__(1024) void k_pq_scan8(PQScan8Args A) {
 template <int NCH, int VPL, int VAR = 0, bool FILTER = false>
 static int launch_pq_scan8_t(const PQScan8Args& A, hipStream_t st) {
     size_t shm = (size_t)(NCH * 16 + 1) * 256 * 4 + 256;   // [256][Mpad+1] table + per-query output parameters
-    if (hipFuncSetAttribute((const void*)k_pq_scan8<NCH, VPL, VAR, FILTER>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm) != hipSuccess)
-        return -1;
+    if (!lds_grant(k_pq_scan8<NCH, VPL, VAR, FILTER>, shm)) return -1;
     dim3 grid((unsigned)((A.max_items + 7) & ~7));
     hipLaunchKernelGGL((k_pq_scan8<NCH, VPL, VAR, FILTER>), grid, dim3(1024), shm, st, A);
     return 0;
@@ -1171,14 +1141,14 @@ void launch_pq_encode(const void* x, int x_f16, int64_t n, int ldx, int d, int M
     size_t shm = (size_t)256 * dsub * sizeof(float);
 #define RSX_ENC(DS)                                                                                         \
     case DS:                                                                                                \
-        if (shm > 48 * 1024) hipFuncSetAttribute((const void*)k_pq_encode<DS>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm); \
+        lds_grant(k_pq_encode<DS>, shm);                                                                   \
         hipLaunchKernelGGL(k_pq_encode<DS>, grid, dim3(256), shm, st, x, x_f16, n, ldx, d, M, Mpad, CB, dsub, centroids, assign, \
                            codebooks, dest_row, codes, plain_out);                                          \
         break;
     switch (dsub) {
         RSX_ENC(2) RSX_ENC(4) RSX_ENC(8) RSX_ENC(12) RSX_ENC(16) RSX_ENC(24) RSX_ENC(32) RSX_ENC(48) RSX_ENC(64)
         default:
-            if (shm > 48 * 1024) hipFuncSetAttribute((const void*)k_pq_encode<0>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm);
+            lds_grant(k_pq_encode<0>, shm);
             hipLaunchKernelGGL(k_pq_encode<0>, grid, dim3(256), shm, st, x, x_f16, n, ldx, d, M, Mpad, CB, dsub, centroids,
                                assign, codebooks, dest_row, codes, plain_out);
     }

@@ -1608,18 +1608,12 @@ int pq_scan_rot_max_wgs(int M) {
     return (ncu + 7) & ~7;
 }
 
-// The one host launcher of the work-item scans: Kernel = a scan kernel instantiation (the static DevOnce below is therefore one
-// per instantiation), M / FILTER pick its k_pq_rot_items, G = records per work item (A.max_items counts WORK ITEMS, the workspace
+// The one host launcher of the work-item scans: Kernel = a scan kernel instantiation, M / FILTER pick its k_pq_rot_items, G = records per work item (A.max_items counts WORK ITEMS, the workspace
 // holds G records each).  shm = the kernel's dynamic LDS; tail = its arguments behind (A, items, log_keys, seg_desc, xcd_ctr
 // [, prog — PROG: the kernel reads the sibling-progress words]).
 template <auto Kernel, int M, int G, bool FILTER, bool PROG = false, typename... Tail>
 static int launch_item_scan(const PQScan8Args& A, size_t shm, void* desc_ws, int log_cap, hipStream_t st, Tail... tail) {
-    static DevOnce once;
-    static std::atomic<int> failed{0};
-    once.once([&] {
-        if (hipFuncSetAttribute((const void*)Kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm) != hipSuccess) failed = 1;
-    });
-    if (failed) return -1;
+    if (!lds_grant(Kernel, shm)) return -1;      // (before the item records: a refused scan launches nothing)
     const int nwg = pq_scan_rot_max_wgs(M);
     const int64_t recs = (int64_t)A.max_items * G;
     PQRotItem* items = reinterpret_cast<PQRotItem*>(desc_ws);
@@ -2145,8 +2139,7 @@ __global__ __launch_bounds__(1024) void k_pq_prepass4(PQPrepassArgs a, int64_t n
 template <int NF, int NH, int SL = 0>
 static void launch_pq_prepass4_t(const PQPrepassArgs& a, int64_t nq, hipStream_t st) {
     const size_t shm = (size_t)(SL ? (SL + 1) / 2 : NF + NH) * 65536 + (size_t)4 * a.pre_rows * 2 + (1024 + 32) * 4 + 64;
-    static DevSize attr;
-    attr.grow(shm, [&] { (void)hipFuncSetAttribute((const void*)k_pq_prepass4<NF, NH, false, SL>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm); });
+    lds_grant(k_pq_prepass4<NF, NH, false, SL>, shm);
     hipLaunchKernelGGL((k_pq_prepass4<NF, NH, false, SL>), dim3((unsigned)((nq + 3) / 4)), dim3(1024), shm, st, a, nq);
 }
 template <int NF, int NH, int SL = 0>
@@ -2154,8 +2147,7 @@ static void launch_pq_prepass4_big_t(const PQPrepassArgs& a, int64_t nq, hipStre
     constexpr int M = SL ? 32 * SL : 64 * NF + 32 * NH;
     constexpr int NBW = ((((255 * M + 1) >> (M > 96 ? 4 : 3)) + 1) + 1) / 2;
     const size_t shm = (size_t)(SL ? (SL + 1) / 2 : NF + NH) * 65536 + (size_t)(4 * NBW + 32 + 4 * PP4_MAXSEG * 4 + 4) * 4 + 64;
-    static DevOnce once;
-    once.once([&] { (void)hipFuncSetAttribute((const void*)k_pq_prepass4<NF, NH, true, SL>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm); });
+    lds_grant(k_pq_prepass4<NF, NH, true, SL>, shm);
     hipLaunchKernelGGL((k_pq_prepass4<NF, NH, true, SL>), dim3((unsigned)((nq + 3) / 4)), dim3(1024), shm, st, a, nq);
 }
 // the BIG form (histogram of the sums, samples of any size over several lists): 0 on launch, -1 when it does not apply
@@ -2286,10 +2278,7 @@ int launch_pq_scan_l2(const PQScanArgs& a, const float* Q32, int ldq, const floa
     if (pairs <= 0 || a.max_chunks <= 0) return 0;
     const size_t shm = (size_t)a.Mpad * 1024 + (size_t)d * 4;
     if (shm > (size_t)160 * 1024) return -1;
-    static DevSize attr;
-    bool attr_ok = true;
-    attr.grow(shm, [&] { attr_ok = hipFuncSetAttribute((const void*)k_pq_scan_l2, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm) == hipSuccess; });
-    if (!attr_ok) return -1;
+    if (!lds_grant(k_pq_scan_l2, shm)) return -1;
     hipLaunchKernelGGL(k_pq_scan_l2, dim3((unsigned)pairs, (unsigned)a.max_chunks), dim3(1024), shm, st, a, Q32, ldq, centroids, codebooks, d, dsub);
     return 0;
 }
@@ -2299,11 +2288,7 @@ int launch_pq_scan_rot_exact(const PQScanArgs& a, hipStream_t st) {
     if (pairs <= 0 || a.max_chunks <= 0) return 0;
     if (!pq_rot_family(a.CB) || !pq_rot_applies(a.M)) return -1;
     const size_t shm = (size_t)a.Mpad * 1024;
-    static DevSize attr;
-    bool attr_ok = true;
-    attr.grow(shm, [&] { attr_ok = hipFuncSetAttribute((const void*)k_pq_scan_rot_exact, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm) == hipSuccess; });
-    if (!attr_ok)
-        return -1;
+    if (!lds_grant(k_pq_scan_rot_exact, shm)) return -1;
     hipLaunchKernelGGL(k_pq_scan_rot_exact, dim3((unsigned)pairs, (unsigned)a.max_chunks), dim3(1024), shm, st, a);
     return 0;
 }

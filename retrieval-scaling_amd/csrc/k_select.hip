@@ -464,8 +464,7 @@ bool pq_gather_select_applies(int nprobe, int tmax, int KP) {
 void launch_pq_gather_select(const PQGatherArgs& a, int64_t nq, hipStream_t st) {
     if (nq <= 0) return;
     const size_t shm = gather_select_lds(a.nprobe, a.tmax, a.KP);
-    static DevSize attr;
-    attr.grow(shm, [&] { (void)hipFuncSetAttribute((const void*)k_pq_gather_select, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm); });
+    lds_grant(k_pq_gather_select, shm);
     hipLaunchKernelGGL(k_pq_gather_select, dim3((unsigned)nq), dim3(256), shm, st, a);
 }
 
@@ -606,8 +605,7 @@ __global__ __launch_bounds__(256) void k_pq_stage_gather(PQStageArgs a) {
 void launch_pq_stage_gather(const PQStageArgs& a, int64_t nq, hipStream_t st) {
     if (nq <= 0) return;
     const size_t shm = 16 + (256 + 8 + 8) * 4 + (size_t)a.ntiles * 16 * 8 + 64;
-    static DevSize attr;
-    attr.grow(shm, [&] { (void)hipFuncSetAttribute((const void*)k_pq_stage_gather, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm); });
+    lds_grant(k_pq_stage_gather, shm);
     hipLaunchKernelGGL(k_pq_stage_gather, dim3((unsigned)nq), dim3(256), shm, st, a);
 }
 
@@ -873,8 +871,7 @@ __global__ __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(8, 8))) vo
 void launch_pq_prepass(const PQPrepassArgs& a, int64_t nq, hipStream_t st) {
     if (nq <= 0) return;
     size_t shm = 16 + 264 * 4 + (size_t)a.Mpad * 256 + (size_t)a.pre_rows * 2 + (4 * PP_MAXSEG + 4) * 4 + 64;
-    static DevSize attr;
-    attr.grow(shm, [&] { hipFuncSetAttribute((const void*)k_pq_prepass, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm); });
+    lds_grant(k_pq_prepass, shm);
     hipLaunchKernelGGL(k_pq_prepass, dim3((unsigned)nq), dim3(1024), shm, st, a);
 }
 
@@ -896,10 +893,10 @@ void launch_select(const SelectArgs& a, hipStream_t st) {
     if (select_radix_applies(a)) {
         size_t shm2 = (size_t)a.KP * 8 + 264 * 4;
         if (a.in_is_keys) {
-            if (shm2 > 48 * 1024) hipFuncSetAttribute((const void*)k_select_radix<1>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm2);
+            lds_grant(k_select_radix<1>, shm2);
             hipLaunchKernelGGL(k_select_radix<1>, dim3((unsigned)a.nrows), dim3(256), shm2, st, a);
         } else {
-            if (shm2 > 48 * 1024) hipFuncSetAttribute((const void*)k_select_radix<0>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm2);
+            lds_grant(k_select_radix<0>, shm2);
             hipLaunchKernelGGL(k_select_radix<0>, dim3((unsigned)a.nrows), dim3(256), shm2, st, a);
         }
         return;
@@ -907,10 +904,10 @@ void launch_select(const SelectArgs& a, hipStream_t st) {
     dim3 grid((unsigned)a.nrows, (unsigned)(a.nseg - a.seg_base));
     size_t shm = (size_t)a.BUF * sizeof(uint64_t);
     if (a.in_is_keys) {
-        if (shm > 48 * 1024) hipFuncSetAttribute((const void*)k_select<1>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm);
+        lds_grant(k_select<1>, shm);
         hipLaunchKernelGGL(k_select<1>, grid, dim3(64), shm, st, a);
     } else {
-        if (shm > 48 * 1024) hipFuncSetAttribute((const void*)k_select<0>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm);
+        lds_grant(k_select<0>, shm);
         hipLaunchKernelGGL(k_select<0>, grid, dim3(64), shm, st, a);
     }
 }
@@ -1155,9 +1152,8 @@ void launch_coarse_pick(const CoarsePickArgs& a0, int64_t nq, hipStream_t st) {
     const int ki = a.nlist <= 1024 ? 0 : a.nlist <= 4096 ? 1 : 2, li = a.cmax_rt <= 48 ? 0 : 1;
     void (*const kerns[3][2])(CoarsePickArgs) = {{k_coarse_pick<4, 6>, k_coarse_pick<4, 8>}, {k_coarse_pick<16, 6>, k_coarse_pick<16, 8>}, {k_coarse_pick<64, 6>, k_coarse_pick<64, 8>}};
     auto kern = kerns[ki][li];
-    static DevSize attr[6];
-    attr[2 * ki + li].grow(shm, [&] { hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm); });
     a.nq = nq;
+    lds_grant(kern, shm);
     hipLaunchKernelGGL(kern, dim3((unsigned)(nq + a.lp0.nblocks)), dim3(256), shm, st, a);
 }
 
@@ -1335,7 +1331,7 @@ void launch_group_pairs(const PairGroupArgs& g, int32_t* cnt, int32_t* cursor, i
     const int nlist = g.nlist; const int64_t npairs = g.npairs;
     if (nlist <= GP1_MAX_LISTS && npairs <= 8192) {   // larger batches: the multi-launch form is parallel and faster (32 k pairs: 45 vs 65 us)
         size_t shm = ((size_t)nlist + 64) * 4;
-        if (shm > 48 * 1024) hipFuncSetAttribute((const void*)k_group_pairs_1wg, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm);
+        lds_grant(k_group_pairs_1wg, shm);
         hipLaunchKernelGGL(k_group_pairs_1wg, dim3(1), dim3(1024), shm, st, g.probe_list, g.npairs, nlist, g.G, g.pair_off,
                            g.group_off, g.total_groups, g.pairs_sorted, g.list_len, g.tile_rows, g.item_off, g.total_items, nprobe, 0, jmax,
                            g.tile_cap);
@@ -2339,21 +2335,9 @@ void launch_pq_final_tab(const FinalizeArgs& a, uint64_t* cand, int cand_cap, ui
         if (room > 4096) room = 4096;
         if (room >= 512) { wq_off = (int)off; wq_cap = (int)room; shm = off + room * 8 + 16; }
     }
-    static DevSize attr;
     auto kern = a.M == 16 ? k_pq_final_tab<1> : a.M == 32 ? k_pq_final_tab<2> : a.M == 64 ? k_pq_final_tab<4> : a.M == 96 ? k_pq_final_tab<6> : k_pq_final_tab<8>;
     if (a.metric != 0) kern = a.M == 16 ? k_pq_final_tab<1, true> : a.M == 32 ? k_pq_final_tab<2, true> : a.M == 64 ? k_pq_final_tab<4, true> : a.M == 96 ? k_pq_final_tab<6, true> : k_pq_final_tab<8, true>;
-    attr.grow(shm, [&] {
-        (void)hipFuncSetAttribute((const void*)k_pq_final_tab<1>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        (void)hipFuncSetAttribute((const void*)k_pq_final_tab<2>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        (void)hipFuncSetAttribute((const void*)k_pq_final_tab<4>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        (void)hipFuncSetAttribute((const void*)k_pq_final_tab<6>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        (void)hipFuncSetAttribute((const void*)k_pq_final_tab<8>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        (void)hipFuncSetAttribute((const void*)k_pq_final_tab<1, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        (void)hipFuncSetAttribute((const void*)k_pq_final_tab<2, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        (void)hipFuncSetAttribute((const void*)k_pq_final_tab<4, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        (void)hipFuncSetAttribute((const void*)k_pq_final_tab<6, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        (void)hipFuncSetAttribute((const void*)k_pq_final_tab<8, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    });
+    lds_grant(kern, shm);
     hipLaunchKernelGGL(kern, dim3((unsigned)a.nq), dim3(1024), shm, st, a, cand, cand_cap, P, tie_ws, stage_probes, bm_off, wq_off, wq_cap);
 }
 
@@ -2377,14 +2361,12 @@ void launch_finalize(const FinalizeArgs& a0, hipStream_t st) {
         a.probe_lds_off = (int)((shm + 15) / 16 * 16);       // (not at K' = 8192, k > 3855 exact: the entries alone fill the 160 KiB)
         shm = probe_end;
     }
-    static DevSize big;
     if (a.kind == KIND_IVFSQ) {
-        static DevSize big_sq;
-        if (shm > 48 * 1024) big_sq.grow(shm, [&] { hipFuncSetAttribute((const void*)k_finalize<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm); });
+        lds_grant(k_finalize<true>, shm);
         hipLaunchKernelGGL(k_finalize<true>, dim3((unsigned)a.nq), dim3(64 * waves), shm, st, a);
         return;
     }
-    if (shm > 48 * 1024) big.grow(shm, [&] { hipFuncSetAttribute((const void*)k_finalize<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm); });
+    lds_grant(k_finalize<false>, shm);
     hipLaunchKernelGGL(k_finalize<false>, dim3((unsigned)a.nq), dim3(64 * waves), shm, st, a);
 }
 
@@ -2438,7 +2420,7 @@ static void launch_merge_strided(int nshards, int64_t nq, int k, int metric, con
     int NP = 64;
     while (NP < nshards * k) NP <<= 1;
     size_t shm = (size_t)NP * 8;
-    if (shm > 48 * 1024) hipFuncSetAttribute((const void*)k_merge_topk, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm);
+    lds_grant(k_merge_topk, shm);
     hipLaunchKernelGGL(k_merge_topk, dim3((unsigned)nq), dim3(64), shm, st, nshards, nq, k, metric, D, d_sstride, d_estride, I,
                        i_sstride, Do, Io, NP);
 }
@@ -2551,7 +2533,7 @@ void launch_merge_topk_byid(int nshards, int64_t nq, int k, int metric, const fl
     int NP = 64;
     while (NP < nshards * k) NP <<= 1;
     const size_t shm = (size_t)NP * 12;
-    if (shm > 48 * 1024) hipFuncSetAttribute((const void*)k_merge_topk_byid, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm);
+    lds_grant(k_merge_topk_byid, shm);
     hipLaunchKernelGGL(k_merge_topk_byid, dim3((unsigned)nq), dim3(256), shm, st, nshards, nq, k, metric, D, I, Do, Io, NP);
 }
 

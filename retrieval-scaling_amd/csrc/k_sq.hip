@@ -368,8 +368,7 @@ template <bool FILTER, int QT, int NW>
 static void sq_launch(const ListScanArgs& a, dim3 grid, hipStream_t st) {
     const int kc = sq_kc(QT, a.ld);
     const size_t shm = (size_t)2 * 16 * QT * (kc + 8) * 2 + (size_t)16 * QT * (8 + 8 + 8 + 4 + 4 + 4);
-    static DevOnce once;
-    once.once([&] { (void)hipFuncSetAttribute((const void*)k_sq_list_scan<FILTER, QT, NW>, hipFuncAttributeMaxDynamicSharedMemorySize, 80 * 1024); });
+    lds_grant(k_sq_list_scan<FILTER, QT, NW>, shm);
     hipLaunchKernelGGL((k_sq_list_scan<FILTER, QT, NW>), grid, dim3(64 * NW), shm, st, a, kc);
 }
 void launch_sq_list_scan(const ListScanArgs& a, hipStream_t st) {

@@ -200,16 +200,6 @@ struct rsx_index {
     bool trained = false;
     int64_t ntotal = 0;
     hipStream_t st = nullptr;
-    // side stream of a search batch (round 4): stages that do not depend on each other run beside the main chain — the table build
-    // beside the coarse quantiser + probe selection, the pair grouping beside the threshold pre-pass
-    hipStream_t st2 = nullptr;
-    hipEvent_t ev_fork = nullptr, ev_probe = nullptr, ev_lut = nullptr, ev_group = nullptr;
-    int overlap = 0;          // 1 = IVF-PQ table build and pair grouping on a side stream beside the coarse quantiser / the pre-pass (rounds 4-5; round 6:
-                              // three cross-stream joins of ~12 us each cost what the overlap buys — one stream, fewer and fused launches instead)
-    ~rsx_index() {
-        if (st2) { (void)hipSetDevice(device); (void)hipStreamDestroy(st2); }
-        for (hipEvent_t e : {ev_fork, ev_probe, ev_lut, ev_group}) if (e) (void)hipEventDestroy(e);
-    }
     PinBuf pin_q, pin_out, pin_flags;     // latency path: pinned staging of queries / results / certificate flags
 
     // trained parameters
@@ -254,8 +244,8 @@ struct rsx_index {
     int pq_lut_early = 1;     // pass 0 of the matrix-core table build as extra workgroups of the probe-pick launch (0 = its own launch)
     int pq_group_fused = 1;   // the (query, probe) pairs grouped by list by extra workgroups of the table launch (0 = its own four launches)
     uint32_t pg_epoch = 0;    // ... whose hand-over words carry this launch counter
-    int lut_tiled = 2;    // fast scan tables (dsub 8): tiled build sharing codebook slices across queries: 2 = one launch (k_pq_lut_once), 1 = two passes
-                          // + parameters in three launches, 0 = one workgroup per query
+    int lut_tiled = 2;    // fast scan tables (dsub 8): non-zero = tiled build sharing codebook slices across queries (inner product: on the matrix cores,
+                          // k_pq_lut_mfma, two launches; L2: VALU tiles, k_pq_lut_tiled + k_pq_qparam), 0 = one workgroup per query
     int pq_prepass_fused = 1;   // filtered fast scan: threshold pre-pass in one launch (0 = grouping + scan + selection)
     int ivf_qtiles = 1;      // IVF-Flat LDS-DMA scans: 1 = choose 16 / 64 / 128 probing queries per group from the queries per list, 2 / 4 / 8 = force 32 / 64 / 128, 0 = always 16
     int pq_prepass4 = 1;     // rotated fast scan, full batches: threshold pre-pass with four queries per workgroup on the scan's table format (1 = small and large k, 2 = small k only, 0 = never)
@@ -365,7 +355,6 @@ static inline void rd(FILE* f, void* p, size_t n) {
 // host functions that cross files (definitions: see the file list above)
 // ---------------------------------------------------------------------------------------
 void use_device(rsx_index* h);
-void ensure_side_stream(rsx_index* h);
 void refuse_while_two_call(const rsx_index* h, const char* what);
 int64_t workspace_bytes(const rsx_index* h);
 void upload_dir(rsx_index* h);

@@ -6,7 +6,9 @@
 #include <stdint.h>
 
 #include <atomic>
+#include <map>
 #include <mutex>
+#include <utility>
 
 namespace rsx {
 
@@ -51,13 +53,12 @@ inline int measure_env(const char* name, int dflt) { const char* e = getenv(name
 constexpr int measure_env(const char*, int dflt) { return dflt; }
 #endif
 
-// hipFuncSetAttribute (dynamic LDS above 64 KiB) is a per-DEVICE property of a kernel: with several GPUs driven from one
-// process (rsx_sharded_create) every device needs its own call.  first() is true once per device; need(bytes) is true when
-// this device has not yet been granted that many bytes.
 inline int cur_device() { int d = 0; (void)hipGetDevice(&d); return d & 63; }
-// Both are used from the host threads of a sharded handle concurrently: the check, the attribute call and the update happen
-// under one process-wide mutex, so no thread can launch a kernel between another thread's "first" and its attribute call.
+// The per-device state below (DevOnce::once, lds_grant) is used from the host threads of a sharded handle concurrently: this one
+// process-wide mutex serialises both — the check, f() or the attribute call, and the update happen under it, so no thread can launch a
+// kernel between another thread's check and its attribute call.
 inline std::mutex& attr_mutex() { static std::mutex m; return m; }
+// Per-device set-up of a launcher: once(f) runs f once per device (pq_scan_rot_max_wgs: the CU count).
 struct DevOnce {
     uint64_t m = 0;
     template <typename F> void once(F&& f) {          // f(): the per-device set-up; runs once per device
@@ -68,16 +69,21 @@ struct DevOnce {
         m |= b;
     }
 };
-struct DevSize {
-    size_t v[64] = {};
-    template <typename F> void grow(size_t bytes, F&& f) {   // f(): grant this device `bytes`; runs when it has fewer
-        std::lock_guard<std::mutex> g(attr_mutex());
-        size_t& s = v[cur_device()];
-        if (bytes <= s) return;
-        f();
-        s = bytes;
-    }
-};
+// THE grant of dynamic LDS: a launch that asks for more than 48 KiB needs the kernel's limit raised first, and the limit is a per-DEVICE
+// property of a kernel (several GPUs driven from one process, rsx_sharded_create: every device needs its own call).  Every launcher
+// calls this with the kernel it is about to launch and the bytes it is about to pass; the runtime is asked only when that exceeds
+// what this (kernel, device) was granted before.  False when the runtime refuses (the launch would fail).
+inline bool lds_grant(const void* kernel, size_t bytes) {
+    if (bytes <= 48 * 1024) return true;
+    static std::map<std::pair<const void*, int>, size_t> granted;
+    std::lock_guard<std::mutex> g(attr_mutex());
+    size_t& have = granted[{kernel, cur_device()}];
+    if (bytes <= have) return true;
+    if (hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes) != hipSuccess) return false;
+    have = bytes;
+    return true;
+}
+template <typename... A> inline bool lds_grant(void (*kernel)(A...), size_t bytes) { return lds_grant(reinterpret_cast<const void*>(kernel), bytes); }
 
 // Per-query candidate counters are atomically bumped from every CU: one counter per 128-byte line (8 B used), so that
 // the device-scope atomics of different queries never serialise on a shared line (measured: ~0.7 ms of a 3.8 ms scan).
@@ -317,7 +323,6 @@ int launch_pq_scan2(const PQScan2Args& A, int vpl, hipStream_t st);   // returns
 // 8-bit table fast scan (4 queries per LDS read) — approximate scores, certified by k_finalize
 struct PairGroupArgs;
 size_t pq_lut8_fused_lds(int M, int Mpad, int dsub);
-enum { PQ_LUT_WHOLE = 0, PQ_LUT_TABLES = 1, PQ_LUT_QPARAM = 2 };     // PQLutArgs::phase
 struct PQLutArgs {
     const float* lut32;        // null -> fused form: the fp32 table is built in LDS from Q32 [nq, ldq] and the codebooks (needs
                                // pq_lut8_fused_lds(M, Mpad, dsub) <= 160 KiB); otherwise quantises the given fp32 tables
@@ -328,16 +333,15 @@ struct PQLutArgs {
     void* ws;                  // pq_lut8_tiled_ws(nq, Mpad) bytes -> tiled build (dsub 8), or null
     int transposed;            // pq_lut8_index: 0: lut8 [nq][Mpad][256]; 1: [nq][256][Mpad] (rotated-layout scans); 2: [nq][Mpad/32][256][32] (sliced)
     int metric;                // rsx_metric; 1 = L2 (IndexPQ only: Q32 is the residual to a zero centroid): negated squared-distance tables by the
-                               // VALU builders only (tiled when ws is given and dsub = 8, else per query), whatever phase / mfma say
-    int phase;                 // tiled build only: PQ_LUT_TABLES = the tables (independent of the probe selection), PQ_LUT_QPARAM = the per-query parameters
+                               // VALU builders only (tiled when ws is given and dsub = 8, else per query), never the matrix cores
     float* lut32_out;          // fused forms only: also store the fp32 tables [nq][Mpad][256] (k_pq_final_tab reads them)
-    int mfma;                  // tiled build, phase 0: the matrix-core form (k_pq_lut_mfma: tables and per-query parameters in two launches; 2: its
-                               // first pass already ran in the probe-pick launch)
+    bool pass0_done;           // tiled inner-product build (k_pq_lut_mfma: tables and per-query parameters in two launches): its first pass already
+                               // ran in the probe-pick launch
     const PairGroupArgs* pg;   // matrix-core form: also group the (query, probe) pairs by list (extra workgroups)
 };
 void launch_pq_lut8(const PQLutArgs& a, hipStream_t st);
 size_t pq_lut8_tiled_ws(int64_t nq, int Mpad);
-int pq_lut_pass0_blocks(int64_t nq, int Mpad);      // workgroups of pass 0 of the matrix-core form (mfma = 2: they already ran elsewhere)
+int pq_lut_pass0_blocks(int64_t nq, int Mpad);      // workgroups of pass 0 of the matrix-core form (PQLutArgs::pass0_done: they already ran elsewhere)
 // shared by the list-major IVF-PQ scans (k_pq.hip, k_pq_rot.hip)
 struct PQQParam { float scale, bias, eps, pad; };   // pad: the largest integer table sum this query's u8 table can produce
 struct PQScan8Args {

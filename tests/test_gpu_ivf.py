@@ -143,7 +143,9 @@ def test_golden_ivfpq(gpu, orc, name, layout):
     ix.set_param("lut_tiled", 0)            # one workgroup per query builds its table (the tiled build is the dsub = 8 default)
     D9, I9 = ix.search(q, g["k"])
     assert_same_results(D9, I9, g["D"], g["I"], name + " per-query table build")
-    ix.set_param("lut_tiled", 1)
+    ix.set_param("lut_tiled", 2)
+    with pytest.raises(RuntimeError, match="unknown parameter 'overlap'"):        # the side-stream form is gone, and so is its knob
+        ix.set_param("overlap", 0)
 
 
 @pytest.mark.parametrize("d,M,nlist", [(96, 12, 8), (64, 8, 4), (768, 16, 16), (128, 64, 8), (64, 16, 7), (320, 160, 4),
@@ -175,6 +177,27 @@ def test_ivfpq_shapes_vs_oracle(gpu, orc, d, M, nlist):
         D, I = ix.search(q, k)
         Dr, Ir = orc.ivfpq_search(cen, cb, lm, q32, nprobe, k)
         assert_same_results(D, I, Dr, Ir, f"d={d} M={M} nprobe={nprobe}")
+
+
+@pytest.mark.parametrize("M", [16, 32])
+def test_ivfpq_k_grows_and_shrinks_on_one_handle(gpu, orc, M):
+    """k = 10, then 1000, then 10 again on ONE handle in one process: the selection, gather and finalize kernels' dynamic LDS grows past
+    48 KiB with K' and shrinks again after the larger size was granted; every search returns the oracle's ids and scores."""
+    d, n, nlist, nprobe, nq = 64, 20000, 32, 8, 64
+    x = orc.synth_vectors(d, nlist, 81, 82, 0.5, 0, n)
+    q = orc.synth_queries(d, nlist, 81, 82, 0.5, n, 83, 0.1, 0, nq)
+    x32, q32 = x.astype(np.float32), q.astype(np.float32)
+    cen = orc.kmeans(0, x32, nlist, 4, 1234)
+    a, _ = orc.assign_ip(cen, x32)
+    cb = orc.pq_train(orc.residuals(cen, x32, a)[:4000], M, 3, 1234)
+    lm = orc.ListMajor(a, np.arange(n), orc.pq_encode(cb, orc.residuals(cen, x32, a)), nlist)
+    ix = gpu.IndexIVFPQ(None, d, nlist, M, 8, 0)
+    ix.set_centroids(cen); ix.set_codebooks(cb); ix.add(x)
+    ix.nprobe = nprobe
+    ref = {k: orc.ivfpq_search(cen, cb, lm, q32, nprobe, k) for k in (10, 1000)}
+    for step, k in enumerate((10, 1000, 10)):
+        D, I = ix.search(q, k)
+        assert_same_results(D, I, *ref[k], f"M={M} search {step}: k={k}")
 
 
 @pytest.mark.parametrize("layout", [2, 1, 0])
@@ -676,7 +699,7 @@ def test_ivfpq_bulk_ties_at_the_kth_score(gpu, orc, M, d):
 
 @pytest.mark.parametrize("M,d", [(96, 768), (16, 768), (64, 256)])
 def test_round4_engine_knobs_never_change_a_result(gpu, orc, M, d):
-    """Round 4's alternatives behind engine parameters: one or two streams per search batch (overlap), finalize from the complete
+    """Round 4's alternatives behind engine parameters: finalize from the complete
     candidate row or through the K' cut (pq_final_tab 0 / 1 / 2), the size of the large-k threshold sample (pq_pre_mult / pq_pre_max).
     Every combination must return the bits of the exact kernel, for small and large k."""
     n, nlist, nq = 60000, 16, 130
@@ -688,20 +711,19 @@ def test_round4_engine_knobs_never_change_a_result(gpu, orc, M, d):
         ix.set_param("scan_kernel", 2)
         De, Ie = ix.search(q, k)
         ix.set_param("scan_kernel", 0)
-        for overlap in (1, 0):
-            for tab in (1, 2, 0):
-                for mult, mx in ((160, 16384), (8, 2048)):
-                    ix.set_param("overlap", overlap); ix.set_param("pq_final_tab", tab)
-                    ix.set_param("pq_pre_mult", mult); ix.set_param("pq_pre_max", mx)
-                    D, I = ix.search(q, k)
-                    assert_same_results(D, I, De, Ie, f"M={M} k={k} overlap={overlap} pq_final_tab={tab} sample={mult}x/{mx}")
+        for tab in (1, 2, 0):
+            for mult, mx in ((160, 16384), (8, 2048)):
+                ix.set_param("pq_final_tab", tab)
+                ix.set_param("pq_pre_mult", mult); ix.set_param("pq_pre_max", mx)
+                D, I = ix.search(q, k)
+                assert_same_results(D, I, De, Ie, f"M={M} k={k} pq_final_tab={tab} sample={mult}x/{mx}")
 
 
 @pytest.mark.parametrize("M,d,nlist", [(96, 768, 16), (16, 768, 40), (64, 256, 7), (20, 160, 16), (6, 48, 9), (128, 1024, 12)])
 def test_round6_table_build_and_grouping_forms_never_change_a_result(gpu, orc, M, d, nlist):
     """Round 6: the 8-bit tables from the matrix cores (lut_tiled 2: k_pq_lut_mfma, per-query parameters in its tail) against the VALU
-    forms (1: two passes + k_pq_qparam, 0: one workgroup per query), the pair grouping as extra workgroups of the table launch
-    (pq_group_fused) against its own launches, one stream against two — every combination returns the exact kernel's bits; batch sizes
+    form (0: one workgroup per query), the pair grouping as extra workgroups of the table launch (pq_group_fused) against its own
+    launches, the table build's first pass in the probe-pick launch or on its own (pq_lut_early) — every combination returns the exact kernel's bits; batch sizes
     around the 32-query tile of the matrix-core form, several searches in a row (the hand-over words and tile counters carry over)."""
     n = 50000
     x = gpu.synth_vectors(d, 16, 1234, 10000, 0.5, 0, n)
@@ -712,12 +734,11 @@ def test_round6_table_build_and_grouping_forms_never_change_a_result(gpu, orc, M
         ix.set_param("scan_kernel", 2)
         De, Ie = ix.search(q[:nq], k)
         ix.set_param("scan_kernel", 0)
-        for overlap, tiled, fused in ((0, 2, 1), (0, 2, 0), (1, 2, 1), (0, 1, 1), (1, 1, 0), (0, 0, 1), (0, 2, 1)):
-            ix.set_param("overlap", overlap); ix.set_param("lut_tiled", tiled); ix.set_param("pq_group_fused", fused)
-            ix.set_param("pq_lut_early", (overlap + tiled + fused) & 1)        # the table build's first pass in the probe-pick launch or on its own
+        for tiled, fused, early in ((2, 1, 1), (2, 0, 0), (2, 1, 0), (0, 1, 1), (2, 1, 1)):
+            ix.set_param("lut_tiled", tiled); ix.set_param("pq_group_fused", fused); ix.set_param("pq_lut_early", early)
             D, I = ix.search(q[:nq], k)
-            assert_same_results(D, I, De, Ie, f"M={M} nq={nq} k={k} overlap={overlap} lut_tiled={tiled} pq_group_fused={fused}")
-    ix.set_param("overlap", 0); ix.set_param("lut_tiled", 2); ix.set_param("pq_group_fused", 1); ix.set_param("pq_lut_early", 1)
+            assert_same_results(D, I, De, Ie, f"M={M} nq={nq} k={k} lut_tiled={tiled} pq_group_fused={fused} pq_lut_early={early}")
+    ix.set_param("lut_tiled", 2); ix.set_param("pq_group_fused", 1); ix.set_param("pq_lut_early", 1)
 
 
 @pytest.mark.parametrize("kind", ["ivfpq", "ivfflat"])
