@@ -1209,6 +1209,15 @@ static void search_batch(rsx_index* h, int64_t nq, const void* dq, int dtype, in
     else ivf_flat_scan(h, P, R, tm);
     select_stage(h, P, R, tm);
     finalize_stage(h, P, R, fa, tm);
+    if (!allow_fast && h->kind != KIND_IVFPQ) {
+        // the exact re-run's selection cut a run of equal scores by column: the ids of that score by id (k_exact_tie_ids)
+        ExactTieArgs ta{};
+        ta.state = h->w_state.as<uint64_t>(); ta.KP = P.KP; ta.k = P.k; ta.nq = nq; ta.temp = h->w_temp.as<float>(); ta.tstride = P.tmax;
+        ta.probe_list = h->w_probelist.as<int32_t>(); ta.seg_start = h->w_segstart.as<int64_t>(); ta.nprobe = P.nprobe;
+        ta.list_base = h->d_base.as<int64_t>(); ta.list_len = h->d_len.as<int64_t>(); ta.ids = h->ids.as<int64_t>(); ta.I = dI;
+        launch_exact_tie_ids(ta, h->st);
+        tm.mark("tie_ids");
+    }
     tm.finish();
     // (the re-run fills score rows: chunked by the budget; the fast coarse quantiser's flags are this batch's)
     if (P.fast || P.certify) rerun_uncertified(h, nq, dq, dtype, k, dD, dI, (size_t)P.tmax * 4, P.coarse_fast, pq_second_chance(h, P, R, fa));

@@ -1708,6 +1708,66 @@ __global__ __launch_bounds__(1024) void k_finalize(FinalizeArgs a) {
     }
 }
 
+// The exact path orders equal scores by id only among the K' keys its selection kept, and the selection keeps equal scores by column.
+// One workgroup per query.  Nothing to do unless the state row is full and its last key ties with the k-th: then rows of that score
+// were cut, and positions [t, k) of the result (t = the keys of a better score) take the smallest ids of ALL columns at that score,
+// one position per pass over the score row, in (id, column) order.  Rare (more than K' - k stored rows that score exactly alike): at
+// most k passes, each of which reads the row's scores once and resolves only the tied columns.
+__global__ __launch_bounds__(256) void k_exact_tie_ids(ExactTieArgs a) {
+    __shared__ int64_t s_id[4], s_col[4];
+    __shared__ int s_cnt[4];
+    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    const int64_t q = blockIdx.x;
+    const uint64_t* st = a.state + q * a.KP;
+    const uint64_t last = st[a.KP - 1];
+    const uint32_t ok = (uint32_t)(st[a.k - 1] >> 32);
+    if (last == 0 || (uint32_t)(last >> 32) != ok) return;      // (workgroup-uniform) every row of the k-th score is in the state row
+    int t = 0;
+    for (int j = tid; j < a.k; j += 256) t += (uint32_t)(st[j] >> 32) > ok;
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) t += __shfl_xor(t, off);
+    if (lane == 0) s_cnt[wv] = t;
+    __syncthreads();
+    t = (s_cnt[0] + s_cnt[1]) + (s_cnt[2] + s_cnt[3]);
+    const int64_t* ss = a.seg_start + q * (a.nprobe + 1);
+    const int64_t total = ss[a.nprobe] < a.tstride ? ss[a.nprobe] : a.tstride;
+    const float* row = a.temp + q * a.tstride;
+    int64_t prev_id = 0, prev_col = -1;
+    for (int j = t; j < a.k; j++) {
+        int64_t bid = INT64_MAX, bcol = INT64_MAX;
+        for (int64_t c = tid; c < total; c += 256) {
+            const float s = row[c] + 0.0f;
+            if (!(s > -__builtin_inff()) || f2ord(s) != ok) continue;
+            int lo = 0, hi = a.nprobe;
+            while (hi - lo > 1) { const int mid = (lo + hi) >> 1; if (ss[mid] <= c) lo = mid; else hi = mid; }
+            const int32_t l = a.probe_list[q * a.nprobe + lo];
+            if (l < 0 || c - ss[lo] >= a.list_len[l]) continue;
+            const int64_t r = a.list_base[l] + (c - ss[lo]);
+            const int64_t id = a.ids ? a.ids[r] : r;
+            const bool after = j == t || id > prev_id || (id == prev_id && c > prev_col);
+            if (after && (id < bid || (id == bid && c < bcol))) { bid = id; bcol = c; }
+        }
+#pragma unroll
+        for (int off = 32; off > 0; off >>= 1) {
+            const int64_t oid = __shfl_xor(bid, off), ocol = __shfl_xor(bcol, off);
+            if (oid < bid || (oid == bid && ocol < bcol)) { bid = oid; bcol = ocol; }
+        }
+        __syncthreads();                              // everybody has read the previous pass's words
+        if (lane == 0) { s_id[wv] = bid; s_col[wv] = bcol; }
+        __syncthreads();
+        bid = s_id[0]; bcol = s_col[0];
+#pragma unroll
+        for (int w = 1; w < 4; w++) if (s_id[w] < bid || (s_id[w] == bid && s_col[w] < bcol)) { bid = s_id[w]; bcol = s_col[w]; }
+        if (bcol == INT64_MAX) return;                // (workgroup-uniform; cannot happen: the state row alone holds k - t such columns)
+        if (tid == 0) a.I[q * a.k + j] = bid;
+        prev_id = bid; prev_col = bcol;
+    }
+}
+void launch_exact_tie_ids(const ExactTieArgs& a, hipStream_t st) {
+    if (a.nq <= 0) return;
+    hipLaunchKernelGGL(k_exact_tie_ids, dim3((unsigned)a.nq), dim3(256), 0, st, a);
+}
+
 // one wave per score-buffer column; lanes over the dimensions; fp64 accumulation of exact products
 __global__ __launch_bounds__(256) void k_exact_scores(ExactScoreArgs a) {
     const int lane = threadIdx.x & 63;

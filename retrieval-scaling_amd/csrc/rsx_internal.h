@@ -742,6 +742,16 @@ struct ExactScoreArgs {
     SqRows sq;                     // KIND_IVFSQ (launch_sq_exact_scores)
 };
 void launch_exact_scores(const ExactScoreArgs& a, hipStream_t st);
+// After the exact path's selection and finalize (IVF-Flat, IVF-SQ): the state row keeps the K' best keys of a score row by (score, COLUMN),
+// and a list's ids need not ascend with its rows (add_with_ids).  Where more rows tie at the k-th score than the state row holds, the
+// result's positions of that score are refilled with the smallest ids among ALL rows of the query's score row at that score.
+struct ExactTieArgs {
+    const uint64_t* state; int KP; int k; int64_t nq;
+    const float* temp; int64_t tstride;            // the exact score rows the state rows were selected from
+    const int32_t* probe_list; const int64_t* seg_start; int nprobe; const int64_t* list_base; const int64_t* list_len;
+    const int64_t* ids; int64_t* I;
+};
+void launch_exact_tie_ids(const ExactTieArgs& a, hipStream_t st);
 
 // k_sq.hip — IVF scalar quantiser (QT_8bit)
 // per-dimension min / max of y over n rows (y = x, or the fp32 residual x - centroids[assign] when centroids != null); mnmx: [2 d] order

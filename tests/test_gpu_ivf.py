@@ -1089,3 +1089,25 @@ def test_large_k_finalize_from_the_row_major_code_copy(gpu, orc, layout):
         D, I = jx.search(q, 1000)
         ix.set_param("scan_kernel", 2); De, Ie = ix.search(q, 1000); ix.set_param("scan_kernel", 0)
         assert_same_results(D, I, De, Ie, f"layout={layout} after save / load, k = 1000")
+
+
+@pytest.mark.parametrize("metric", [0, 1])
+def test_ivfflat_exact_rerun_orders_a_run_of_equal_scores_by_id(gpu, orc, metric):
+    """300 copies of a stored row added with DESCENDING ids (tests/sq_ref.py, set E, in fp16): more equal scores than the state row holds, so
+    the certificate sends the six queries at the copies to the exact re-run, whose selection keeps equal scores by column — the ids
+    returned must still be the smallest ones (k_exact_tie_ids)"""
+    import sq_ref
+    c = sq_ref.inputs("E")
+    x, q = c.x.astype(np.float16), c.q.astype(np.float16)
+    a, _ = orc.assign_ip(c.cen, x.astype(np.float32))
+    lm = orc.ListMajor(a, c.ids, x.astype(np.float32), c.nlist)
+    ix = gpu.IndexIVFFlat(None, c.d, c.nlist, metric)
+    ix.set_centroids(c.cen); ix.add_with_ids(x, c.ids); ix.nprobe = c.nprobe
+    for k in (10, 100):
+        Dr, Ir = orc.ivfflat_search(metric, c.cen, lm, q.astype(np.float32), c.nprobe, k)
+        assert np.isin(Ir[c.is_crowd_q][:, k - 1], c.crowd_ids).all(), "the k-th result of a crowd query is a copy"
+        for filt in (0, 2):
+            ix.set_param("ivf_filter", filt); ix.set_param("profile", 0)
+            D, I = ix.search(q, k)
+            assert ix.get_timing("fallback_queries") >= 6
+            assert_same_results(D, I, Dr, Ir, f"IVF-Flat, crowd of equal rows, metric {metric} k {k} ivf_filter {filt}")
