@@ -46,7 +46,7 @@ enum rsx_status {
 
 enum rsx_metric { RSX_METRIC_INNER_PRODUCT = 0, RSX_METRIC_L2 = 1 }; /* = faiss.METRIC_* */
 enum rsx_dtype { RSX_F32 = 0, RSX_F16 = 1 };
-enum rsx_kind { RSX_KIND_FLAT = 0, RSX_KIND_IVFFLAT = 1, RSX_KIND_IVFPQ = 2, RSX_KIND_PQ = 3, RSX_KIND_IVFSQ = 4 };
+enum rsx_kind { RSX_KIND_FLAT = 0, RSX_KIND_IVFFLAT = 1, RSX_KIND_IVFPQ = 2, RSX_KIND_PQ = 3, RSX_KIND_IVFSQ = 4, RSX_KIND_SQ = 5 };
 
 /* Thread-local message of the last error raised on the calling thread ("" if none). */
 const char* rsx_last_error(void);
@@ -105,6 +105,25 @@ int rsx_pq_create(int d, int M, int nbits, int metric, int device, rsx_index_t**
  * plus "qtype" and "by_residual".  Refused with RSX_ERR_UNSUPPORTED and a message naming the kind: selectors, rsx_remove_ids, sharded
  * handles (rsx_sharded_create, rsx_load_sharded), the two-call search, "scan_chunk". */
 int rsx_ivfsq_create(int d, int nlist, int qtype, int metric, int by_residual, int device, rsx_index_t** out);
+
+/* faiss.IndexScalarQuantizer(d, ScalarQuantizer.QT_8bit, metric) - factory "SQ8": the flat sibling of rsx_ivfsq_create, an exhaustive
+ * search over one code byte per dimension (half of what IndexFlat's fp16 rows take).  The reference has no call of it (its
+ * flat backend is faiss.IndexFlatIP, src/indicies/flat.py:42); FAISS 1.8.0: IndexScalarQuantizer, an IndexFlatCodes.  qtype must be 0
+ * (QT_8bit), any other is RSX_ERR_UNSUPPORTED.  rsx_train = the per-dimension minimum and maximum - minimum over ALL training vectors, on the
+ * GPU; rsx_add encodes (sequential ids; ids must be NULL: IndexFlatCodes has no add_with_ids); a search returns the canonical Flat scores of
+ * the queries against the DECODED vectors x^ (fp64 accumulation, rounded once; squared L2 = distance to x^), ties by id.  Batches of more
+ * than 32 queries take a certified int8 matrix-core scan (k_sq_gemm: code - 128 against two int8 planes of the scaled query, exact i32
+ * sums, staged filtered launches), exact re-score of the candidates from their decoded rows; the queries the certificate cannot clear are
+ * searched again through the one-list route and, where that cannot clear them either, exactly; smaller batches take rsx_ivfsq_create's
+ * one-list routes.  Every kernel over the one list addresses rows with 64 bits: more
+ * than 2 GiB of codes are served.  rsx_get "kind" = RSX_KIND_SQ, "code_size" = d, "qtype"; list calls see ONE list (number 0) in insertion
+ * order, uint8 [n, d]; rsx_set_sq_trained / rsx_get_sq_trained and rsx_reconstruct_batch (the key is the row) apply.  Refused with a
+ * message naming the kind: selectors, rsx_remove_ids, rsx_range_search, the two-call search, sharded handles (RSX_ERR_UNSUPPORTED);
+ * "add_list_mod", rsx_set_nprobe, rsx_assign, rsx_reserve_lists, rsx_set_centroids / rsx_get_centroids (RSX_ERR_INVALID).
+ * rsx_set_param "sqflat_cand_cap" (this kind only): keys a query's candidate row holds per stage of the scan (0 = default).
+ * rsx_get_timing: "sqflat_gemm_launches" (launches of the int8 scan), "sqflat_stages" (its filtered stages), "fallback_queries" (queries its
+ * certificate could not clear), "sqflat_exact_queries" (of those, the ones that reached the exact scores). */
+int rsx_sq_create(int d, int qtype, int metric, int device, rsx_index_t** out);
 
 /* ONE handle over several GPUs of the node, single process — SURVEY.md 8(b)/(e).  The reference's offline driver makes one
  * index.search(all_queries, k) call (src/search.py:296) and its serving tier fans a query out to shard workers over HTTP and

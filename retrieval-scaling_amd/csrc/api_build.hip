@@ -18,7 +18,7 @@ int64_t workspace_bytes(const rsx_index* h) {
                             &h->w_temp, &h->w_lut, &h->w_lutws, &h->w_state, &h->w_D, &h->w_I, &h->w_qin, &h->w_pairs, &h->w_flag, &h->w_x,
                             &h->w_partial, &h->w_assign, &h->w_dest, &h->w_idsin, &h->w_misc, &h->w_lut8, &h->w_qparam, &h->w_uncertain,
                             &h->w_fbq, &h->w_fbD, &h->w_fbI, &h->w_cand, &h->w_candcnt, &h->w_itemdesc, &h->w_tau, &h->w_excl, &h->w_state2, &h->w_addcnt, &h->w_addstart, &h->w_qitems, &h->w_tiews, &h->w_stagedir, &h->w_rlabels, &h->w_sqhi, &h->w_sqlo, &h->w_sqc, &h->sh_D, &h->sh_I, &h->sh_q,
-                            &h->sh_oD, &h->sh_oI, &h->sel_mask, &h->sel_dev, &h->codes_plain /* derived from the payload on demand, dropped by the next add */,
+                            &h->w_sqplanes, &h->w_sqs, &h->w_sqfbq, &h->w_sqfbD, &h->w_sqfbI, &h->sh_oD, &h->sh_oI, &h->sel_mask, &h->sel_dev, &h->codes_plain /* derived from the payload on demand, dropped by the next add */,
                             &h->dmap /* the direct map: derived on demand, released by every mutation (api_reconstruct.hip) */, &h->dmap_ws, &h->w_rkeys, &h->w_rout};
     int64_t t = 0;
     for (const DevBuf* b : bufs) t += (int64_t)b->bytes;
@@ -217,6 +217,18 @@ rsx_index* create_ivfsq(int d, int nlist, int qtype, int metric, int by_residual
     std::unique_ptr<rsx_index> h(create_common(KIND_IVFSQ, d, nlist, 0, 8, metric, device));
     h->sq_qtype = qtype; h->by_residual = by_residual != 0;
     h->storage_f16 = 1; h->storage_decided = true;      // (no row dtype to decide: the rows are code bytes)
+    return h.release();
+}
+
+// faiss.IndexScalarQuantizer: one list, zero centroid, no residual (rsx_index::flat_sq); trained once the quantiser's parameters are there
+rsx_index* create_flat_sq(int d, int qtype, int metric, int device) {
+    if (qtype != 0)
+        RSX_THROW(RSX_ERR_UNSUPPORTED, "IndexScalarQuantizer (kind 5): only QT_8bit (qtype 0) is implemented (got qtype %d); fp16 rows (QT_fp16) are what IndexFlat stores", qtype);
+    std::unique_ptr<rsx_index> h(create_ivfsq(d, 1, qtype, metric, 0, device));
+    h->flat_sq = true;
+    const std::vector<float> zero((size_t)d, 0.0f);
+    set_centroids(h.get(), zero.data());
+    update_trained(h.get());
     return h.release();
 }
 
@@ -484,7 +496,7 @@ void train_impl(rsx_index* h, int64_t n, const void* x, int dtype) {
     std::vector<float> cen((size_t)h->nlist * d), cb;
     DevBuf dcen;                                  // the new centroids on the device, for the PQ stage
     // ---- coarse quantiser: k-means, IP assignment, spherical centroids, niter 10, <=256 pts/centroid
-    if (h->flat_pq) {      // IndexPQ: no coarse stage — the zero centroid stays, the codebooks are trained on the vectors themselves (x - 0 = x)
+    if (h->flat_pq || h->flat_sq) {      // IndexPQ / IndexScalarQuantizer: no coarse stage — the zero centroid stays, the quantiser is trained on the vectors themselves (x - 0 = x)
         std::fill(cen.begin(), cen.end(), 0.0f);
         dcen.ensure((size_t)d * 4);
         HIPCHECK(hipMemsetAsync(dcen.p, 0, (size_t)d * 4, h->st));
@@ -778,8 +790,8 @@ rsx_index* load_impl(const char* path, int device) {
         FileHeader hd{};
         rd(f, &hd, sizeof(hd));
         if (memcmp(hd.magic, "RSX1", 4) != 0) RSX_THROW(RSX_ERR_IO, "%s is not an RSX1 index file", path);
-        if (hd.kind < 0 || hd.kind > 4) RSX_THROW(RSX_ERR_IO, "%s: unknown index kind %d", path, hd.kind);
-        h = hd.kind == 3 ? create_flat_pq(hd.d, hd.M, hd.nbits, hd.metric, device) : hd.kind == KIND_IVFSQ ? create_ivfsq(hd.d, hd.nlist, 0, hd.metric, 1, device)
+        if (hd.kind < 0 || hd.kind > 5) RSX_THROW(RSX_ERR_IO, "%s: unknown index kind %d", path, hd.kind);
+        h = hd.kind == 3 ? create_flat_pq(hd.d, hd.M, hd.nbits, hd.metric, device) : hd.kind == 5 ? create_flat_sq(hd.d, 0, hd.metric, device) : hd.kind == KIND_IVFSQ ? create_ivfsq(hd.d, hd.nlist, 0, hd.metric, 1, device)
                          : create_common(hd.kind, hd.d, hd.nlist, hd.M, hd.nbits, hd.metric, device);
         h->nprobe = hd.nprobe;
         FileHeaderV2 h2{0, 1, 0};
@@ -796,6 +808,7 @@ rsx_index* load_impl(const char* path, int device) {
             rd(f, rec, sizeof(rec)); rd(f, &nsq, 8);
             if (rec[0] != 0) RSX_THROW(RSX_ERR_IO, "scalar-quantiser record: unknown qtype %d", rec[0]);
             if (nsq != 0 && nsq != (int64_t)2 * h->d) RSX_THROW(RSX_ERR_IO, "bad scalar-quantiser block");
+            if (h->flat_sq && rec[1] != 0) RSX_THROW(RSX_ERR_IO, "scalar-quantiser record: an IndexScalarQuantizer (kind 5) has no residual");
             h->by_residual = rec[1] != 0;
             std::vector<float> sqv((size_t)nsq); rd(f, sqv.data(), (size_t)nsq * 4);
             if (nsq) set_sq_trained(h, sqv.data());

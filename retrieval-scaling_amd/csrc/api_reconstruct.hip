@@ -11,8 +11,8 @@ void release_direct_map(rsx_index* h) {
     h->dmap_type = DM_NONE; h->dmap_n = 0; h->dmap_gen = ~0ull;
 }
 
-// A Flat handle of sequential ids and an IndexPQ handle store vector i in row i: the key is the row, checked against ntotal.
-static inline bool needs_direct_map(const rsx_index* h) { return !(h->flat_pq || (h->kind == KIND_FLAT && !h->custom_ids)); }
+// A Flat handle of sequential ids, an IndexPQ and an IndexScalarQuantizer handle store vector i in row i: the key is the row, checked against ntotal.
+static inline bool needs_direct_map(const rsx_index* h) { return !(h->flat_pq || h->flat_sq || (h->kind == KIND_FLAT && !h->custom_ids)); }
 
 static void dm_alloc(rsx_index* h, size_t bytes, const char* form) {
     size_t free_b = 0, total_b = 0;

@@ -205,6 +205,7 @@ static rsx_index* sharded_load_plain(const char* path, int ndev, const int* devi
         FileHeaderV2 h2{0, 1, 0};
         if (hd.version >= 2) rd(f, &h2, sizeof(h2));
         if (hd.kind == RSX_KIND_PQ) RSX_THROW(RSX_ERR_UNSUPPORTED, "%s holds an IndexPQ (kind 3): it has no sharded form in this build", path);
+        if (hd.kind == RSX_KIND_SQ) RSX_THROW(RSX_ERR_UNSUPPORTED, "%s holds an IndexScalarQuantizer (kind 5): it has no sharded form in this build", path);
         if (hd.kind == RSX_KIND_IVFSQ) RSX_THROW(RSX_ERR_UNSUPPORTED, "%s holds an IndexIVFScalarQuantizer (kind 4): it has no sharded form in this build", path);
         if (h2.add_list_mod > 1) RSX_THROW(RSX_ERR_UNSUPPORTED, "%s is a list shard (add_list_mod = %d): it cannot be re-sharded", path, h2.add_list_mod);
         p = sharded_create(hd.kind, hd.d, hd.nlist, hd.M, hd.nbits, hd.metric, ndev, devices);

@@ -68,7 +68,7 @@ static int search_prepass_common(rsx_index_t* h, int64_t nq, const void* q, int 
 extern "C" {
 
 const char* rsx_last_error(void) { return g_err.c_str(); }
-int rsx_version(void) { return 1008; }     // 1008: rsx_vt_create, rsx_vt_set, rsx_vt_apply, rsx_vt_destroy (api_vt.hip); 1007: rsx_make_direct_map, rsx_reconstruct_batch; 1001: filtered search (rsx_selector_*, rsx_search_sel, rsx_search_prepass_sel); 1002: rsx_remove_ids; 1003: rsx_pq_create; 1004: rsx_refine; 1005: rsx_ivfsq_create; 1006: rsx_range_search, rsx_range_result_get, rsx_range_result_destroy
+int rsx_version(void) { return 1009; }     // 1009: rsx_sq_create (api_sqflat.hip); 1008: rsx_vt_create, rsx_vt_set, rsx_vt_apply, rsx_vt_destroy (api_vt.hip); 1007: rsx_make_direct_map, rsx_reconstruct_batch; 1001: filtered search (rsx_selector_*, rsx_search_sel, rsx_search_prepass_sel); 1002: rsx_remove_ids; 1003: rsx_pq_create; 1004: rsx_refine; 1005: rsx_ivfsq_create; 1006: rsx_range_search, rsx_range_result_get, rsx_range_result_destroy
 
 int rsx_device_count(int* n) {
     return guarded([&] {
@@ -95,11 +95,15 @@ int rsx_pq_create(int d, int M, int nbits, int metric, int device, rsx_index_t**
 int rsx_ivfsq_create(int d, int nlist, int qtype, int metric, int by_residual, int device, rsx_index_t** out) {
     return guarded([&] { if (!out) RSX_THROW(RSX_ERR_INVALID, "null out"); *out = create_ivfsq(d, nlist, qtype, metric, by_residual, device); });
 }
+int rsx_sq_create(int d, int qtype, int metric, int device, rsx_index_t** out) {
+    return guarded([&] { if (!out) RSX_THROW(RSX_ERR_INVALID, "null out"); *out = create_flat_sq(d, qtype, metric, device); });
+}
 int rsx_sharded_create(int kind, int d, int nlist, int M, int nbits, int metric, int ndev, const int* devices, rsx_index_t** out) {
     return guarded([&] {
         if (!out) RSX_THROW(RSX_ERR_INVALID, "null out");
         if (kind == RSX_KIND_IVFSQ) RSX_THROW(RSX_ERR_UNSUPPORTED, "sharded_create: IndexIVFScalarQuantizer (kind 4) has no sharded form in this build");
         if (kind == RSX_KIND_PQ) RSX_THROW(RSX_ERR_UNSUPPORTED, "sharded_create: IndexPQ (kind 3) has no sharded form in this build");
+        if (kind == RSX_KIND_SQ) RSX_THROW(RSX_ERR_UNSUPPORTED, "sharded_create: IndexScalarQuantizer (kind 5) has no sharded form in this build");
         if (kind != KIND_FLAT && kind != KIND_IVFFLAT && kind != KIND_IVFPQ) RSX_THROW(RSX_ERR_INVALID, "unknown index kind %d", kind);
         *out = sharded_create(kind, d, nlist, M, nbits, metric, ndev, devices);
     });
@@ -150,6 +154,7 @@ int rsx_set_centroids(rsx_index_t* h, const float* c) {
         if (!h || !c) RSX_THROW(RSX_ERR_INVALID, "null pointer");
         refuse_while_two_call(h, "set_centroids");
         refuse_flat_pq(h, RSX_ERR_INVALID, "set_centroids");
+        refuse_flat_sq(h, RSX_ERR_INVALID, "set_centroids");
         if (h->kind == KIND_FLAT) RSX_THROW(RSX_ERR_INVALID, "Flat has no centroids");
         if (h->ntotal) RSX_THROW(RSX_ERR_INVALID, "cannot replace centroids of a populated index");
         if (is_sharded(h)) {
@@ -195,6 +200,7 @@ int rsx_get_centroids(rsx_index_t* h, float* out) {
     return guarded([&] {
         if (!h || !out) RSX_THROW(RSX_ERR_INVALID, "null pointer");
         refuse_flat_pq(h, RSX_ERR_INVALID, "get_centroids");
+        refuse_flat_sq(h, RSX_ERR_INVALID, "get_centroids");
         if (is_sharded(h)) h = h->shards[0];
         if (h->h_centroids.empty()) RSX_THROW(RSX_ERR_NOT_TRAINED, "no centroids");
         memcpy(out, h->h_centroids.data(), h->h_centroids.size() * 4);
@@ -216,6 +222,7 @@ int rsx_add(rsx_index_t* h, int64_t n, const void* x, int dtype, const int64_t* 
         if (dtype != RSX_F32 && dtype != RSX_F16) RSX_THROW(RSX_ERR_INVALID, "bad dtype %d", dtype);
         if (!h->trained) RSX_THROW(RSX_ERR_NOT_TRAINED, "add before train");
         if (ids) refuse_flat_pq(h, RSX_ERR_UNSUPPORTED, "add with ids (FAISS's IndexFlatCodes has no add_with_ids)");
+        if (ids) refuse_flat_sq(h, RSX_ERR_UNSUPPORTED, "add with ids (FAISS's IndexFlatCodes has no add_with_ids)");
         if (n <= 0) return;
         if (is_sharded(h)) { sharded_add(h, n, x, dtype, ids); if (ids) h->ids_given = true; return; }
         use_device(h);
@@ -230,6 +237,7 @@ int rsx_assign(rsx_index_t* h, int64_t n, const void* x, int dtype, int64_t* lab
         if (h->kind == KIND_FLAT) RSX_THROW(RSX_ERR_INVALID, "Flat has no coarse quantiser");
         refuse_while_two_call(h, "assign");
         refuse_flat_pq(h, RSX_ERR_INVALID, "assign");
+        refuse_flat_sq(h, RSX_ERR_INVALID, "assign");
         if (is_sharded(h)) h = h->shards[0];
         if (h->h_centroids.empty()) RSX_THROW(RSX_ERR_NOT_TRAINED, "assign before train");
         use_device(h);
@@ -280,6 +288,7 @@ int rsx_reserve_lists(rsx_index_t* h, const int64_t* counts) {
         if (!h || !counts) RSX_THROW(RSX_ERR_INVALID, "null pointer");
         refuse_while_two_call(h, "reserve_lists");
         refuse_flat_pq(h, RSX_ERR_INVALID, "reserve_lists");
+        refuse_flat_sq(h, RSX_ERR_INVALID, "reserve_lists");
         if (is_sharded(h)) { sharded_reserve(h, counts); return; }
         use_device(h);
         std::vector<int64_t> need(counts, counts + h->nlist);
@@ -326,6 +335,7 @@ int rsx_set_nprobe(rsx_index_t* h, int nprobe) {
         if (!h) RSX_THROW(RSX_ERR_INVALID, "null pointer");
         refuse_while_two_call(h, "set_nprobe");
         refuse_flat_pq(h, RSX_ERR_INVALID, "set_nprobe");
+        refuse_flat_sq(h, RSX_ERR_INVALID, "set_nprobe");
         if (nprobe <= 0) RSX_THROW(RSX_ERR_INVALID, "nprobe must be positive (got %d)", nprobe);
         // FAISS accepts any nprobe and probes min(nprobe, nlist) lists; the effective value is bounded at search time
         h->nprobe = nprobe;
@@ -344,7 +354,7 @@ int rsx_search(rsx_index_t* h, int64_t nq, const void* q, int dtype, int k, floa
             return;
         }
         use_device(h);
-        search_impl(h, nq, q, dtype, k, D, I);
+        if (h->flat_sq) sqflat_search(h, nq, q, dtype, k, D, I); else search_impl(h, nq, q, dtype, k, D, I);
     });
 }
 int rsx_search_sel(rsx_index_t* h, int64_t nq, const void* q, int dtype, int k, const rsx_selector_t* sel, int nprobe_override,
@@ -356,14 +366,14 @@ int rsx_search_sel(rsx_index_t* h, int64_t nq, const void* q, int dtype, int k, 
         if (nprobe_override < 0) RSX_THROW(RSX_ERR_INVALID, "nprobe override must be positive or 0 (got %d)", nprobe_override);
         if (sel) refuse_flat_pq(h, RSX_ERR_UNSUPPORTED, "search with a selector (FAISS 1.8.0 IndexPQ::search takes no search parameters)");
         if (sel) refuse_ivfsq(h, "search with a selector");
-        SelScope sc(h, sel, h->flat_pq ? 0 : nprobe_override);
+        SelScope sc(h, sel, (h->flat_pq || h->flat_sq) ? 0 : nprobe_override);
         if (is_sharded(h)) {
             if (!h->trained) RSX_THROW(RSX_ERR_NOT_TRAINED, "search before train");
             sharded_search(h, nq, q, dtype, k, D, I);
             return;
         }
         use_device(h);
-        search_impl(h, nq, q, dtype, k, D, I);
+        if (h->flat_sq) sqflat_search(h, nq, q, dtype, k, D, I); else search_impl(h, nq, q, dtype, k, D, I);
     });
 }
 
@@ -412,6 +422,7 @@ int rsx_range_search(rsx_index_t* h, int64_t nq, const void* q, int dtype, float
         if (dtype != RSX_F32 && dtype != RSX_F16) RSX_THROW(RSX_ERR_INVALID, "range_search: bad dtype %d", dtype);
         if (nprobe_override < 0) RSX_THROW(RSX_ERR_INVALID, "range_search: nprobe override must be positive or 0 (got %d)", nprobe_override);
         if (is_sharded(h)) RSX_THROW(RSX_ERR_UNSUPPORTED, "range_search: not available on a sharded handle in this build");
+        refuse_ivfsq(h, "range_search");
         if (public_kind(h) != RSX_KIND_FLAT && public_kind(h) != RSX_KIND_IVFFLAT)
             RSX_THROW(RSX_ERR_UNSUPPORTED, "range_search: available on Flat and IVF-Flat handles only in this build (this handle's kind is %d)", public_kind(h));
         use_device(h);
@@ -629,6 +640,7 @@ int rsx_set_param(rsx_index_t* h, const char* key, double value) {
         else if (s == "add_list_mod" || s == "add_list_rem") {
             if (h->kind == KIND_FLAT) RSX_THROW(RSX_ERR_UNSUPPORTED, "%s: IVF indexes only", key);
             refuse_flat_pq(h, RSX_ERR_INVALID, key);
+            refuse_flat_sq(h, RSX_ERR_INVALID, key);
             if (h->ntotal + h->ndropped > 0) RSX_THROW(RSX_ERR_INVALID, "%s must be set before the first add", key);
             if (s == "add_list_mod") { if (value < 1) RSX_THROW(RSX_ERR_INVALID, "add_list_mod >= 1"); h->add_list_mod = (int)value; h->add_list_rem = 0; }
             else { if (value < 0 || value >= h->add_list_mod) RSX_THROW(RSX_ERR_INVALID, "0 <= add_list_rem < add_list_mod"); h->add_list_rem = (int)value; }
@@ -667,6 +679,10 @@ int rsx_set_param(rsx_index_t* h, const char* key, double value) {
         else if (s == "ivf_overflow_max") h->ivf_overflow_max = std::max(0, (int)value);
         else if (s == "flat_stages") h->flat_stages = std::max(0, (int)value);
         else if (s == "flat_cert") h->flat_cert = (int)value;
+        else if (s == "sqflat_cand_cap") {
+            if (!h->flat_sq) RSX_THROW(RSX_ERR_UNSUPPORTED, "sqflat_cand_cap: IndexScalarQuantizer (kind 5) only");
+            h->sqflat_cand_cap = std::max(0, (int)value);
+        }
         else if (s == "range_cand_cap") h->range_cand_cap = std::max(0, (int)value);
         else if (s == "profile") { h->profile = (int)value; h->timing.clear(); }
         else if (s == "temp_budget_mb") h->temp_budget = (int64_t)value << 20;

@@ -191,6 +191,14 @@ struct rsx_index {
     // KIND_IVFSQ (faiss.IndexIVFScalarQuantizer, QT_8bit; rsx_ivfsq_create): rows of ld code bytes in the IVF-Flat directory, ids
     // and (L2) norm terms of the DECODED vectors beside them; sq_trained = vmin[d] then vdiff[d]; max_norm2 is over the decoded vectors
     int sq_qtype = 0; bool by_residual = false;
+    // RSX_KIND_SQ (faiss.IndexScalarQuantizer, rsx_sq_create): stored as an IVF-SQ index of ONE list with a zero centroid and
+    // by_residual off (kind stays KIND_IVFSQ: training, encoder, list import / export, the RSX1 record, finalize and the exact re-run are
+    // shared) that reports kind 5, refuses what a flat index has not, and sends batches of more than 32 queries through the int8 GEMM scan
+    // (api_sqflat.hip)
+    bool flat_sq = false;
+    int sqflat_cand_cap = 0;                      // ... keys a query's candidate row holds per stage (0 = 32768 for K' <= 64, else 131072); read by this kind only
+    DevBuf w_sqfbq, w_sqfbD, w_sqfbI;             // ... the flagged queries of a batch and their second search's results (sqf_rerun)
+    DevBuf w_sqplanes, w_sqs;                    // ... per-batch int8 query planes and {1 / s, constant} per query (k_sqflat_planes; layout: rsx_sqflat.h)
     std::vector<float> h_sq; DevBuf d_sq;
     float sq_nvmin = 0.0f, sq_nvdiff = 0.0f;      // >= the L2 norms of vmin / vdiff (certificate terms, with the parameters)
     float sq_vdmax = 0.0f;                        // the largest vdiff_j
@@ -367,6 +375,8 @@ void update_trained(rsx_index* h);
 rsx_index* create_common(int kind, int d, int nlist, int M, int nbits, int metric, int device);
 rsx_index* create_flat_pq(int d, int M, int nbits, int metric, int device);
 rsx_index* create_ivfsq(int d, int nlist, int qtype, int metric, int by_residual, int device);
+rsx_index* create_flat_sq(int d, int qtype, int metric, int device);
+void sqflat_search(rsx_index* h, int64_t nq, const void* q, int dtype, int k, float* D, int64_t* I);      // api_sqflat.hip
 void add_all(rsx_index* h, int64_t n, const void* x, int dtype, const int64_t* ids);
 void train_impl(rsx_index* h, int64_t n, const void* x, int dtype);
 void search_impl(rsx_index* h, int64_t nq, const void* q, int dtype, int k, float* D, int64_t* I);
@@ -411,9 +421,14 @@ void launch_rm_flat_chunk(const uint32_t* mask, const int32_t* word_pre, const i
 static inline bool is_sharded(const rsx_index* h) { return !h->shards.empty(); }
 // what this build does not offer on an IndexIVFScalarQuantizer handle: the message names the kind, the handle stays untouched
 static inline void refuse_ivfsq(const rsx_index* h, const char* what) {
+    if (h && h->flat_sq) RSX_THROW(RSX_ERR_UNSUPPORTED, "%s: not available on an IndexScalarQuantizer handle (kind 5) in this build", what);
     if (h && h->kind == KIND_IVFSQ) RSX_THROW(RSX_ERR_UNSUPPORTED, "%s: not available on an IndexIVFScalarQuantizer handle (kind 4) in this build", what);
 }
-static inline int public_kind(const rsx_index* h) { return h->flat_pq ? 3 : h->kind; }      // rsx_kind as callers and files see it
+// faiss.IndexScalarQuantizer handles (rsx_index::flat_sq) have no coarse quantiser: one list, a zero centroid
+static inline void refuse_flat_sq(const rsx_index* h, int code, const char* what) {
+    if (h && h->flat_sq) RSX_THROW(code, "%s: not available on an IndexScalarQuantizer handle (kind 5: a flat scalar quantiser, one list, no coarse quantiser)", what);
+}
+static inline int public_kind(const rsx_index* h) { return h->flat_pq ? 3 : h->flat_sq ? 5 : h->kind; }      // rsx_kind as callers and files see it
 
 template <typename F>
 static inline void for_each_shard_parallel(rsx_index* h, F&& f) {

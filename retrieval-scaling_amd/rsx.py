@@ -10,6 +10,7 @@ written against `faiss`:
     faiss.IndexIVFFlat(q,d,nlist,METRIC_INNER_PRODUCT) ivf_flat.py:144   rsx.IndexIVFFlat(...)
     faiss.IndexIVFPQ(q,d,nlist,M,nbits,METRIC_IP)      ivf_pq.py:147     rsx.IndexIVFPQ(...)
     faiss.IndexPQ(d,M,nbits,METRIC_IP)    contriever/src/index.py:19     rsx.IndexPQ(...)
+    faiss.IndexScalarQuantizer(d,QT_8bit,metric)  (factory "SQ8")          rsx.IndexScalarQuantizer(...)
     faiss.IndexRefineFlat(base)           (factory "...,RFlat")          rsx.IndexRefineFlat(base)
     index.reconstruct / reconstruct_batch / reconstruct_n / search_and_reconstruct / make_direct_map
         (faiss.Index verbs; the reference's get_embs(indices))            same, decoded on the GPU
@@ -51,7 +52,7 @@ ABI_SYMBOLS = [
     "rsx_get_timing", "rsx_save", "rsx_load", "rsx_synth_vectors", "rsx_synth_queries",
     "rsx_selector_create", "rsx_selector_destroy", "rsx_selector_is_member", "rsx_search_sel", "rsx_search_prepass_sel",
     "rsx_remove_ids", "rsx_refine",
-    "rsx_ivfsq_create", "rsx_set_sq_trained", "rsx_get_sq_trained",
+    "rsx_ivfsq_create", "rsx_set_sq_trained", "rsx_get_sq_trained", "rsx_sq_create",
     "rsx_range_search", "rsx_range_result_get", "rsx_range_result_destroy",
     "rsx_make_direct_map", "rsx_reconstruct_batch",
     "rsx_vt_create", "rsx_vt_set", "rsx_vt_apply", "rsx_vt_destroy",
@@ -433,7 +434,7 @@ class Index:
 
     @property
     def storage_dtype(self):
-        if self._get("kind") == 4:
+        if self._get("kind") in (4, 5):
             return "sq8"
         return {0: "float32", 1: "float16", -1: "pq"}[self._get("storage_dtype")]
 
@@ -591,13 +592,13 @@ class Index:
 
     # -- inspection (parity tests, writer)
     def get_list(self, list_no=0):
-        """-> (payload, ids): IVFPQ payload = codes uint8 [n, M]; IVFSQ payload = codes uint8 [n, d]; Flat/IVFFlat payload = float32 [n, d]."""
+        """-> (payload, ids): IVFPQ payload = codes uint8 [n, M]; IVFSQ / IndexScalarQuantizer payload = codes uint8 [n, d]; Flat/IVFFlat payload = float32 [n, d]."""
         n = ctypes.c_int64(0)
         _check(lib().rsx_get_list(self._h, ctypes.c_int64(list_no), ctypes.byref(n), None, None))
         n = n.value
         if self._get("kind") in (2, 3):
             payload = np.empty((n, self._get("M")), dtype=np.uint8)
-        elif self._get("kind") == 4:
+        elif self._get("kind") in (4, 5):
             payload = np.empty((n, self.d), dtype=np.uint8)
         else:
             payload = np.empty((n, self.d), dtype=np.float32)
@@ -852,6 +853,48 @@ class IndexIVFScalarQuantizer(_IndexIVF):
         raise RuntimeError("search_prepass (the two-call search): not available on an IndexIVFScalarQuantizer (kind 4) in this build")
 
 
+class IndexScalarQuantizer(Index):
+    """faiss.IndexScalarQuantizer(d, qtype, metric=METRIC_L2) — factory "SQ8": a flat scalar quantiser, one code byte per dimension and no coarse
+    stage: every query scans every code (rsx_sq_create).  Only ScalarQuantizer.QT_8bit.  A search returns the exact Flat scores
+    of the queries against the DECODED vectors; batches of more than 32 queries take the certified int8 matrix-core scan.  Sequential ids:
+    no add_with_ids (FAISS's IndexFlatCodes has none).  Not in this build (each refused with a message naming the kind): selectors /
+    SearchParameters with a selector, remove_ids, range_search, the two-call search, sharded handles, IndexRefineFlat over it, FAISS-format
+    files."""
+
+    def __init__(self, d, qtype=ScalarQuantizer.QT_8bit, metric=METRIC_L2, device=None, devices=None):
+        devs = _resolve_devices(device, devices)
+        if devs is not None and len(devs) > 1:
+            raise RuntimeError("IndexScalarQuantizer (kind 5) has no sharded form in this build: name one device")
+        if devs is not None:
+            device = devs[0]
+        h = ctypes.c_void_p()
+        _check(lib().rsx_sq_create(int(d), int(qtype), int(metric), default_device() if device is None else int(device), ctypes.byref(h)))
+        super().__init__(h, int(d), int(metric))
+        self.sq = ScalarQuantizer(self)
+
+    code_size = IndexIVFScalarQuantizer.code_size
+    set_sq_trained = IndexIVFScalarQuantizer.set_sq_trained
+
+    def add_with_ids(self, x, ids):
+        raise RuntimeError("IndexScalarQuantizer (kind 5): add_with_ids not implemented for this type of index (FAISS's IndexFlatCodes has none)")
+
+    def search_prepass(self, x, k, params=None):
+        raise RuntimeError("search_prepass (the two-call search): not available on an IndexScalarQuantizer (kind 5) in this build")
+
+    def range_search(self, x, radius, *, params=None):
+        raise RuntimeError("range_search: not available on an IndexScalarQuantizer (kind 5) in this build (IndexFlat* and IndexIVFFlat only)")
+
+    def add_codes(self, codes):
+        """Bulk import of already encoded vectors (uint8 [n, d]) behind the stored ones, sequential ids (rsx_add_list, list 0)."""
+        codes = np.ascontiguousarray(codes, dtype=np.uint8)
+        assert codes.ndim == 2 and codes.shape[1] == self.d
+        n0 = self.ntotal
+        ids = np.arange(n0, n0 + len(codes), dtype=np.int64)
+        if len(codes):
+            _check(lib().rsx_add_list(self._h, ctypes.c_int64(0), ctypes.c_int64(len(codes)), codes.ctypes.data_as(ctypes.c_void_p), _F32,
+                                      ids.ctypes.data_as(ctypes.c_void_p)))
+
+
 class IndexPQ(Index):
     """faiss.IndexPQ(d, M, nbits=8, metric=METRIC_L2): a flat product quantiser — no coarse stage, every query scans every code
     (contriever/src/index.py:19, built by passage_retrieval.py --n_subquantizers; rsx_pq_create).  nbits must be 8.  `pq_layout`
@@ -916,6 +959,8 @@ class IndexRefineFlat:
     def __init__(self, base_index, k_factor=1.0):
         if isinstance(base_index, IndexIVFScalarQuantizer):
             raise RuntimeError("IndexRefineFlat: an IndexIVFScalarQuantizer base (kind 4) is not supported in this build")
+        if isinstance(base_index, IndexScalarQuantizer):
+            raise RuntimeError("IndexRefineFlat: an IndexScalarQuantizer base (kind 5) is not supported in this build")
         if not isinstance(base_index, (IndexIVFPQ, IndexPQ, IndexIVFFlat, IndexFlat)):
             raise TypeError(f"IndexRefineFlat: the base must be an IndexIVFPQ, IndexPQ, IndexIVFFlat or IndexFlat, got {type(base_index).__name__}")
         if base_index.nshards:
@@ -1042,14 +1087,14 @@ def _wrap_handle(h):
         return v.value
 
     kind, d, metric = g("kind"), g("d"), g("metric")
-    cls = {0: IndexFlat, 1: IndexIVFFlat, 2: IndexIVFPQ, 3: IndexPQ, 4: IndexIVFScalarQuantizer}[kind]
+    cls = {0: IndexFlat, 1: IndexIVFFlat, 2: IndexIVFPQ, 3: IndexPQ, 4: IndexIVFScalarQuantizer, 5: IndexScalarQuantizer}[kind]
     obj = cls.__new__(cls)
     Index.__init__(obj, h, d, metric)
     if kind in (2, 3):
         obj.M, obj.nbits = g("M"), g("nbits")
     if kind in (1, 2, 4):
         obj.quantizer = None
-    if kind == 4:
+    if kind in (4, 5):
         obj.sq = ScalarQuantizer(obj)
     return obj
 
@@ -1069,6 +1114,9 @@ def write_index(index, path):
         if isinstance(index, IndexIVFScalarQuantizer):
             raise RuntimeError("write_index: an IndexIVFScalarQuantizer (kind 4) has no FAISS-format writer in this build (RSX_INDEX_FORMAT=faiss); "
                                "unset it to write the native RSX1 container")
+        if isinstance(index, IndexScalarQuantizer):
+            raise RuntimeError("write_index: an IndexScalarQuantizer (kind 5) has no FAISS-format writer in this build (RSX_INDEX_FORMAT=faiss: "
+                               "FAISS's IxSQ record); unset it to write the native RSX1 container")
         from rsx_faiss_io import write_faiss_index
         return write_faiss_index(index, os.fspath(path))
     if isinstance(index, IndexRefineFlat):

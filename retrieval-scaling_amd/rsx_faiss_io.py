@@ -162,6 +162,9 @@ def _read_index(r):
     if cc == "IwSq":
         raise RuntimeError("FAISS IndexIVFScalarQuantizer files ('IwSq') are not read in this build: an IndexIVFScalarQuantizer (kind 4) "
                            "is persisted in the native RSX1 container only")
+    if cc == "IxSQ":
+        raise RuntimeError("FAISS IndexScalarQuantizer files ('IxSQ') are not read in this build: an IndexScalarQuantizer (kind 5) "
+                           "is persisted in the native RSX1 container only")
     raise RuntimeError(f"unsupported FAISS index type '{cc}' (supported: IxFI, IxF2, IwFl, IwPQ, IxPq, IxRF)")
 
 
@@ -267,6 +270,8 @@ def index_to_parsed(index):
                 "k_factor": float(index.k_factor)}
     if index._get("kind") == 4:
         raise RuntimeError("an IndexIVFScalarQuantizer (kind 4) has no FAISS-format writer in this build")
+    if index._get("kind") == 5:
+        raise RuntimeError("an IndexScalarQuantizer (kind 5) has no FAISS-format writer in this build")
     kind = {0: "Flat", 1: "IVFFlat", 2: "IVFPQ", 3: "PQ"}[index._get("kind")]
     p = {"kind": kind, "d": index.d, "metric": index.metric_type, "ntotal": index.ntotal,
          "is_trained": index.is_trained}
@@ -309,6 +314,8 @@ def _write_faiss_stream(index, out):
         return
     if index._get("kind") == 4:
         raise RuntimeError("an IndexIVFScalarQuantizer (kind 4) has no FAISS-format writer in this build")
+    if index._get("kind") == 5:
+        raise RuntimeError("an IndexScalarQuantizer (kind 5) has no FAISS-format writer in this build")
     kind = {0: "Flat", 1: "IVFFlat", 2: "IVFPQ", 3: "PQ"}[index._get("kind")]
     if kind in ("Flat", "PQ"):      # (an IndexPQ of 100M x 96 bytes is 9.6 GB of codes: one list, exported in one piece)
         out.write(serialize_faiss(index_to_parsed(index)))

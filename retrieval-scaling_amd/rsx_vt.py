@@ -454,7 +454,7 @@ class SearchParametersPreTransform(_r.SearchParameters):
 
 class IndexPreTransform:
     """faiss.IndexPreTransform(index) / IndexPreTransform(ltrans, index): every vector goes through `chain` (applied first to last, on the
-    GPU) before it reaches `index` — an unsharded IndexIVFPQ, IndexPQ, IndexIVFScalarQuantizer, IndexIVFFlat or IndexFlat.  What the
+    GPU) before it reaches `index` — an unsharded IndexIVFPQ, IndexPQ, IndexIVFScalarQuantizer, IndexScalarQuantizer, IndexIVFFlat or IndexFlat.  What the
     index accepts and refuses (selectors, range_search, remove_ids, add_with_ids, ...) applies unchanged.  Rotated vectors are not
     fp16-representable: a Flat or IVF-Flat base behind a transform stores fp32 rows (its widened path).  reconstruct* return the index's
     stored vector taken back through the chain, which needs every transform to be orthonormal.  IndexRefineFlat does not take an
@@ -471,7 +471,7 @@ class IndexPreTransform:
         else:
             raise TypeError("IndexPreTransform(index) or IndexPreTransform(ltrans, index)")
         if not isinstance(index, _r.Index):
-            raise TypeError(f"IndexPreTransform: the index must be an IndexIVFPQ, IndexPQ, IndexIVFScalarQuantizer, IndexIVFFlat or IndexFlat, "
+            raise TypeError(f"IndexPreTransform: the index must be an IndexIVFPQ, IndexPQ, IndexIVFScalarQuantizer, IndexScalarQuantizer, IndexIVFFlat or IndexFlat, "
                             f"got {type(index).__name__}")
         if index.nshards:
             raise RuntimeError("IndexPreTransform: a sharded index is not supported (the transform lives on one device)")
@@ -639,7 +639,7 @@ def _read_pretransform(path, device):
 def parse_index_factory(d, description):
     """The factory string as plain values (no GPU): {"transforms": [(kind, args...)], "d_index": the index's dimension, "base": (kind,
     args...), "refine": bool}.  Prefixes OPQ{M}[_{d2}], PCA{d}, PCAR{d}, RR{d}; then Flat | IVF{n},Flat | IVF{n},PQ{M}[x8] | IVF{n},SQ8 |
-    PQ{M}[x8]; an optional trailing RFlat.  Anything else raises ValueError naming the token."""
+    PQ{M}[x8] | SQ8; an optional trailing RFlat.  Anything else raises ValueError naming the token."""
     d = int(d)
     toks = [t.strip() for t in str(description).split(",")]
     if not toks or any(not t for t in toks):
@@ -699,6 +699,8 @@ def parse_index_factory(d, description):
         else:
             raise ValueError(f"index_factory: unknown token {rest[1]!r}")
         used = 2
+    elif rest[0] == "SQ8":
+        base, used = ("SQ",), 1
     elif pq(rest[0]) is not None:
         base, used = ("PQ", pq(rest[0])), 1
     else:
@@ -707,6 +709,8 @@ def parse_index_factory(d, description):
         raise ValueError(f"index_factory: unexpected token {rest[used]!r}")
     if refine and base[0] == "IVFSQ":
         raise ValueError("index_factory: token 'RFlat': IndexRefineFlat over an IndexIVFScalarQuantizer is not supported in this build")
+    if refine and base[0] == "SQ":
+        raise ValueError("index_factory: token 'RFlat': IndexRefineFlat over an IndexScalarQuantizer is not supported in this build")
     if refine and transforms:
         raise ValueError("index_factory: token 'RFlat': IndexRefineFlat over an IndexPreTransform is not supported in this build")
     return {"transforms": transforms, "d_index": cur, "base": base, "refine": refine}
@@ -720,6 +724,8 @@ def index_factory(d, description, metric=_r.METRIC_L2, device=None):
         ix = _r.IndexFlat(di, metric, device=device)
     elif base[0] == "PQ":
         ix = _r.IndexPQ(di, base[1], 8, metric, device=device)
+    elif base[0] == "SQ":
+        ix = _r.IndexScalarQuantizer(di, _r.ScalarQuantizer.QT_8bit, metric, device=device)
     elif base[0] == "IVFFlat":
         ix = _r.IndexIVFFlat(None, di, base[1], metric, device=device)
     elif base[0] == "IVFSQ":
