@@ -454,6 +454,42 @@ int rsx_range_result_destroy(rsx_range_result_t* r);
  * remove_ids), a list shard ("add_list_mod" > 1).  Refused (RSX_ERR_INVALID): NULL arguments, an open two-call search. */
 int rsx_remove_ids(rsx_index_t* h, const rsx_selector_t* sel, int64_t* nremoved);
 
+/* ---- joining and splitting indexes (ABI 1010) --------------------------- */
+/* InvertedLists::subset_type_t of FAISS 1.8.0 (invlists/InvertedLists.h). */
+enum rsx_subset_type {
+    RSX_SUBSET_TYPE_ID_RANGE = 0,          /* a1 <= id < a2 */
+    RSX_SUBSET_TYPE_ID_MOD = 1,            /* id % a1 == a2 */
+    RSX_SUBSET_TYPE_ELEMENT_RANGE = 2,     /* elements a1 .. a2 - 1 of ntotal, split evenly over the lists */
+    RSX_SUBSET_TYPE_INVLIST_FRACTION = 3,  /* refused */
+    RSX_SUBSET_TYPE_INVLIST = 4            /* refused */
+};
+
+/* dst.merge_from(src, add_id) — replaces FAISS 1.8.0's IndexIVF::merge_from (IVF-Flat, IVF-PQ in every code layout and any pair of
+ * layouts, IVF-SQ), IndexFlatCodes::merge_from (Flat with sequential ids, IndexPQ, IndexScalarQuantizer: add_id must be 0, else
+ * "cannot set ids in FlatCodes index"; src's vector i becomes id ntotal + i) and IndexIDMap::merge_from (Flat with explicit ids: both
+ * sides carry explicit ids, or dst is empty and adopts src's id mode).  Every list of src is appended behind dst's in src's order,
+ * ids stored as id + add_id, dst.ntotal grows by src.ntotal and src ends EMPTY (as after rsx_reset: trained, capacity kept).  The
+ * result is what one index that was fed everything holds: lists, ids and search results bit for bit.  Runs on the device (k_merge.hip);
+ * nothing passes through the host.  Flat / IVF-Flat: fp32 rows on either side leave dst with fp32 rows (fp16 rows are widened inside
+ * the copy).  The certificate maxima take the larger of both sides; L2 norm terms are copied.  The direct map and the row-major code
+ * copy of both handles are released.  rsx_get "explicit_ids" of dst stays 0 only when neither side had explicit ids and add_id equals
+ * dst's ntotal before the call (what sequential adds would have stored).
+ * Checked BEFORE anything is touched — a refused call leaves both handles as they were: dst != src; the same kind, d, metric, nlist,
+ * M, nbits, qtype, by_residual; both trained; centroids, codebooks and scalar-quantiser parameters BIT-EQUAL (FAISS compares the
+ * sizes only); both unsharded, on one device, outside an open two-call search, no list shard ("add_list_mod" > 1).
+ * Memory: when a list of dst overflows, dst is laid out again and dst old, dst new and src exist at once; rsx_reserve_lists on dst
+ * beforehand avoids that.  hipMemGetInfo is checked first (RSX_ERR_OOM, both handles untouched).
+ * rsx_get_timing (dst): "merge_relayouts", "merge_rows", "merge_copy_ms" (host wall time of the copy). */
+int rsx_merge_from(rsx_index_t* dst, rsx_index_t* src, int64_t add_id);
+
+/* src.copy_subset_to(dst, subset_type, a1, a2) — replaces FAISS 1.8.0's IndexIVF::copy_subset_to (InvertedLists::copy_subset_to): IVF
+ * kinds only.  src is unchanged; dst gains the selected entries of every list behind its own, in list order, ids unchanged; dst.ntotal
+ * grows by their number.  Types 0 and 1 test the stored id; type 2 is FAISS's running split over the lists in order, so consecutive
+ * (a1, a2) ranges partition every list.  Types 3 and 4 are refused (RSX_ERR_UNSUPPORTED, the message names the type); so are a1 > a2
+ * (type 0), a1 <= 0 or a2 outside [0, a1) (type 1), a range outside [0, ntotal] (type 2) (RSX_ERR_INVALID).  The compatibility rules
+ * of rsx_merge_from apply.  The per-list counts of types 0 / 1 are the call's only read-back. */
+int rsx_copy_subset_to(rsx_index_t* src, rsx_index_t* dst, int subset_type, int64_t a1, int64_t a2);
+
 /* ---- persistence ------------------------------------------------------------------- */
 
 /* faiss.write_index(index, path) / faiss.read_index(path)

@@ -95,7 +95,7 @@ void ensure_capacity(rsx_index* h, const std::vector<int64_t>& need, bool exact)
 }
 
 // Flat / IVF-Flat keep fp16 rows while every value ever added is fp16-representable, else fp32.
-static void upgrade_storage_to_f32(rsx_index* h) {
+void upgrade_storage_to_f32(rsx_index* h) {
     if (!h->storage_f16) return;
     if (h->data.p && h->total_cap > 0) {
         void* nd = nullptr;

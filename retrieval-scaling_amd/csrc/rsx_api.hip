@@ -68,7 +68,7 @@ static int search_prepass_common(rsx_index_t* h, int64_t nq, const void* q, int 
 extern "C" {
 
 const char* rsx_last_error(void) { return g_err.c_str(); }
-int rsx_version(void) { return 1009; }     // 1009: rsx_sq_create (api_sqflat.hip); 1008: rsx_vt_create, rsx_vt_set, rsx_vt_apply, rsx_vt_destroy (api_vt.hip); 1007: rsx_make_direct_map, rsx_reconstruct_batch; 1001: filtered search (rsx_selector_*, rsx_search_sel, rsx_search_prepass_sel); 1002: rsx_remove_ids; 1003: rsx_pq_create; 1004: rsx_refine; 1005: rsx_ivfsq_create; 1006: rsx_range_search, rsx_range_result_get, rsx_range_result_destroy
+int rsx_version(void) { return 1010; }     // 1010: rsx_merge_from, rsx_copy_subset_to (api_merge.hip); 1009: rsx_sq_create (api_sqflat.hip); 1008: rsx_vt_create, rsx_vt_set, rsx_vt_apply, rsx_vt_destroy (api_vt.hip); 1007: rsx_make_direct_map, rsx_reconstruct_batch; 1001: filtered search (rsx_selector_*, rsx_search_sel, rsx_search_prepass_sel); 1002: rsx_remove_ids; 1003: rsx_pq_create; 1004: rsx_refine; 1005: rsx_ivfsq_create; 1006: rsx_range_search, rsx_range_result_get, rsx_range_result_destroy
 
 int rsx_device_count(int* n) {
     return guarded([&] {
@@ -462,6 +462,13 @@ int rsx_remove_ids(rsx_index_t* h, const rsx_selector_t* sel, int64_t* nremoved)
         use_device(h);
         *nremoved = remove_impl(h, sel);
     });
+}
+
+int rsx_merge_from(rsx_index_t* dst, rsx_index_t* src, int64_t add_id) {
+    return guarded([&] { merge_from_impl(dst, src, add_id); });
+}
+int rsx_copy_subset_to(rsx_index_t* src, rsx_index_t* dst, int subset_type, int64_t a1, int64_t a2) {
+    return guarded([&] { copy_subset_impl(src, dst, subset_type, a1, a2); });
 }
 
 static std::atomic<uint64_t> g_sel_serial{0};

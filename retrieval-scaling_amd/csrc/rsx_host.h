@@ -9,6 +9,7 @@
 //   api_vt.hip       rsx_vt_*: the linear vector transform handle and its entry points (k_vt.hip)
 //   api_sharded.hip  the single-process multi-GPU handle
 //   api_remove.hip   rsx_remove_ids: the removal plan and compaction (k_remove.hip) on a handle and on the shards of one
+//   api_merge.hip    rsx_merge_from / rsx_copy_subset_to: joining and splitting indexes on one device (k_merge.hip; mapping in k_merge.h)
 //   rsx_api.hip      the extern "C" entry points
 // Host control plane only; all search arithmetic is in the k_*.hip kernels.  There is no CPU search path.
 #pragma once
@@ -399,6 +400,9 @@ void release_direct_map(rsx_index* h);
 void make_direct_map_impl(rsx_index* h, int type);
 void reconstruct_impl(rsx_index* h, int64_t n, const int64_t* keys, int fill_negative, float* out);
 int64_t sharded_remove(rsx_index* h, const rsx_selector* s);
+void upgrade_storage_to_f32(rsx_index* h);
+void merge_from_impl(rsx_index* dst, rsx_index* src, int64_t add_id);
+void copy_subset_impl(rsx_index* src, rsx_index* dst, int subset_type, int64_t a1, int64_t a2);
 
 // k_remove.hip: the removal kernels (mask: k_sel_mask, bit s = slot s is removed; slots of the moves are uint32: < 2^32 storage rows)
 namespace rsx {

@@ -56,6 +56,7 @@ ABI_SYMBOLS = [
     "rsx_range_search", "rsx_range_result_get", "rsx_range_result_destroy",
     "rsx_make_direct_map", "rsx_reconstruct_batch",
     "rsx_vt_create", "rsx_vt_set", "rsx_vt_apply", "rsx_vt_destroy",
+    "rsx_merge_from", "rsx_copy_subset_to",
 ]
 
 
@@ -476,6 +477,15 @@ class Index:
         _check(lib().rsx_remove_ids(self._h, sel._native(), ctypes.byref(n)))
         return int(n.value)
 
+    def merge_from(self, other, add_id=0):
+        """faiss.Index.merge_from(other, add_id): every entry of `other` moves behind this index's own (per list, in other's order, ids
+        stored as id + add_id) and `other` ends empty.  On the GPU, without a pass through the host (rsx_merge_from).  Both must be
+        unsharded handles of one kind on one device with bit-equal trained parameters; Flat-codes kinds (IndexFlat* of sequential ids,
+        IndexPQ, IndexScalarQuantizer) take add_id = 0 only."""
+        if not isinstance(other, Index):
+            raise TypeError(f"merge_from: the other index must be an rsx index handle, got {type(other).__name__}")
+        _check(lib().rsx_merge_from(self._h, other._h, ctypes.c_int64(int(add_id))))
+
     def search(self, x, k, *, params=None):
         """-> (D float32 [n,k], I int64 [n,k]); numpy in -> numpy out, CUDA tensor in -> CUDA tensors out.
         params: SearchParameters (Flat) / SearchParametersIVF (IVF) — a filtered search returns what the unfiltered search of an
@@ -692,6 +702,11 @@ class DirectMap:
     NoMap, Array, Hashtable = 0, 1, 2
 
 
+class InvertedLists:
+    """faiss.InvertedLists.subset_type_t: what copy_subset_to selects (rsx_subset_type)."""
+    SUBSET_TYPE_ID_RANGE, SUBSET_TYPE_ID_MOD, SUBSET_TYPE_ELEMENT_RANGE, SUBSET_TYPE_INVLIST_FRACTION, SUBSET_TYPE_INVLIST = 0, 1, 2, 3, 4
+
+
 class IndexFlat(Index):
     def __init__(self, d, metric=METRIC_L2, device=None, devices=None):
         super().__init__(_create(0, d, 1, 0, 8, metric, device, devices), int(d), int(metric))
@@ -742,6 +757,14 @@ class _IndexIVF(Index):
         counts = np.ascontiguousarray(counts, dtype=np.int64)
         assert counts.shape == (self.nlist,)
         _check(lib().rsx_reserve_lists(self._h, counts.ctypes.data_as(ctypes.c_void_p)))
+
+    def copy_subset_to(self, other, subset_type, a1, a2):
+        """faiss.IndexIVF.copy_subset_to(other, subset_type, a1, a2): `other` gains the selected entries of every list behind its own, in
+        list order and with their ids; this index is unchanged (rsx_copy_subset_to).  subset_type: InvertedLists.SUBSET_TYPE_ID_RANGE
+        (a1 <= id < a2), _ID_MOD (id % a1 == a2) or _ELEMENT_RANGE (elements a1 .. a2 - 1 of ntotal, split evenly over the lists)."""
+        if not isinstance(other, Index):
+            raise TypeError(f"copy_subset_to: the other index must be an rsx index handle, got {type(other).__name__}")
+        _check(lib().rsx_copy_subset_to(self._h, other._h, int(subset_type), ctypes.c_int64(int(a1)), ctypes.c_int64(int(a2))))
 
     def add_list(self, list_no, payload, ids):
         ids = np.ascontiguousarray(ids, dtype=np.int64)
@@ -1010,6 +1033,9 @@ class IndexRefineFlat:
 
     def remove_ids(self, x):
         raise RuntimeError("IndexRefineFlat: remove_ids not implemented for this type of index (FAISS's IndexRefine has none)")
+
+    def merge_from(self, other, add_id=0):
+        raise RuntimeError("IndexRefineFlat: merge_from not implemented for this type of index (FAISS's IndexRefine has none)")
 
     def range_search(self, x, radius, *, params=None):
         raise RuntimeError("IndexRefineFlat: range_search is not available in this build (IndexFlat* and IndexIVFFlat only)")

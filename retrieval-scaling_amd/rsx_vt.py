@@ -556,6 +556,23 @@ class IndexPreTransform:
     def remove_ids(self, x):
         return self.index.remove_ids(x)
 
+    def merge_from(self, other, add_id=0):
+        """faiss.IndexPreTransform.merge_from: forwards to the base index when both chains are bit-equal (the same transform kinds and
+        matrices); otherwise refused, with both indexes untouched."""
+        if not isinstance(other, IndexPreTransform):
+            raise RuntimeError(f"IndexPreTransform.merge_from: the other index must be an IndexPreTransform, got {type(other).__name__}")
+        if other is self:
+            raise RuntimeError("IndexPreTransform.merge_from: source and destination are the same index")
+        if len(self.chain) != len(other.chain):
+            raise RuntimeError(f"IndexPreTransform.merge_from: the chains differ in length ({len(self.chain)} and {len(other.chain)})")
+        for i, (a, b) in enumerate(zip(self.chain, other.chain)):
+            ra, rb = a._record(), b._record()
+            same = type(a) is type(b) and (ra["d_in"], ra["d_out"], bool(ra["have_bias"])) == (rb["d_in"], rb["d_out"], bool(rb["have_bias"]))
+            same = same and all(_pack_array(ra[key], F32) == _pack_array(rb[key], F32) for key in ("A", "b"))
+            if not same:
+                raise RuntimeError(f"IndexPreTransform.merge_from: transform {i} of the chains differs (kinds and matrices must be bit-equal)")
+        self.index.merge_from(other.index, add_id)
+
     def _index_params(self, params):
         if params is None:
             return None
